@@ -9,20 +9,29 @@ Melo-GAN's GAN training hot path (G + D + frozen emotion-D), B=64 per GPU, 128x2
 A "step" = one D-step (src/gan/train_gan.py:183-205) + one G-step (:211-251) on one batch of
 synthetic (B, T=256, C=128) rolls resident in HBM, including the per-step device RNG draws,
 the gradient all-reduce (N>1) and both Adam updates.  value = N*B*K / max-over-ranks wall time of
-exactly K steps (barrier + synchronize on both sides).  Beside it, "event_timing": every step of a
-second window of max(K, 64) steps between its own pair of HIP events on the engine's stream --
-median / p10 / p90 per step (median of >= 50 hipEvent-timed iterations).
+exactly K steps (barrier + synchronize on both sides); ms_per_step = that wall time / K.
 Behind the W warm-up steps (the first of them eager / capturing, the GPU mostly idle) --settle-steps (default 32) MORE untimed
 steps of the same workload are replayed before the timed window, so that a short window (the driver's K = 20) does not start
 on clocks that are still ramping (0.875 -> 0.825 ms per step over the first ~15 replays, tools/first_steps.py); the line
 reports them as `warmup_settle_steps`.
 
-The same JSON line carries
+--dump-outputs DIR: after the timed window, what its last step handed the caller goes to DIR/<name>.npy (float32/float64,
+about 28 MB): the critic's loss scalars (loss_d, critic_real_mean, critic_fake_mean, gp), the generator's (g_adv, g_emo),
+the generator step's rolls (fake_notes) and the updated G / E_num / D state_dicts (`G.<key>`, ...).  Weights, batches and
+the device RNG are seeded, so the same arguments give the same inputs on every run.
+
+A plain run does only the above.  --full adds the legs beside the headline, each after the timed window, and the same JSON
+line then also carries
+  event_timing : every step of a second window of max(K, 64) steps between its own pair of HIP events on the engine's
+                 stream -- median / p10 / p90 per step (SURVEY 8d: median of >= 50 hipEvent-timed iterations);
+  secondary    : samples/s at the reference's schedule, 5 critic updates per generator update;
+  secondary_bf16_ed : the same step with the frozen emotion discriminator stored in bf16 (N=1);
   roofline     : the dominant kernel SYMBOL (wino3_kernel: the emotion discriminator's three-tap layers by minimal
                  filtering F(2,3), 5 launches = 20.1 of the step's 56.9 algorithmic GFLOP).  The launches are recorded
                  during one step and replayed (same tensors, HIP events on the launch stream): ALGORITHMIC (direct-form)
                  FLOPs / that time, against the dense fp32-MFMA peak (157.3 TFLOP/s) -- the kernel EXECUTES 2/3 of those
-                 FLOPs on the matrix pipe, `mfma_executed_frac` is the pipe's own utilisation;
+                 FLOPs on the matrix pipe, `mfma_executed_frac` is the pipe's own utilisation (`roofline_stride2_family`:
+                 the same for the conv16 kernels);
   cpu_baseline : the oracle (PyTorch-CPU fp32 restatement of the reference step) timed on this
                  host on a bounded number of the same steps (rank 0, N=1 only): once with every physical
                  core this process may use, once with 1 thread; CPU model and counts stated.
@@ -63,6 +72,11 @@ def parse():
     ap.add_argument("--settle-steps", type=int, default=32,
                     help="further untimed steps behind the warm-up, until the GPU's clocks have settled (reported in the line)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: per-step event timing, the 5:1 schedule, roofline replays, "
+                         "the bf16 secondary configuration and the CPU baseline (off: set up, warm up, time, report)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (losses, generated rolls, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="time budget of the all-cores CPU leg (the 1-thread "
                     "leg gets the same budget and at least 2 steps)")
@@ -77,7 +91,12 @@ def parse():
                     help="gan: the headline cfg2 step (default); ae: BASELINE config 4 (VAE step, B=256, T=256, C=4); "
                          "gen1: BASELINE config 5 (batch-1 E_num->G generation latency); ed: emotion-discriminator "
                          "pre-training step (SURVEY f-2) at the cfg2 shape")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "gan":
+        ap.error("--dump-outputs is for the headline workload (--workload gan)")
+    return args
 
 
 class RecordHook:
@@ -261,6 +280,24 @@ def cpu_baseline(seconds: float):
                 value_1thread=round(v_one, 2),
                 sample_1thread=f"median of {n_one} steps, 1 thread, {el_one:.1f} s",
                 cpu_model=model, host_physical_cores=physical, usable_logical_cpus=logical)
+
+
+def dump_outputs(out_dir, eng):
+    """The last step's results as out_dir/<name>.npy (module docstring).  The frozen emotion discriminator is left out: the
+    step reads it and never writes it."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    d = eng.loss_d_out.cpu()
+    arrays = {"loss_d": d[0:1], "critic_real_mean": d[1:2], "critic_fake_mean": d[2:3], "gp": eng.gp, "g_adv": eng.adv,
+              "g_emo": eng.emo, "fake_notes": eng.notes}
+    for part, sd in eng.state_dicts().items():
+        if part != "ED":
+            arrays.update((f"{part}.{k}", v) for k, v in sd.items())
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)         # num_batches_tracked
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def side_workload(args):
@@ -457,30 +494,34 @@ def main():
             t = torch.tensor([el], device="cuda", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX, async_op=True).wait()
             el = float(t.item())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eng)
 
         # ---- per-step HIP events: a second window of >= 64 steps, each between its own event pair on the
         # engine's stream; the host runs ahead, so the events see device time only ----
-        n_ev = max(args.steps, 64)
-        evs = [ops.Event() for _ in range(n_ev + 1)]
-        evs[0].record()
-        for i in range(n_ev):
-            step(i)
-            evs[i + 1].record()
-        torch.cuda.synchronize()
-        barrier()
-        per = sorted(evs[i].elapsed_ms(evs[i + 1]) for i in range(n_ev))
-        ev_stats = [per[n_ev // 2], per[n_ev // 10], per[(9 * n_ev) // 10]]
-        if dist_on:      # the slowest rank's median (the ranks are in lock-step through the collectives anyway)
-            t = torch.tensor(ev_stats, device="cuda", dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, async_op=True).wait()
-            ev_stats = t.tolist()
-        event_timing = {"method": "hipEvent pair per step on the engine stream", "steps": n_ev,
-                        "median_ms": round(ev_stats[0], 4), "p10_ms": round(ev_stats[1], 4), "p90_ms": round(ev_stats[2], 4),
-                        "value_at_median": round(world * B_PER_GPU / (ev_stats[0] * 1e-3), 1)}
+        event_timing = None
+        if args.full:
+            n_ev = max(args.steps, 64)
+            evs = [ops.Event() for _ in range(n_ev + 1)]
+            evs[0].record()
+            for i in range(n_ev):
+                step(i)
+                evs[i + 1].record()
+            torch.cuda.synchronize()
+            barrier()
+            per = sorted(evs[i].elapsed_ms(evs[i + 1]) for i in range(n_ev))
+            ev_stats = [per[n_ev // 2], per[n_ev // 10], per[(9 * n_ev) // 10]]
+            if dist_on:      # the slowest rank's median (the ranks are in lock-step through the collectives anyway)
+                t = torch.tensor(ev_stats, device="cuda", dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, async_op=True).wait()
+                ev_stats = t.tolist()
+            event_timing = {"method": "hipEvent pair per step on the engine stream", "steps": n_ev,
+                            "median_ms": round(ev_stats[0], 4), "p10_ms": round(ev_stats[1], 4), "p90_ms": round(ev_stats[2], 4),
+                            "value_at_median": round(world * B_PER_GPU / (ev_stats[0] * 1e-3), 1)}
 
         # ---- secondary: the reference's schedule, CRITIC_ITERS = 5 critic updates per generator update ----
         sched = None
-        if args.profile_steps > 0:
+        if args.full and args.profile_steps > 0:
             iters = max(4, min(20, args.steps // 5))
             for k in range(2 * 5):
                 dp.step(use_graph, g_step=(k % 5 == 4))
@@ -504,7 +545,7 @@ def main():
 
         # ---- roofline leg: the dominant kernel's launches of one step, recorded and replayed under HIP events ----
         roof = roof2 = None
-        if rank == 0 and args.profile_steps > 0:
+        if rank == 0 and args.full and args.profile_steps > 0:
             hook = RecordHook(DOMINANT + DOMINANT_DIRECT + CONV16)
             ops.set_launch_hook(hook)
             # the production launch sequence of one step, eagerly (the hook sees every launch) -- through a LOCAL wrapper and
@@ -597,7 +638,7 @@ def main():
     # ---- secondary configuration beside the fp32 headline (BASELINE.json configs[1] names bf16): the same step with the
     # frozen emotion discriminator's activations / folded weights STORED in bf16 (fp32 accumulate); all trained state fp32 ----
     sec = None
-    if rank == 0 and world == 1 and args.ed_dtype == "fp32" and args.profile_steps > 0 and use_graph:
+    if rank == 0 and world == 1 and args.full and args.ed_dtype == "fp32" and args.profile_steps > 0 and use_graph:
         try:
             eng2 = GanEngine(cfg, ed_cfg, f"cuda:{local_rank}", B_PER_GPU, ed_dtype="bf16")
             eng2.init_weights(seed=42)
@@ -628,7 +669,7 @@ def main():
             sec = {"error": f"{type(e).__name__}: {e}"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)
     if dist_on:
         dist.barrier(async_op=True).wait()

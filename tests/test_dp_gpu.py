@@ -328,7 +328,7 @@ def test_bench_runs_to_completion_on_two_ranks():
     env = dict(os.environ, MELO_SHARE_GPU="1", MELO_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29571", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--profile-steps", "2", "--no-cpu-baseline"]
+           "--profile-steps", "2", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]

@@ -10,9 +10,9 @@ d = [json.loads(l) for l in sys.stdin.read().splitlines() if l.startswith('{\"me
 print('%-44s ms/step %.4f  event median %.4f  dp_mode %s  kernel nodes/step %s' % ('$1', d['ms_per_step'], d['event_timing']['median_ms'], d['config']['dp_mode'], d['config']['launches_per_step']))"; }
 : > $O
 for i in 1 2 3; do
-  python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --profile-steps 0 2>/dev/null | line "plain single GPU" | tee -a $O
-  MELO_FORCE_DP=1 python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --profile-steps 0 2>/dev/null | line "1-rank RCCL group, ingraph (default)" | tee -a $O
+  python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --profile-steps 0 --full 2>/dev/null | line "plain single GPU" | tee -a $O
+  MELO_FORCE_DP=1 python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --profile-steps 0 --full 2>/dev/null | line "1-rank RCCL group, ingraph (default)" | tee -a $O
 done
 for m in gather allreduce; do
-  MELO_FORCE_DP=1 MELO_DP_MODE=$m python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --profile-steps 0 2>/dev/null | line "1-rank RCCL group, $m (round-2 order)" | tee -a $O
+  MELO_FORCE_DP=1 MELO_DP_MODE=$m python3 $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --profile-steps 0 --full 2>/dev/null | line "1-rank RCCL group, $m (round-2 order)" | tee -a $O
 done

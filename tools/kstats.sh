@@ -12,8 +12,8 @@ n=0
 for cfg in "$@"; do
   (
     for kv in $cfg; do export "$kv"; done
-    python3 $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline --profile-steps 0 > $O/$n.json 2> $O/$n.err
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O/st$n -o s -- python3 $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline --profile-steps 0 > /dev/null 2>&1
+    python3 $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline --profile-steps 0 --full > $O/$n.json 2> $O/$n.err
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O/st$n -o s -- python3 $R/bench.py --steps 60 --warmup 10 --no-cpu-baseline --profile-steps 0 --full > /dev/null 2>&1
     cp $O/st$n/s_kernel_stats.csv $O/$n.csv; rm -rf $O/st$n
   )
   echo "[$n] $cfg: $(python3 -c "import json,sys; print(json.load(open('$O/$n.json'))['ms_per_step'])" 2>/dev/null)" | tee -a $O/summary.txt

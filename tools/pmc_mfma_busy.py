@@ -1,7 +1,7 @@
 """MFMA-pipe busy fraction per kernel, reconciled with the FLOP-derived roofline fraction.
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d out/pmc_mfma -o m -- \
-        python3 bench.py --no-graph --steps 6 --warmup 2 --no-cpu-baseline --profile-steps 0 --launch-flops out/launch_flops.json
+        python3 bench.py --no-graph --steps 6 --warmup 2 --no-cpu-baseline --profile-steps 0 --full --launch-flops out/launch_flops.json
     python tools/pmc_mfma_busy.py out/pmc_mfma/*/m_counter_collection.csv out/pmc_mfma/*/m_kernel_trace.csv out/launch_flops.json
 
 Three numbers per kernel symbol, per launch on average:

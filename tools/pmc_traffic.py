@@ -1,7 +1,7 @@
 """HBM bytes per launch of the dominant kernel (wino3_kernel; argv[3] = another kernel-name regex) from two rocprofv3 PMC passes (one counter per pass, as
 MI355X_MICROARCH.md's HBM section prescribes; never combined with trace domains):
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/pmc_fetch -o f -- python3 bench.py --no-graph --steps 6 --warmup 2 --no-cpu-baseline --profile-steps 0
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out/pmc_fetch -o f -- python3 bench.py --no-graph --steps 6 --warmup 2 --no-cpu-baseline --profile-steps 0 --full
     rocprofv3 --pmc WRITE_SIZE --output-format csv -d out/pmc_write -o w -- python3 bench.py --no-graph ... (same)
     python tools/pmc_traffic.py out/pmc_fetch/f_counter_collection.csv out/pmc_write/w_counter_collection.csv
 
