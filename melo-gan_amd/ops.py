@@ -382,7 +382,7 @@ def conv16(x: Tensor, wq: Tensor, y: Tensor, N: int, transposed: bool, odd: bool
     def launch():
         return lib.mg_conv16_ex(_p(x), _p(wq), _p(y), B, Tin, Cin, N, 1 if transposed else 0, Tout, Tin * Cin, Ty * N, C.byref(e),
                                 C.byref(ex), _stream())
-    rid = "true" if (stats is not None or pool is not None or perm or mix is not None) else "false"
+    rid = "true" if (stats is not None or pool is not None or perm or mix is not None or bnb is not None) else "false"
     sym = lambda: "conv16_kernel<%s,%d,%s>" % ("true" if transposed else "false", _conv16_plan(B, Tin, N, transposed)[2] // 32, rid)  # noqa: E731
     with _observe(sym, 2.0 * B * (Tin if transposed else Tout) * N * Cin * 5, launch):
         rc = launch()
