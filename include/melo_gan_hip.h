@@ -512,6 +512,25 @@ int mg_rng_fill_tick2_stage(float* normal, long n_normal, float* uniform, long n
                             int n_jobs, int n_rows, const int64_t* order, long order_len, const uint64_t* base,
                             mg_stream_t stream);
 
+/* ---- sampling from a trained generator (melo_gan_amd.gan.generate; the reference's generation route, app.py:53-65,97-110) ----
+ * mg_gen_inputs: the generator's three inputs for `rows` samples in ONE launch (replaces app.py's torch.randn noise, its
+ *   base-vector + 0.15 * torch.randn_like jitter and torch.zeros latent): for row r with key (emotion[r], sample[r])
+ *     noise[r, 0:noise_dim]   ~ N(0,1)
+ *     numeric[r, 0:num_dim]   = table[emotion[r], :] + jitter * N(0,1)     (table: n_emotions x num_dim, device)
+ *     latent[r, 0:latent_dim] = 0                                         (latent may be NULL when latent_dim is 0)
+ *   Philox4x32-10 keyed by `seed`, counter = (element block, input, emotion, sample): a sample's inputs do not depend on the
+ *   other rows, their number or their order.  A row whose emotion lies outside [0, n_emotions) is padding: zeros. */
+int mg_gen_inputs(const int32_t* emotion, const int32_t* sample, int rows, float* noise, int noise_dim, float* numeric,
+                  int num_dim, const float* table, int n_emotions, float jitter, float* latent, int latent_dim, uint64_t seed,
+                  mg_stream_t stream);
+/* mg_emotion_score: the frozen classifier's verdict on `rows` generated samples (torch.softmax(logits, 1) indexed by the
+ * target and torch.argmax(logits, 1) of the G-step's emotion loss inputs, src/gan/train_gan.py:230-240):
+ *   p_target[r] = softmax(logits[r, :])[target[r]]  (fp32, row maximum subtracted first)   pred[r] = first argmax
+ *   acc[3c + {0, 1, 2}] += {rows with target c, of them with pred == c, sum of their p_target}   (fp64, n_classes <= 32)
+ * Rows whose target lies outside [0, n_classes) are padding: p_target 0, not counted.  One block: reruns add identical sums. */
+int mg_emotion_score(const float* logits, int rows, int n_classes, const int32_t* target, float* p_target, int32_t* pred,
+                     double* acc, mg_stream_t stream);
+
 /* ---- fused flat Adam / AdamW (torch.optim.Adam defaults; src/gan/train_gan.py:136-145,
  *      src/ae/train_ae.py:79).  state: double[4] = {step, beta1^step, beta2^step, unused},
  *      advanced on device so the launch is hipGraph-replayable.  grad_scale multiplies g first

@@ -919,6 +919,12 @@ __device__ __forceinline__ void philox4(unsigned (&c)[4], unsigned k0, unsigned 
     }
 }
 __device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// four N(0,1) draws from one Philox output block (Box-Muller on the pairs (c0, c1) and (c2, c3))
+__device__ __forceinline__ void box_muller4(const unsigned (&c)[4], float (&v)[4]) {
+    const float r0 = sqrtf(-2.f * logf(u01(c[0]))), r1 = sqrtf(-2.f * logf(u01(c[2])));
+    const float t0 = 6.28318530717958647692f * u01(c[1]), t1 = 6.28318530717958647692f * u01(c[3]);
+    v[0] = r0 * cosf(t0); v[1] = r0 * sinf(t0); v[2] = r1 * cosf(t1); v[3] = r1 * sinf(t1);
+}
 
 struct RngJob { float* dst; long n; int kind; float p0; };   // kind 0: N(0,1); 1: U(0,1); 2: keep-mask*(1/(1-p0))
 struct RngJobs { RngJob j[4]; int njobs; };
@@ -991,9 +997,7 @@ __global__ void rng_fill_kernel(const RngJobs jobs, unsigned long long seed, uns
             philox4(c, (unsigned)seed, (unsigned)(seed >> 32));
             float v[4];
             if (jb.kind == 0) {
-                const float r0 = sqrtf(-2.f * logf(u01(c[0]))), r1 = sqrtf(-2.f * logf(u01(c[2])));
-                const float t0 = 6.28318530717958647692f * u01(c[1]), t1 = 6.28318530717958647692f * u01(c[3]);
-                v[0] = r0 * cosf(t0); v[1] = r0 * sinf(t0); v[2] = r1 * cosf(t1); v[3] = r1 * sinf(t1);
+                box_muller4(c, v);
             } else if (jb.kind == 1) {
                 for (int e = 0; e < 4; ++e) v[e] = u01(c[e]);
             } else {
@@ -1007,6 +1011,91 @@ __global__ void rng_fill_kernel(const RngJobs jobs, unsigned long long seed, uns
 }
 __global__ void rng_advance_kernel(unsigned long long* step_ctr) {
     if (threadIdx.x == 0 && blockIdx.x == 0) step_ctr[0] += 1;
+}
+
+// ---------------- sampling from a trained generator (gan/generate.py) ----------------
+// The generator's three inputs for one chunk, one block per row (app.py:53-65,97-103): noise ~ N(0,1), numeric =
+// table[e] + jitter * N(0,1), latent = 0.  Row r carries the key (emotion[r], sample[r]); a draw's Philox counter is
+// (element block, GEN_TAG | input, emotion, sample) under key = seed, so sample (e, k) gets the same bits whatever else the
+// chunk holds, its size or its order.  A padding row (emotion outside [0, n_emotions)) gets zeros.
+constexpr unsigned GEN_TAG = 0x47454E00u;       // keeps these counters apart from rng_fill_kernel's (stream id < 16)
+__global__ __launch_bounds__(64) void gen_inputs_kernel(const int* __restrict__ emotion, const int* __restrict__ sample,
+                                                        float* __restrict__ noise, int noise_dim, float* __restrict__ numeric,
+                                                        int num_dim, const float* __restrict__ table, int n_emotions,
+                                                        float jitter, float* __restrict__ latent, int latent_dim,
+                                                        unsigned long long seed) {
+    const int r = blockIdx.x;
+    const int e = emotion[r];
+    const bool pad = e < 0 || e >= n_emotions;
+    const float* base = table + (long)(pad ? 0 : e) * num_dim;
+    const int nb_noise = (noise_dim + 3) >> 2, nb_num = (num_dim + 3) >> 2;
+    for (int q = threadIdx.x; q < nb_noise + nb_num; q += blockDim.x) {
+        const unsigned which = q < nb_noise ? 0u : 1u;
+        const int qb = which ? q - nb_noise : q;
+        unsigned c[4] = {(unsigned)qb, GEN_TAG | which, (unsigned)e, (unsigned)sample[r]};
+        philox4(c, (unsigned)seed, (unsigned)(seed >> 32));
+        float v[4];
+        box_muller4(c, v);
+        for (int j = 0; j < 4; ++j) {
+            const int col = 4 * qb + j;
+            if (which == 0 && col < noise_dim) noise[(long)r * noise_dim + col] = pad ? 0.f : v[j];
+            if (which == 1 && col < num_dim) numeric[(long)r * num_dim + col] = pad ? 0.f : base[col] + jitter * v[j];
+        }
+    }
+    for (int j = threadIdx.x; j < latent_dim; j += blockDim.x) latent[(long)r * latent_dim + j] = 0.f;
+}
+
+// The classifier's verdict on a chunk (one block: a fixed summation order, so reruns and replays add bit-identical sums).
+// Per row: p_target = softmax(logits)[target] in fp32 with the row maximum subtracted first (torch.softmax), pred = the
+// first index of the maximum (torch.argmax; NaN counts as the maximum).  Per class c: acc[3c .. 3c+2] += {rows with target
+// c, of them predicted c, sum of their p_target} in fp64.  A row whose target lies outside [0, C) is padding: p_target 0,
+// not counted.
+constexpr int SCORE_THREADS = 256;
+__global__ __launch_bounds__(SCORE_THREADS) void emotion_score_kernel(const float* __restrict__ logits, int rows, int C,
+                                                                      const int* __restrict__ target, float* __restrict__ p_target,
+                                                                      int* __restrict__ pred, double* __restrict__ acc) {
+    __shared__ int s_t[SCORE_THREADS], s_hit[SCORE_THREADS];
+    __shared__ float s_p[SCORE_THREADS];
+    double cnt = 0.0, hits = 0.0, sum = 0.0;        // thread c < C: class c
+    for (int r0 = 0; r0 < rows; r0 += SCORE_THREADS) {
+        const int r = r0 + threadIdx.x;
+        int t = -1, hit = 0;
+        float p = 0.f;
+        if (r < rows) {
+            const float* z = logits + (long)r * C;
+            float mx = z[0];
+            int am = 0;
+            for (int j = 1; j < C; ++j) {
+                const float v = z[j];
+                if (v > mx || (isnan(v) && !isnan(mx))) { mx = v; am = j; }
+            }
+            float se = 0.f;
+            for (int j = 0; j < C; ++j) se += expf(z[j] - mx);
+            t = target[r];
+            const bool ok = t >= 0 && t < C;
+            if (ok) p = expf(z[t] - mx) / se;
+            else t = -1;
+            hit = ok && am == t;
+            p_target[r] = p;
+            pred[r] = am;
+        }
+        s_t[threadIdx.x] = t;
+        s_hit[threadIdx.x] = hit;
+        s_p[threadIdx.x] = p;
+        __syncthreads();
+        if ((int)threadIdx.x < C) {
+            const int n = min(SCORE_THREADS, rows - r0);
+            for (int i = 0; i < n; ++i)
+                if (s_t[i] == (int)threadIdx.x) { cnt += 1.0; hits += (double)s_hit[i]; sum += (double)s_p[i]; }
+        }
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < C) {
+        double* a = acc + 3 * threadIdx.x;
+        a[0] += cnt;
+        a[1] += hits;
+        a[2] += sum;
+    }
 }
 
 // ---------------- Adam ----------------
@@ -1656,6 +1745,28 @@ int mg_rng_fill(float* normal, long n_normal, float* uniform, long n_uniform, fl
                            mg_stream_t stream) {
     return rng_fill_impl(normal, n_normal, uniform, n_uniform, mask0, n_mask0, mask1, n_mask1, p_drop, seed,
                          step_counter, nullptr, nullptr, 0.f, 0.f, stream);
+}
+
+int mg_gen_inputs(const int32_t* emotion, const int32_t* sample, int rows, float* noise, int noise_dim, float* numeric,
+                  int num_dim, const float* table, int n_emotions, float jitter, float* latent, int latent_dim, uint64_t seed,
+                  mg_stream_t stream) {
+    MG_CHECK_ARG(emotion && sample && noise && numeric && table && rows > 0 && noise_dim > 0 && num_dim > 0 && n_emotions > 0 &&
+                     latent_dim >= 0 && (latent || latent_dim == 0),
+                 "mg_gen_inputs: need keys, noise, numeric and table pointers, positive sizes, and latent unless latent_dim is 0");
+    hipLaunchKernelGGL(gen_inputs_kernel, dim3((unsigned)rows), dim3(64), 0, ST, (const int*)emotion, (const int*)sample, noise,
+                       noise_dim, numeric, num_dim, table, n_emotions, jitter, latent, latent_dim, (unsigned long long)seed);
+    MG_CHECK_LAUNCH("gen_inputs");
+    return MG_OK;
+}
+
+int mg_emotion_score(const float* logits, int rows, int n_classes, const int32_t* target, float* p_target, int32_t* pred,
+                     double* acc, mg_stream_t stream) {
+    MG_CHECK_ARG(logits && target && p_target && pred && acc && rows > 0 && n_classes >= 1 && n_classes <= 32,
+                 "mg_emotion_score: need every pointer, rows > 0 and 1..32 classes");
+    hipLaunchKernelGGL(emotion_score_kernel, dim3(1), dim3(SCORE_THREADS), 0, ST, logits, rows, n_classes, (const int*)target,
+                       p_target, (int*)pred, acc);
+    MG_CHECK_LAUNCH("emotion_score");
+    return MG_OK;
 }
 
 int mg_rng_fill_tick(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0,

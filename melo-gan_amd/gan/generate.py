@@ -1,0 +1,360 @@
+#!/usr/bin/env python3
+"""Emotion-conditioned sampling from a trained generator -- the generation step that ends the reference pipeline
+(full_script.sh:33-36 runs `python -m src.gan.test_gan --emotion <e> --samples 1`, a module the reference tree does not
+hold; its only generation code left is the Flask route, app.py:53-65,92-119):
+
+    python -m melo_gan_amd.gan.generate --config config/gan_config.yaml \
+        [--ckpt <CHECKPOINT_DIR>/gan_final.pth] [--emotion happy|sad|angry|calm|all] \
+        [--samples <N_SAMPLES_PER_EMOTION>] [--out <SAMPLE_DIR>] [--seed <SEED>] [--batch 64] \
+        [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth]
+
+writes <out>/test_<emotion>_<k>.mid for k = 1..N (the reference's file names) with app.py's scale and tempo per emotion,
+and <out>/summary.json with the frozen emotion classifier's verdict on every sample when one is given.
+
+The inputs follow app.py: noise ~ N(0,1), numeric = the emotion's base vector + 0.15 * N(0,1), latent = 0.  mg_gen_inputs
+draws them on the device from a Philox counter per (emotion, sample), so a sample does not depend on what else is
+requested.  One hipGraph -- inputs -> E_num -> G (eval) [-> ED (eval) -> mg_emotion_score] -- is replayed once per chunk of
+`batch` rows; the last chunk is padded.  Every input from outside is checked on the host before any GPU use.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import config as C
+
+EMOTIONS = ("happy", "sad", "angry", "calm")          # emotion_to_index (gan/utils.py) = the classifier's class order
+# app.py:53-65 (get_gan_features): the base vector of each emotion and the jitter added to it
+EMOTION_TABLE = ((1.0, 1.0, 0.8, 0.8, 0.5, 0.5),
+                 (-1.0, -1.0, -0.5, -0.5, -0.5, -0.5),
+                 (1.0, -1.0, 1.0, 1.0, -0.8, 0.8),
+                 (-1.0, 1.0, -0.8, -0.8, 0.5, -0.5))
+JITTER = 0.15
+# app.py:109-110: (scale, bpm) per emotion; root key C, piano
+STYLE = {"happy": ("major", 140), "sad": ("minor", 70), "angry": ("minor", 160), "calm": ("major", 90)}
+DEFAULT_BATCH = 64
+
+
+class GenerateError(ValueError):
+    """A bad input of the sampler, found on the host before any GPU use."""
+
+
+def emotion_names(emotion: str) -> List[str]:
+    """--emotion: one name or 'all' (the four in class order)."""
+    e = str(emotion).lower()
+    if e == "all":
+        return list(EMOTIONS)
+    if e not in EMOTIONS:
+        raise GenerateError(f"unknown emotion {emotion!r}: expected one of {', '.join(EMOTIONS)} or all")
+    return [e]
+
+
+def check_gan_config(cfg: dict):
+    n = int(cfg.get("NUMERIC_INPUT_DIM", 6))
+    if n != len(EMOTION_TABLE[0]):
+        raise GenerateError(f"NUMERIC_INPUT_DIM = {n}: the emotion table (app.py:53-65) holds {len(EMOTION_TABLE[0])}-wide "
+                            "numeric vectors")
+
+
+def check_ed_config(ed_cfg: dict, cfg: dict):
+    """The classifier must score the four emotions and read what this generator produces."""
+    n = ed_cfg.get("n_classes", 4)
+    if n != len(EMOTIONS):
+        raise GenerateError(f"ED config: n_classes = {n}, the sampler scores the {len(EMOTIONS)} emotions {', '.join(EMOTIONS)}")
+    mode = ed_cfg.get("input_mode", "notes")
+    if mode == "notes":
+        if ed_cfg.get("note_dim", 4) != cfg["NOTE_DIM"]:
+            raise GenerateError(f"ED config: note_dim = {ed_cfg.get('note_dim', 4)} but the GAN config's NOTE_DIM = {cfg['NOTE_DIM']}")
+    elif mode == "latent":
+        if ed_cfg.get("latent_dim", 128) != cfg["LATENT_DIM"]:
+            raise GenerateError(f"ED config: latent_dim = {ed_cfg.get('latent_dim', 128)} but the GAN config's LATENT_DIM = "
+                                f"{cfg['LATENT_DIM']}")
+    else:
+        raise GenerateError(f"ED config: input_mode = {mode!r}, expected 'notes' or 'latent'")
+
+
+def check_generator_checkpoint(ck, cfg: dict, path: str = "checkpoint"):
+    """A dict with 'G' (with its BatchNorm running statistics) and 'E_num' whose tensors have the shapes the config implies."""
+    from .engine import feature_encoder_spec, generator_spec
+    if not isinstance(ck, dict) or "G" not in ck or "E_num" not in ck:
+        have = sorted(ck) if isinstance(ck, dict) else type(ck).__name__
+        raise GenerateError(f"{path}: not a generator checkpoint (needs 'G' and 'E_num'; has {have})")
+    gspec = generator_spec(int(cfg["NOISE_DIM"]), int(cfg["LATENT_DIM"]), cfg.get("INTEGRATION_MODE", "conditioning"), 512,
+                           int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg.get("ENCODER_OUT_DIM", 128)))
+    for bn, ch in (("decoder.deconv.1", 128), ("decoder.deconv.4", 64)):
+        gspec[bn + ".running_mean"] = gspec[bn + ".running_var"] = (ch,)
+    espec = feature_encoder_spec(int(cfg.get("NUMERIC_INPUT_DIM", 6)), tuple(cfg.get("ENCODER_HIDDEN", [256, 128])),
+                                 int(cfg.get("ENCODER_OUT_DIM", 128)))
+    for part, spec in (("G", gspec), ("E_num", espec)):
+        sd = ck[part]
+        for k, shape in spec.items():
+            if k not in sd:
+                raise GenerateError(f"{path}: {part} lacks {k}")
+            if tuple(sd[k].shape) != tuple(shape):
+                raise GenerateError(f"{path}: {part}.{k} has shape {tuple(sd[k].shape)}, the GAN config implies {tuple(shape)}")
+
+
+def load_checkpoint(path: str) -> dict:
+    if not os.path.isfile(path):
+        raise GenerateError(f"checkpoint {path} does not exist")
+    try:
+        return torch.load(path, map_location="cpu")
+    except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
+        raise GenerateError(f"cannot read checkpoint {path}: {e}") from e
+
+
+@dataclass
+class Samples:
+    """What Sampler.sample returns, in (emotion, k) order."""
+    emotion: List[str]
+    k: List[int]
+    notes: np.ndarray                   # (M, MAX_NOTES, NOTE_DIM)
+    p_target: Optional[np.ndarray]      # (M,) softmax probability of the requested emotion (None without a classifier)
+    pred: Optional[np.ndarray]          # (M,) the classifier's predicted class
+    summary: Dict[str, dict]            # emotion -> {n, ed_accuracy, ed_mean_p_target}
+
+
+class Sampler:
+    """One GanEngine of `batch` rows in eval mode: E_num -> G, and the frozen emotion classifier when ed_cfg is given."""
+
+    def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH):
+        from .engine import GanEngine
+        if int(batch) < 1:
+            raise GenerateError(f"batch = {batch}: must be >= 1")
+        cfg = {"LR_G": 0.0, "LR_D": 0.0, **C.with_gan_defaults(cfg, require=False)}      # the rates are never used here
+        check_gan_config(cfg)
+        self.has_ed = ed_cfg is not None
+        if self.has_ed:
+            check_ed_config(ed_cfg, cfg)
+        else:       # the engine always holds a classifier: the smallest one (latent mode), never run
+            ed_cfg = dict(input_mode="latent", latent_dim=int(cfg["LATENT_DIM"]), mlp_hidden=[256, 128], n_classes=len(EMOTIONS))
+        self.cfg, self.B = cfg, int(batch)
+        self.eng = eng = GanEngine(cfg, ed_cfg, device, self.B)
+        eng.init_weights(int(cfg.get("SEED", 42)))          # defines every parameter, the critic's unused ones included
+        d = eng.dev
+        self.keys = torch.full((2, self.B), -1, dtype=torch.int32, device=d)      # (emotion, sample) of every row
+        self.table = torch.tensor(EMOTION_TABLE, dtype=torch.float32, device=d)
+        self.p_target = torch.zeros(self.B, device=d)
+        self.pred = torch.zeros(self.B, dtype=torch.int32, device=d)
+        self.acc = torch.zeros(len(EMOTIONS), 3, dtype=torch.float64, device=d)
+        self._graph, self._graph_seed, self._warm = None, None, False
+
+    def load_generator(self, ck):
+        """G (with its BatchNorm running statistics) and E_num from a checkpoint dict or path (gan_final.pth,
+        gan_epochNNNN.pth; this trainer's or the reference's)."""
+        from .train_gan import load_generator_state
+        if isinstance(ck, (str, os.PathLike)):
+            path = str(ck)
+            ck = load_checkpoint(path)
+        else:
+            path = "checkpoint"
+        check_generator_checkpoint(ck, self.cfg, path)
+        load_generator_state(self.eng, ck)
+        self.eng.params_changed()
+
+    def load_ed(self, path: str):
+        """The frozen classifier (train_ed's ed_best.pth or a bare state_dict; spectral-norm keys folded)."""
+        from .train_gan import load_ed_checkpoint
+        if not self.has_ed:
+            raise GenerateError("this Sampler was built without an ED config")
+        if not os.path.isfile(path):
+            raise GenerateError(f"ED checkpoint {path} does not exist")
+        load_ed_checkpoint(self.eng, path)
+
+    def _launches(self, seed: int):
+        from .. import ops
+        eng = self.eng
+        ops.gen_inputs(self.keys[0], self.keys[1], eng.noise, eng.numeric, self.table, JITTER,
+                       eng.latent if eng.latent_dim > 0 else None, seed)
+        eng._e_fwd(False, "g", gin=True)
+        eng._g_fwd(eng.notes, False, "g")
+        if self.has_ed:
+            eng._ed_fwd(eng.notes)
+            ops.emotion_score(eng.logits, self.keys[0], self.p_target, self.pred, self.acc)
+
+    def _graph_for(self, seed: int):
+        """The chunk graph of this seed (the seed is a launch argument): captured on first use, after one eager run that
+        allocates every workspace."""
+        from .. import ops
+        if self._graph is not None and self._graph_seed == seed:
+            return self._graph
+        if not self._warm:
+            self._launches(seed)
+            self._warm = True
+        torch.cuda.synchronize()
+        g = ops.Graph()
+        g.begin()
+        try:
+            self._launches(seed)
+        finally:
+            g.end()
+        self._graph, self._graph_seed = g, seed
+        return g
+
+    def sample(self, emotions: Sequence[str], samples: int, seed: int) -> Samples:
+        names = []
+        for e in emotions:
+            for n in emotion_names(e):
+                if n not in names:
+                    names.append(n)
+        if int(samples) < 1:
+            raise GenerateError(f"samples = {samples}: must be >= 1")
+        keys = [(EMOTIONS.index(e), k) for e in names for k in range(1, int(samples) + 1)]
+        M, B, eng = len(keys), self.B, self.eng
+        notes = np.empty((M, eng.T, eng.C), np.float32)
+        p = np.empty(M, np.float32) if self.has_ed else None
+        pred = np.empty(M, np.int64) if self.has_ed else None
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        with torch.cuda.stream(eng.stream):
+            g = self._graph_for(seed)
+            self.acc.zero_()
+            for c0 in range(0, M, B):
+                chunk = keys[c0:c0 + B]
+                n = len(chunk)
+                host = torch.full((2, B), -1, dtype=torch.int32)
+                host[:, :n] = torch.tensor(chunk, dtype=torch.int32).t()
+                host[1, n:] = 0
+                self.keys.copy_(host)
+                g.launch()
+                notes[c0:c0 + n] = eng.notes[:n].cpu().numpy()         # synchronises the stream
+                if self.has_ed:
+                    p[c0:c0 + n] = self.p_target[:n].cpu().numpy()
+                    pred[c0:c0 + n] = self.pred[:n].cpu().numpy()
+            acc = self.acc.cpu().numpy()
+        summary = {}
+        for e in names:
+            cnt, hits, sp = acc[EMOTIONS.index(e)]
+            summary[e] = {"n": int(samples),
+                          "ed_accuracy": float(hits / cnt) if self.has_ed else None,
+                          "ed_mean_p_target": float(sp / cnt) if self.has_ed else None}
+        return Samples([EMOTIONS[e] for e, _ in keys], [k for _, k in keys], notes, p, pred, summary)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CLI
+# ---------------------------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m melo_gan_amd.gan.generate",
+                                 description="Emotion-conditioned MIDI samples from a trained generator.")
+    ap.add_argument("--config", type=str, default="config/gan_config.yaml", help="Path to the main GAN config")
+    ap.add_argument("--ckpt", type=str, default=None, help="generator checkpoint (default <CHECKPOINT_DIR>/gan_final.pth)")
+    ap.add_argument("--emotion", type=str, default="all", help="happy, sad, angry, calm or all")
+    ap.add_argument("--samples", type=int, default=None, help="samples per emotion (default N_SAMPLES_PER_EMOTION)")
+    ap.add_argument("--out", type=str, default=None, help="output directory (default SAMPLE_DIR)")
+    ap.add_argument("--seed", type=int, default=None, help="sampling seed (default SEED)")
+    ap.add_argument("--batch", type=int, default=DEFAULT_BATCH, help="rows per replayed chunk")
+    ap.add_argument("--ed_config", type=str, default=None, help="ED config of the classifier that scores the samples")
+    ap.add_argument("--ed_ckpt", type=str, default=None, help="ED checkpoint (ed_best.pth)")
+    return ap.parse_args(argv)
+
+
+@dataclass
+class Plan:
+    cfg: dict
+    ed_cfg: Optional[dict]
+    ckpt_path: str
+    ckpt: dict
+    ed_ckpt: Optional[str]
+    emotions: List[str]
+    samples: int
+    out: str
+    seed: int
+    batch: int
+
+
+def _read_config(path: str, what: str) -> dict:
+    if not os.path.isfile(path):
+        raise GenerateError(f"{what} {path} does not exist")
+    cfg = C.load_config(path)
+    if not isinstance(cfg, dict):
+        raise GenerateError(f"{what} {path} is not a YAML mapping")
+    return cfg
+
+
+def plan(args) -> Plan:
+    """Every check of what comes from outside, on the host (no GPU needed); raises GenerateError."""
+    emotions = emotion_names(args.emotion)
+    if args.batch < 1:
+        raise GenerateError(f"--batch {args.batch}: must be >= 1")
+    cfg = C.with_gan_defaults(_read_config(args.config, "config"), require=False)
+    missing = [k for k in ("NOISE_DIM", "LATENT_DIM", "MAX_NOTES", "NOTE_DIM") if k not in cfg]
+    if missing:
+        raise GenerateError(f"config {args.config} lacks {', '.join(missing)}")
+    samples = args.samples if args.samples is not None else int(cfg.get("N_SAMPLES_PER_EMOTION", 2))
+    if samples < 1:
+        raise GenerateError(f"--samples {samples}: must be >= 1")
+    check_gan_config(cfg)
+    if int(cfg["NOTE_DIM"]) != 4:
+        raise GenerateError(f"NOTE_DIM = {cfg['NOTE_DIM']}: the MIDI writer reads (pitch, velocity, duration, step) rows")
+    if args.ed_ckpt is not None and args.ed_config is None:
+        raise GenerateError("--ed_ckpt needs --ed_config (the classifier's architecture)")
+    if args.ed_config is not None and args.ed_ckpt is None:
+        raise GenerateError("--ed_config needs --ed_ckpt (an untrained classifier's verdict means nothing)")
+    ckpt_path = args.ckpt or os.path.join(cfg.get("CHECKPOINT_DIR", "experiments/gan/checkpoints"), "gan_final.pth")
+    ckpt = load_checkpoint(ckpt_path)
+    check_generator_checkpoint(ckpt, cfg, ckpt_path)
+    ed_cfg = None
+    if args.ed_config is not None:
+        ed_cfg = _read_config(args.ed_config, "ED config")
+        check_ed_config(ed_cfg, cfg)
+        if not os.path.isfile(args.ed_ckpt):
+            raise GenerateError(f"ED checkpoint {args.ed_ckpt} does not exist")
+    out = args.out or cfg.get("SAMPLE_DIR", "experiments/gan/samples")
+    seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
+    return Plan(cfg, ed_cfg, ckpt_path, ckpt, args.ed_ckpt, emotions, samples, out, seed, args.batch)
+
+
+def midi_name(emotion: str, k: int) -> str:
+    return f"test_{emotion}_{k}.mid"
+
+
+def write_outputs(p: Plan, res: Samples) -> dict:
+    from .. import midi
+    os.makedirs(p.out, exist_ok=True)
+    files = []
+    for i, (e, k) in enumerate(zip(res.emotion, res.k)):
+        scale, bpm = STYLE[e]
+        midi.save_piano_roll_to_midi(res.notes[i], os.path.join(p.out, midi_name(e, k)), bpm=bpm, scale=scale, root_key=0,
+                                     instrument_name="Acoustic Grand Piano")
+        files.append({"file": midi_name(e, k), "emotion": e, "k": k,
+                      "ed_pred": None if res.pred is None else EMOTIONS[int(res.pred[i])],
+                      "ed_p_target": None if res.p_target is None else float(res.p_target[i])})
+    summary = {"checkpoint": p.ckpt_path, "ed_checkpoint": p.ed_ckpt, "seed": p.seed, "samples": p.samples,
+               "batch": p.batch, "emotions": p.emotions, "per_emotion": res.summary, "files": files}
+    with open(os.path.join(p.out, "summary.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    return summary
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    try:
+        p = plan(args)
+    except GenerateError as e:
+        print(f"generate: error: {e}", file=sys.stderr)
+        return 2
+    if not torch.cuda.is_available():
+        raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+    sampler = Sampler(p.cfg, p.ed_cfg, "cuda", p.batch)
+    sampler.load_generator(p.ckpt)
+    if p.ed_cfg is not None:
+        sampler.load_ed(p.ed_ckpt)
+    res = sampler.sample(p.emotions, p.samples, p.seed)
+    write_outputs(p, res)
+    fmt = lambda v, spec: "-" if v is None else format(v, spec)  # noqa: E731
+    print(f"{'emotion':<8} {'n':>4} {'ed_accuracy':>12} {'ed_mean_p_target':>17}")
+    for e, s in res.summary.items():
+        print(f"{e:<8} {s['n']:>4} {fmt(s['ed_accuracy'], '.3f'):>12} {fmt(s['ed_mean_p_target'], '.4f'):>17}")
+    print(f"wrote {len(res.emotion)} MIDI files and summary.json to {p.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -156,6 +156,14 @@ def load_adam_state_dict(fp, sd: dict):
     fp.state[0], fp.state[1], fp.state[2] = step, float(b1) ** step, float(b2) ** step
 
 
+def load_generator_state(eng: GanEngine, ck: dict):
+    """G (with its BatchNorm running statistics) and E_num of a checkpoint dict -- gan_final.pth or gan_epochNNNN.pth, of
+    this trainer or the reference's.  The caller runs eng.params_changed() once everything is loaded."""
+    eng.GE.load({**{"G." + k: v for k, v in ck["G"].items()}, **{"E." + k: v for k, v in ck["E_num"].items()}})
+    for k in eng.Gbuf:
+        eng.Gbuf[k].copy_(ck["G"][k].float())
+
+
 def resume_checkpoint(eng: GanEngine, path: str) -> int:
     """Continue from a gan_epochNNNN.pth written by save_checkpoint (or by the reference trainer, train_gan.py:267-276):
     G (with its BatchNorm buffers), D, E_num, both optimisers.  Returns the epoch the checkpoint was written after."""
@@ -163,10 +171,8 @@ def resume_checkpoint(eng: GanEngine, path: str) -> int:
     for key in ("G", "D", "E_num", "opt_G", "opt_D"):
         if key not in ck:
             raise KeyError(f"{path}: not a full training checkpoint (no '{key}')")
-    eng.GE.load({**{"G." + k: v for k, v in ck["G"].items()}, **{"E." + k: v for k, v in ck["E_num"].items()}})
+    load_generator_state(eng, ck)
     eng.D.load(ck["D"])
-    for k in eng.Gbuf:
-        eng.Gbuf[k].copy_(ck["G"][k].float())
     nbt = [v for k, v in ck["G"].items() if k.endswith("num_batches_tracked")]
     if nbt:
         eng.num_batches_tracked = int(nbt[0])

@@ -1373,6 +1373,44 @@ def rng_fill(normal, uniform, mask0, mask1, p_drop, seed, step_counter, tick_sta
                                  n(mask1), p_drop, seed & 0xFFFFFFFFFFFFFFFF, _p(step_counter), _stream()), "mg_rng_fill")
 
 
+def gen_inputs(emotion, sample, noise, numeric, table, jitter, latent, seed):
+    """The generator's inputs for one chunk of samples (mg_gen_inputs): row r has the key (emotion[r], sample[r]) (int32
+    device vectors; emotion -1 = a padding row, written with zeros); noise (rows, noise_dim) ~ N(0,1), numeric (rows, D) =
+    table[emotion] + jitter * N(0,1) with table (n_emotions, D), latent (rows, latent_dim) = 0 (None: no latent input)."""
+    _chk(emotion, "emotion", dtype=torch.int32)
+    rows = emotion.numel()
+    _chk(sample, "sample", (rows,), torch.int32)
+    _chk(noise, "noise")
+    _chk(table, "table")
+    if noise.dim() != 2 or noise.shape[0] != rows or table.dim() != 2:
+        raise ValueError("gen_inputs: noise (rows, noise_dim) and table (n_emotions, D) expected")
+    _chk(numeric, "numeric", (rows, table.shape[1]))
+    latent_dim = 0
+    if latent is not None:
+        _chk(latent, "latent")
+        if latent.dim() != 2 or latent.shape[0] != rows:
+            raise ValueError("gen_inputs: latent (rows, latent_dim) expected")
+        latent_dim = latent.shape[1]
+    L.check(L.load().mg_gen_inputs(_p(emotion), _p(sample), rows, _p(noise), noise.shape[1], _p(numeric), table.shape[1], _p(table),
+                                   table.shape[0], float(jitter), _p(latent), latent_dim, int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
+            "mg_gen_inputs")
+
+
+def emotion_score(logits, target, p_target, pred, acc):
+    """The classifier's verdict (mg_emotion_score): p_target[r] = softmax(logits[r])[target[r]], pred[r] = argmax(logits[r]),
+    acc (n_classes, 3) fp64 += per class {rows, hits, sum of p_target}.  target int32 (rows,); -1 = a padding row."""
+    _chk(logits, "logits")
+    if logits.dim() != 2:
+        raise ValueError("emotion_score: logits (rows, n_classes) expected")
+    rows, nc = logits.shape
+    _chk(target, "target", (rows,), torch.int32)
+    _chk(p_target, "p_target", (rows,))
+    _chk(pred, "pred", (rows,), torch.int32)
+    _chk(acc, "acc", (nc, 3), torch.float64)
+    L.check(L.load().mg_emotion_score(_p(logits), rows, nc, _p(target), _p(p_target), _p(pred), _p(acc), _stream()),
+            "mg_emotion_score")
+
+
 def wq_table(entries):
     """ctypes table for adam_flat(wq=...): entries = [(start, N, Cc, K, w_sn, w_sc, dst tensor), ...] (mg_wq_entry)."""
     if len(entries) > L.MAX_WQ_ENTRIES:
