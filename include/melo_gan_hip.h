@@ -74,17 +74,16 @@ const char* mg_last_error(void);
  *   work/work_bytes: optional scratch (mg_conv_workspace_bytes(B, Tout, N)); when given and the output
  *   tiling alone would leave most CUs idle, the channel reduction is split over workgroups into partial
  *   slabs that a second kernel sums in fixed order before the epilogue.  NULL => never split.
+ *   lds_pad: 0..120 KiB of extra LDS per workgroup, i.e. fewer resident workgroups per CU (ignored where it would take
+ *   the launch past 160 KiB, and by the thin route).  For a branch that runs on a side stream beside the step's critical
+ *   path (the frozen emotion discriminator): its 1024-workgroup convolutions otherwise fill every CU's registers and the
+ *   critical path's small dependent kernels wait for their workgroups to retire.  0: the default occupancy.
  */
 size_t mg_conv_workspace_bytes(int B, int Tout, int N);
-/* Launch hint for the window-GEMM launches that FOLLOW (process-wide, baked into a hipGraph at capture): `bytes` of extra LDS per
- * workgroup, i.e. fewer resident workgroups per CU.  For a branch that runs on a side stream beside the step's critical path
- * (the frozen emotion discriminator): its 1024-workgroup convolutions otherwise fill every CU's registers and the critical
- * path's small dependent kernels wait for their workgroups to retire.  0 restores the default. */
-int mg_conv_set_lds_pad(long bytes);
 int mg_conv1d_gather(const float* x, const float* w, float* y,
                      int B, int Tin, int Cin, int N, int K, int stride, int flip,
                      int w_sn, int w_sc, long xbs, long ybs,
-                     const mg_epilogue* epi, void* work, size_t work_bytes, mg_stream_t stream);
+                     const mg_epilogue* epi, void* work, size_t work_bytes, long lds_pad, mg_stream_t stream);
 
 /* mg_conv1d_scatter2: stride-2, K=5, padding 2, output_padding 1 transposed convolution
  *   y[b,t,n] = EPI( sum_{k,c : t+2-k even} x[b,(t+2-k)/2,c] * W(n,c,k) ),  t < Tout,
@@ -236,11 +235,11 @@ int mg_linear_perm(const float* x, const float* w, float* y, int M, int K, int N
  *                     (forward: w (N,Cin,3), w_sn = 3 Cin, w_sc = 3; data gradient of a Conv1d whose weight is (Cout,Cin,3):
  *                     N = Cin, "Cin" = Cout, w_sn = 3, w_sc = 3 Cin_conv, flip = 1).  Cin % 4 == 0.
  *   mg_conv1d_wino3:  y[b,t,n] = EPI( sum_{k,c} x[b, t+k-1, c] * g_k(n,c) ), x (B,T,Cin) and y (B,T,N) dense, 16-byte aligned;
- *                     T even, Cin % 16 == 0, N % 64 == 0 (mg_conv1d_wino3_supported).  Honours mg_conv_set_lds_pad. */
+ *                     T even, Cin % 16 == 0, N % 64 == 0 (mg_conv1d_wino3_supported).  lds_pad: as for mg_conv1d_gather. */
 int mg_conv1d_wino3_supported(int B, int T, int Cin, int N);
 int mg_wino3_weights(const float* w, float* wt, int N, int Cin, long w_sn, long w_sc, int flip, mg_stream_t stream);
 int mg_conv1d_wino3(const float* x, const float* wt, float* y, int B, int T, int Cin, int N, const mg_epilogue* epi,
-                    mg_stream_t stream);
+                    long lds_pad, mg_stream_t stream);
 /* mg_wino3_weights for several filters in ONE launch (a network in training transforms all its layers' weights, forward and
  * data-gradient images, at the top of every step: emotion_discriminator/engine.py) */
 #define MG_MAX_WINO_WJOBS 8

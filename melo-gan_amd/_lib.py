@@ -79,8 +79,7 @@ SIGNATURES = {
     "mg_version": (i32, []),
     "mg_last_error": (C.c_char_p, []),
     "mg_conv_workspace_bytes": (sz, [i32, i32, i32]),
-    "mg_conv_set_lds_pad": (i32, [i64]),
-    "mg_conv1d_gather": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), vp, sz, vp]),
+    "mg_conv1d_gather": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), vp, sz, i64, vp]),
     "mg_conv1d_scatter2": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), vp, sz, vp]),
     "mg_wq_relayout": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "mg_conv16_supported": (i32, [i32, i32, i32, i32, i32, i32]),
@@ -131,7 +130,7 @@ SIGNATURES = {
     "mg_spectral_norm_bwd": (i32, [vp, i32, vp]),
     "mg_conv1d_wino3_supported": (i32, [i32, i32, i32, i32]),
     "mg_wino3_weights": (i32, [vp, vp, i32, i32, i64, i64, i32, vp]),
-    "mg_conv1d_wino3": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "mg_conv1d_wino3": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
     "mg_wino3_weights_multi": (i32, [vp, i32, vp]),
     "mg_gp_interp": (i32, [vp, vp, vp, vp, i32, i64, vp]),
     "mg_gp_penalty": (i32, [vp, vp, vp, vp, f32, i32, i64, vp]),

@@ -24,8 +24,6 @@
 
 namespace {
 
-long g_conv_lds_pad = 0;      // mg_conv_set_lds_pad
-
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // -DMG_STAMPS: debug build that records wall-clock stamps (100 MHz) of workgroup phases; see tools/conv_stamps.py
@@ -642,8 +640,11 @@ __global__ void conv_finish_kernel(const float* __restrict__ part, float* __rest
     }
 }
 
+// lds_pad: extra LDS per workgroup = fewer resident workgroups per CU, for launches that run BESIDE another stream's
+// critical path (the frozen emotion discriminator's branch): they leave wave slots, registers and LDS to it.  A pad that
+// would take the launch past 160 KiB is ignored.
 template <int S, int K, bool TR2, int TM, int TN>
-int launch_cfg(const ConvP& p0, hipStream_t stream) {
+int launch_cfg(const ConvP& p0, long lds_pad, hipStream_t stream) {
     ConvP p = p0;
     constexpr int BM = 64 * TM, BN = 64 * TN;
     constexpr int BKC = ChunkOf<K>::value, SX = BKC + 4;
@@ -660,9 +661,7 @@ int launch_cfg(const ConvP& p0, hipStream_t stream) {
     constexpr int PP = (BN + (K == 5 ? 5 : K == 3 ? 3 : 1)) * 4;     // the larger (padded, CNK) weight plane of the kernel
     const size_t lds1 = ((size_t)TB * R * SX + (size_t)(BKC / 4) * K * PP) * sizeof(float);
     size_t lds = 2 * lds1 + 256 * 4 * sizeof(float);   // two buffers + the per-thread staging sink
-    // mg_conv_set_lds_pad: extra LDS per workgroup = fewer resident workgroups per CU, for launches that run BESIDE another
-    // stream's critical path (the frozen emotion discriminator's branch): they leave wave slots, registers and LDS to it
-    if (g_conv_lds_pad > 0 && lds + (size_t)g_conv_lds_pad <= 160 * 1024) lds += (size_t)g_conv_lds_pad;
+    if (lds_pad > 0 && lds + (size_t)lds_pad <= 160 * 1024) lds += (size_t)lds_pad;
     if (lds > 160 * 1024) {
         mg_set_error("conv_wgemm: LDS request %zu too large", lds);
         return MG_EUNSUP;
@@ -738,11 +737,11 @@ int scatter_tile(long m_total, int N) {
 }
 
 template <int S, int K>
-int launch_gather(const ConvP& p, hipStream_t stream) {
+int launch_gather(const ConvP& p, long lds_pad, hipStream_t stream) {
     switch (gather_tile((long)p.B * p.Tm, p.N)) {
-        case 22: return launch_cfg<S, K, false, 2, 2>(p, stream);
-        case 12: return launch_cfg<S, K, false, 1, 2>(p, stream);
-        default: return launch_cfg<S, K, false, 1, 1>(p, stream);
+        case 22: return launch_cfg<S, K, false, 2, 2>(p, lds_pad, stream);
+        case 12: return launch_cfg<S, K, false, 1, 2>(p, lds_pad, stream);
+        default: return launch_cfg<S, K, false, 1, 1>(p, lds_pad, stream);
     }
 }
 
@@ -769,8 +768,9 @@ int fill_epilogue(ConvP& p, const mg_epilogue* epi) {
 
 extern "C" int mg_conv1d_gather(const float* x, const float* w, float* y, int B, int Tin, int Cin, int N, int K,
                                 int stride, int flip, int w_sn, int w_sc, long xbs, long ybs,
-                                const mg_epilogue* epi, void* work, size_t work_bytes, mg_stream_t stream) {
+                                const mg_epilogue* epi, void* work, size_t work_bytes, long lds_pad, mg_stream_t stream) {
     MG_CHECK_ARG(x && w && y, "mg_conv1d_gather: null tensor");
+    MG_CHECK_ARG(lds_pad >= 0 && lds_pad <= 120 * 1024, "mg_conv1d_gather: lds_pad %ld outside 0..120 KiB", lds_pad);
     MG_CHECK_ARG(B > 0 && Tin > 0 && Cin > 0 && N > 0, "mg_conv1d_gather: bad shape B=%d Tin=%d Cin=%d N=%d", B, Tin, Cin, N);
     MG_CHECK_ARG(K == 1 || K == 3 || K == 5, "mg_conv1d_gather: K=%d unsupported", K);
     MG_CHECK_ARG(stride == 1 || stride == 2, "mg_conv1d_gather: stride=%d unsupported", stride);
@@ -796,11 +796,11 @@ extern "C" int mg_conv1d_gather(const float* x, const float* w, float* y, int B,
         if (rc != MG_EUNSUP) return rc;
     }
     if (stride == 1) {
-        if (K == 1) return launch_gather<1, 1>(p, s);
-        if (K == 3) return launch_gather<1, 3>(p, s);
-        return launch_gather<1, 5>(p, s);
+        if (K == 1) return launch_gather<1, 1>(p, lds_pad, s);
+        if (K == 3) return launch_gather<1, 3>(p, lds_pad, s);
+        return launch_gather<1, 5>(p, lds_pad, s);
     }
-    if (K == 5) return launch_gather<2, 5>(p, s);
+    if (K == 5) return launch_gather<2, 5>(p, lds_pad, s);
     mg_set_error("mg_conv1d_gather: stride 2 needs K=5");
     return MG_EUNSUP;
 }
@@ -821,7 +821,7 @@ int mg_conv_linear_perm(const float* x, const float* w, float* y, int M, int K, 
     { const long xb = (long)M * K * 4; p.x_bytes = xb < (1L << 31) ? xb : 0; }
     { const long wb = ((long)(N - 1) * w_sn + K) * 4; p.w_bytes = wb < (1L << 31) ? wb : 0; }
     if (int rc = fill_epilogue(p, epi)) return rc;
-    return launch_gather<1, 1>(p, stream);
+    return launch_gather<1, 1>(p, 0, stream);
 }
 
 extern "C" int mg_conv1d_scatter2(const float* x, const float* w, float* y, int B, int Tin, int Cin, int N,
@@ -846,8 +846,8 @@ extern "C" int mg_conv1d_scatter2(const float* x, const float* w, float* y, int 
         const int rc = mg_conv_thin_dispatch(x, w, y, B, Tin, Cin, Tout, N, 5, 2, 0, 1, w_sn, w_sc, p.xbs, p.ybs, &p.e, s);
         if (rc != MG_EUNSUP) return rc;
     }
-    if (scatter_tile((long)B * Tin, N) == 12) return launch_cfg<2, 5, true, 1, 2>(p, s);
-    return launch_cfg<2, 5, true, 1, 1>(p, s);
+    if (scatter_tile((long)B * Tin, N) == 12) return launch_cfg<2, 5, true, 1, 2>(p, 0, s);
+    return launch_cfg<2, 5, true, 1, 1>(p, 0, s);
 }
 
 // Which template instantiation a call would launch: returns TM*10+TN of conv_wgemm_kernel<S,K,TR2,TM,TN>
@@ -863,12 +863,4 @@ extern "C" int mg_dbg_set_stamps(long long* buf) {
 
 extern "C" int mg_conv_tile_config(long m_rows, int N, int scatter2) {
     return scatter2 ? scatter_tile(m_rows, N) : gather_tile(m_rows, N);
-}
-
-long mg_conv_lds_pad_value() { return g_conv_lds_pad; }      // conv_wino.hip
-
-extern "C" int mg_conv_set_lds_pad(long bytes) {
-    MG_CHECK_ARG(bytes >= 0 && bytes <= 120 * 1024, "mg_conv_set_lds_pad: 0..120 KiB");
-    g_conv_lds_pad = bytes;
-    return MG_OK;
 }

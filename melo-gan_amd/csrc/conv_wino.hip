@@ -24,8 +24,6 @@
 #include "common.h"
 #include <type_traits>
 
-long mg_conv_lds_pad_value();      // conv_mfma.hip: mg_conv_set_lds_pad
-
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -353,8 +351,9 @@ int mg_wino3_weights(const float* w, float* wt, int N, int Cin, long w_sn, long 
 }
 
 int mg_conv1d_wino3(const float* x, const float* wt, float* y, int B, int T, int Cin, int N, const mg_epilogue* epi,
-                    mg_stream_t stream) {
+                    long lds_pad, mg_stream_t stream) {
     MG_CHECK_ARG(x && wt && y, "mg_conv1d_wino3: null tensor");
+    MG_CHECK_ARG(lds_pad >= 0 && lds_pad <= 120 * 1024, "mg_conv1d_wino3: lds_pad %ld outside 0..120 KiB", lds_pad);
     if (!mg_conv1d_wino3_supported(B, T, Cin, N)) {
         mg_set_error("mg_conv1d_wino3: unsupported shape B=%d T=%d Cin=%d N=%d (T even, Cin %% 16, N %% 64)", B, T, Cin, N);
         return MG_EUNSUP;
@@ -371,8 +370,8 @@ int mg_conv1d_wino3(const float* x, const float* wt, float* y, int B, int T, int
         MG_CHECK_ARG(!(p.e.scale && !p.e.shift), "epilogue: scale without shift");
     }
     size_t lds = 2 * (size_t)BUF * sizeof(float);
-    const long pad = mg_conv_lds_pad_value();      // occupancy cap of launches that run beside another stream's critical path
-    if (pad > 0 && lds + (size_t)pad <= 160 * 1024) lds += (size_t)pad;
+    // occupancy cap of launches that run beside another stream's critical path (conv_mfma.hip: launch_cfg)
+    if (lds_pad > 0 && lds + (size_t)lds_pad <= 160 * 1024) lds += (size_t)lds_pad;
     static bool attr_set = false;
     if (!attr_set) {
         MG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -6,10 +6,10 @@ gradient buffers (critic 1.25 MB every batch; generator + numeric encoder 18.8 M
 steps), the 1/world factor folded into the fused Adam launch (grad_scale).  On ROCm the "nccl"
 backend is RCCL over xGMI.
 
-Step orders (MELO_DP_MODE).  The default on real GPUs is **ingraph** (round 3): a PRIVATE RCCL communicator (gan/rccl.py,
-ctypes over librccl: `ncclAllReduce` / `ncclAllGather` take the engine's stream and are captured like kernel launches), so
-the N > 1 step is exactly the N = 1 step -- one graph per batch, or the split flow's four with the emotion branch on the side
-stream -- with three collective nodes inside it:
+Step orders (MELO_DP_MODE).  The default on real GPUs is **ingraph**: a PRIVATE RCCL communicator (gan/rccl.py, ctypes over
+librccl: `ncclAllReduce` / `ncclAllGather` take the engine's stream and are captured like kernel launches), so the N > 1 step
+is exactly the N = 1 step -- one graph per batch, with the emotion branch forked onto the side stream when generator steps
+follow each other -- with three collective nodes inside it:
 
     C1  group{ all-reduce(critic gradient, 1.25 MB), all-gather(a_p0: pre.2's INPUT factor, 128 KB per rank) }   in front of the
         critic's Adam launch (a_p0 exists since the generator pass: it rides in the collective that is issued anyway)
@@ -18,10 +18,9 @@ stream -- with three collective nodes inside it:
     C3  all-reduce(everything else of the generator / encoder gradient, 2 MB)    in front of the generator's Adam launch
 
 No host involvement between the pieces, no process-group watchdog (torch.distributed only broadcasts the parameters at
-start-up), nothing to prepare() before the first collective.  The older orders below stay for backends without such a
-communicator (gloo: the CPU tests, several ranks rehearsing on one GPU) and as the reference the new one is tested against.
-
-The older orders: a batch's step is a fixed sequence of hipGraphs with the collectives between them.  With a generator update:
+start-up), nothing to prepare() before the first collective.  The orders below stay for backends without such a
+communicator (gloo: the CPU tests, several ranks rehearsing on one GPU) and as the reference the ingraph order is tested
+against: a batch's step is a fixed sequence of hipGraphs with the collectives between them.  With a generator update:
 
     G1  dg_forward_d_backward_rng   one Philox draw, the 2B-row E_num + generator pass, the critic step's forward/backward
     C1  all-reduce(critic gradient, 1.25 MB)
@@ -34,23 +33,15 @@ The older orders: a batch's step is a fixed sequence of hipGraphs with the colle
     C3  all-reduce(everything else of the generator / encoder gradient, 2 MB)
     G6  g_update
 
-Optional (MELO_DP_SIDE=1, off by default -- see __init__): the emotion branch (G2) launched on the engine's SIDE stream right
-after the generator pass -- G1 split into G1a (draw + generator pass) and G1b (critic step's backward), G3 into G3a (critic
-Adam + critic pass over the generated batch) and G3b (from the first use of the emotion branch's gradient on) -- beside G1b,
-C1 and G3a; the main stream joins it in front of G3b.  Measured on one MI355X with a 1-rank RCCL group: gather 1.023 -> 0.984
-ms/step, allreduce 0.995 -> 0.957, overlap 1.105 -> 1.049; results bit-identical.
-
 Step orders (MELO_DP_MODE; default "auto" = "overlap" from 8 ranks up, "gather" below):
   gather     every collective synchronous, on the engine's stream, in program order.
   overlap    C2 -- the only transfer large enough to be worth it, 18 MB received per rank at N = 8 -- is issued
              asynchronously (RCCL's own stream, ordered behind the engine's by an event) and runs beside G4 (~150 us of
              weight gradients that do not depend on it); C1 and C3 stay synchronous.
   allreduce  one synchronous all-reduce per optimiser, no factor gather.
-Why not everything asynchronous: measured on one MI355X with a 1-rank RCCL group (the transfers take no time there, so
-what shows is the price of the mechanism): no collectives 1.176 ms/step, allreduce 1.214, gather 1.245, C1 and C2 both
-asynchronous 1.345 -- and 1.352 with the collectives synchronous but G2 / G4 forked onto a side stream instead.  A
-cross-stream fork + join around a hipGraph launch costs ~50 us on this platform whichever side carries the collective,
-so overlap pays only for a transfer that takes longer than that: C2 at N = 8 (~75-150 us expected), not C1 (~30 us).
+Why not everything asynchronous: a cross-stream fork + join around a hipGraph launch costs ~50 us on this platform whichever
+side carries the collective, so overlap pays only for a transfer that takes longer than that: C2 at N = 8 (~75-150 us
+expected), not C1 (~30 us).
 
 Factor gather: decoder.pre.2.weight is 16.8 of the generator's 18.8 MB and its gradient is d_p2^T a_p0, so the ranks
 all-gather those two per-sample factors (2.2 MB per rank) and each computes the global batch's weight gradient itself
@@ -171,20 +162,7 @@ class DataParallel:
         engine.world_size = self.world
         self._pending = []
         self._prepared = False
-        self._prev_g = False                                        # was the previous batch a generator step (split flow)
-        # N > 1: MELO_DP_SIDE=1 puts the emotion branch on the side stream as well.  Off by default: it could only be measured
-        # on a 1-rank RCCL group (-40..-55 us per step in every mode), not with real inter-GPU collectives, and two
-        # processes SHARING one GPU over gloo (the rehearsal setup) fall to 440 ms per step with it (process time slicing
-        # between two queues each) -- the proven one-stream order stays the default for runs nobody could rehearse.
-        self._dp_side = os.environ.get("MELO_DP_SIDE", "0") == "1" and getattr(engine, "ed_dtype", "fp32") == "fp32" \
-            and hasattr(engine, "d_update_g_critic_front")
-        # split | ingraph | none.  Default: the split flow for the fp32 engine; the bf16-stored emotion branch is a third as
-        # long and the three extra graph launches cost more than hiding it returns (0.831 -> 0.872 ms): it forks inside
-        # the one graph instead (0.770)
-        self._ed_flow = os.environ.get("MELO_ED_FLOW") or "ingraph"
-        # (round 2 took "split" for the fp32 engine: 96 launches per step made the forked graph's launch cost the host 0.87 ms,
-        #  more than the GPU step; at 60 launches the host is back ahead and one graph with the fork inside beats the four
-        #  graphs of the split flow by their three extra boundaries: 0.886 -> 0.868 ms per step)
+        self._prev_g = False                                        # was the previous batch a generator step
 
     def _backend(self):
         try:
@@ -285,7 +263,7 @@ class DataParallel:
         """Everything of the generator / numeric-encoder gradient except pre.2's weight and bias (first in the flat
         buffer; both come out of the gathered factors as global-batch sums already)."""
         e = self.engine
-        off, n = e.p2_grad_slice() if hasattr(e, "p2_grad_slice") else e.big_grad_slice()
+        off, n = e.p2_grad_slice()
         if off != 0:
             raise RuntimeError("gather mode expects decoder.pre.2 at offset 0 of the flat gradient")
         self._allreduce(e.GE.grad[n:])
@@ -293,41 +271,17 @@ class DataParallel:
     # ---- the step --------------------------------------------------------------------------------------------
     def step(self, use_graph: bool = True, g_step: bool = True):
         """One training step (1 critic update, optionally 1 generator update) on the batch already set with
-        engine.set_batch().  world == 1: one graph per batch, or the split flow below when generator steps follow each
-        other.  world > 1: the step order of MELO_DP_MODE (module
-        docstring)."""
+        engine.set_batch().  world == 1, or N GPUs with the collectives inside the graphs (engine.coll): one graph per
+        batch.  Otherwise the step order of MELO_DP_MODE (module docstring)."""
         e = self.engine
         if not self.active or self.mode == "ingraph":
-            # one GPU -- or N GPUs with the collectives inside the graphs (engine.coll): the same flows
-            side = getattr(e, "ed_side", None)
             back_to_back, self._prev_g = self._prev_g and g_step, g_step
-            if back_to_back and use_graph and side is not None and self._ed_flow == "split":
-                # The split flow: the frozen emotion discriminator's branch (a third of the step's MFMA work; needs only the
-                # generated batch, is needed only where the generator's backward starts) runs as its OWN graph on a side
-                # stream beside the critic step, whose ~50 launches are mostly small dependent kernels that leave the matrix
-                # pipes idle.  Four graphs per batch: [draw + 2B-row generator pass] -> fork -> side: [emotion branch] beside
-                # main: [critic step + critic pass over the generated batch] -> join -> [generator backward + update].
-                # Only when generator steps follow each other (the host is then a whole step ahead of the GPU): measured
-                # 0.959 -> 0.929 ms/batch at 1 critic : 1 generator update, but 0.474 -> 0.503 at the reference's 5 : 1
-                # (DESIGN.md section 6, Streams).
-                import torch
-                cur = torch.cuda.current_stream()
-                e.run("dg_forward_rng", True)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    e.run("g_ed_branch_side", True)
-                e.run("d_step_g_critic_front", True)
-                cur.wait_stream(side)
-                e.run("g_finish", True)
+            if back_to_back and use_graph:
+                # generator steps follow each other (the host is then a whole step ahead of the GPU): the frozen emotion
+                # discriminator's branch as a parallel branch of the one graph, on the side stream (GanEngine.dg_fork_step_rng)
+                e.run("dg_fork_step_rng", True)
                 return
-            if back_to_back and use_graph and side is not None and self._ed_flow == "fork2":
-                e.run("dg_forward_rng", True)
-                e.run("dg_fork_rest", True)
-                return
-            if back_to_back and use_graph and side is not None and self._ed_flow == "ingraph":
-                e.run("dg_fork_step_rng", True)       # the branch inside the one graph (GanEngine.dg_fork_step_rng)
-                return
-            # one graph per batch: the critic step alone, or critic + generator step with ONE 2B-row generator pass
+            # the critic step alone, or critic + generator step with ONE 2B-row generator pass
             e.run("dg_step_rng" if g_step else "d_step_rng", use_graph)
             return
         if not self._prepared:
@@ -341,26 +295,10 @@ class DataParallel:
             self.allreduce_d()
             e.run("d_update", use_graph)
             return
-        side = getattr(e, "ed_side", None) if self._dp_side else None
-        if side is not None:
-            # the frozen emotion discriminator's branch on a side stream, beside the critic step's backward, C1 and the
-            # critic's pass over the generated batch (as on one GPU: DataParallel.step, "the split flow")
-            import torch
-            cur = torch.cuda.current_stream()
-            e.run("dg_forward_rng", use_graph)            # G1a
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                e.run("g_ed_branch_side", use_graph)      # G2, side stream
-            e.run("d_backward_nofwd", use_graph)          # G1b
-            self.allreduce_d()                            # C1
-            e.run("d_update_g_critic_front", use_graph)   # G3a
-            cur.wait_stream(side)
-            e.run("g_critic_back", use_graph)             # G3b
-        else:
-            e.run("dg_forward_d_backward_rng", use_graph)
-            self.allreduce_d()                            # C1
-            e.run("g_ed_branch", use_graph)
-            e.run("d_update_g_critic_chain", use_graph)
+        e.run("dg_forward_d_backward_rng", use_graph)
+        self.allreduce_d()                            # C1
+        e.run("g_ed_branch", use_graph)
+        e.run("d_update_g_critic_chain", use_graph)
         if self.mode == "allreduce":
             e.run("g_backward_b", use_graph)
             self.allreduce_g()

@@ -35,6 +35,10 @@ from ..ops import ACT_GELU, ACT_LRELU, ACT_RELU
 
 Tensor = torch.Tensor
 BN_EPS, BN_MOM, P_DROP = 1e-5, 0.1, 0.2
+# extra LDS per workgroup of the emotion branch's convolutions when they run beside the critical path (g_ed_branch_side):
+# one workgroup per CU instead of three.  Its data-gradient convolutions take the same cap: they mostly
+# run after the main branch has reached the join, yet lifting it for them measured slower (0.867 -> 0.882 ms per step).
+ED_SIDE_LDS_PAD = 42000
 
 
 # ------------------------------------------------------------------------------------------
@@ -323,15 +327,9 @@ class GanEngine:
         self._graphs = {}
         # hipGraph capture is illegal on the null stream: every step runs on this side stream
         self.stream = torch.cuda.Stream(device=d)
-        # side stream of the fused step's emotion branch (dg_step_rng); MELO_ED_SIDE=0: everything on one stream
-        self.ed_side = torch.cuda.Stream(device=d) if os.environ.get("MELO_ED_SIDE", "1") == "1" else None
-        self._tail_fork = False         # set by the forked step around g_backward_b
-        self._d_wgrad_side, self._d_wgrad_ev = False, None
-        self.ed_side_lds_pad = int(os.environ.get("MELO_ED_LDS_PAD", "42000"))      # g_ed_branch_side
-        # its data-gradient convolutions: the same cap.  (In the forked-graph flow they mostly run after the main branch has
-        # reached the join, yet lifting the cap for them measured SLOWER: 0.867 -> 0.882 ms per step; alone on the chip a
-        # capped launch is only 8-10 % slower, tools/ed_pad_bench.py.)
-        self.ed_side_lds_pad_bwd = int(os.environ.get("MELO_ED_LDS_PAD_BWD", str(self.ed_side_lds_pad)))
+        # side stream of the forked step's emotion branch (dg_fork_step_rng)
+        self.ed_side = torch.cuda.Stream(device=d)
+        self._d_wgrad_ev = None         # the critic's weight gradients on the side stream (d_backward): d_update waits for it
         # (Forked side streams for independent branches of a step were implemented and measured in round 1: every
         # fork/join cost more cross-queue latency than the overlap returned once the kernels filled the chip -- 1.70 ms
         # single-stream vs 1.73-1.82 -- and were removed; independent launches of one kernel share a launch instead.)
@@ -339,11 +337,9 @@ class GanEngine:
         # x_hat rides in the launch that produces the critic step's fake batch where conv16 runs the last deconvolution
         # (for B and for 2B rows) and the generated roll fills the whole time axis (no zero-pad tail, models.py:78-81)
         self._mix_fused = (self.L3 == T and ("G.decoder.deconv.6.weight", "fwd") in self.wq and
-                           all(ops.conv16_supported(nb, 4 * self.red, 64, C, True, 8 * self.red) for nb in (B, 2 * B)) and
-                           os.environ.get("MELO_MIX_FUSED", "1") == "1")
+                           all(ops.conv16_supported(nb, 4 * self.red, 64, C, True, 8 * self.red) for nb in (B, 2 * B)))
         self._init_chains()
         self._bound = None          # bind_batches(): the step stages its own batch
-        self._il = None             # the emotion branch's launch generator while a forked graph is captured interleaved
         # data parallelism with the collectives INSIDE the sub-steps (DataParallel, mode "ingraph"): an InGraphCollectives
         self.coll = None
         self._p2_pending = self._a_p0_gathered = False
@@ -379,14 +375,6 @@ class GanEngine:
             add(self.GE, "GE", nm, "dgrad", Cin, Cout, Cout * 5, 5)      # gather form: n = Cin, c = Cout
         self._wq_tab = {"D": ops.wq_table(ent["D"]) if ent["D"] else None,
                         "GE": ops.wq_table(ent["GE"]) if ent["GE"] else None}
-        # the generator's update in two ranges (forked step, g_backward_b): [0, head) = decoder.pre.2 (89 % of the bytes; no
-        # WQ copy inside), [head, n) = everything else with the table's offsets re-based
-        o, cnt = self.GE.offsets["G.decoder.pre.2.bias"]
-        self._ge_head = o + cnt if self.GE.offsets["G.decoder.pre.2.weight"][0] == 0 else 0
-        if any(e[0] < self._ge_head for e in ent["GE"]):
-            self._ge_head = 0
-        self._wq_tab["GE_rest"] = ops.wq_table([(e[0] - self._ge_head,) + tuple(e[1:]) for e in ent["GE"]]) if ent["GE"] else None
-        self._ge_head_done = False
 
     def _init_chains(self):
         """Which small per-sample layer stacks run as ONE row-chain launch (csrc/row_chain.hip) instead of a launch per
@@ -405,7 +393,7 @@ class GanEngine:
         # backwards, their data-gradients: one launch from the numeric features to decoder.pre.2's input and back
         self._chain_gf = (self._chain_e and Ch.supported(self.in_dim, 512, max(self.latent_dim, 1)) and self.latent_dim % 4 == 0
                           and Ch.weights_ok(PG("noise_to_latent.net.0.weight"), PG("noise_to_latent.net.2.weight"),
-                                            PG("decoder.pre.0.weight")) and os.environ.get("MELO_CHAIN_GF", "1") == "1")
+                                            PG("decoder.pre.0.weight")))
         self._chain_d = on and Ch.supported(256, self.E) and Ch.weights_ok(PD["fc.1.weight"])
         mh = tuple(self.ed_cfg.get("mlp_hidden", (256, 128)))
         ws = [PED[f"classifier.net.{3 * j}.weight"] for j in range(len(mh))] + [PED["classifier.head.weight"]]
@@ -435,15 +423,6 @@ class GanEngine:
 
         def __init__(self):
             self.parts, self.pooled, self.perm, self.mixed, self.bnb = None, False, False, False, None
-
-    def _tick(self):
-        """Interleaved capture of the forked step graph (dg_fork_step_rng): after a main-branch convolution launch, issue the
-        emotion branch's next launch on the side stream."""
-        il = self._il
-        if il is not None:
-            with torch.cuda.stream(self.ed_side):
-                if next(il, "done") == "done":
-                    self._il = None
 
     def _conv5s2(self, kind: str, x: Tensor, fp: "FlatParams", name: str, y: Tensor, stats=None, pool=None, perm=False,
                  mix=None, bnb=None, **epi):
@@ -490,7 +469,6 @@ class GanEngine:
                 kw["mix"] = mix
                 res.mixed = True
             ops.conv16(x, wq, y, N, transposed, odd=odd, **kw)
-            self._tick()
             return res
         if perm:
             return res                              # not launched: the caller's transpose route
@@ -669,11 +647,9 @@ class GanEngine:
         # (Tried: the staging launch on the side stream beside the draw -- a fork and a join for two 5-10-us launches: 75.4 k
         # samples/s against 76.2 k without.)
         stage = None
-        if self._bound is not None and os.environ.get("MELO_STAGE_RIDER", "1") == "1":
+        if self._bound is not None:
             # a bound split: the batch's staging rides in the draw's launch (both only read the step counter)
             stage = (self._bound, self.B, self.batch_order, self.batch_order_len, self.batch_base)
-        else:
-            self._stage_bound()
         ops.rng_fill(self.noise_2, self.alpha, self.dmask_2[0], self.dmask_2[1], P_DROP, self.rng_seed, self.rng_step,
                      tick_state=self.D.state, betas=self.betas, tick_state2=self.GE.state, stage=stage)
         self.D.ticked, self.GE.ticked = True, "nobump"
@@ -877,25 +853,26 @@ class GanEngine:
                 ops.wb_relayout(w, self.ed_wb_d[i], ci, co, k, k, ci * k, flip=True)
         self._ed_folded = True
 
-    def _ed_conv_fwd(self, i: int, x: Tensor):
-        """Layer i of the frozen encoder, fp32: Conv1d -> folded BatchNorm (z kept) -> GELU (ed_model.py:24-46)."""
+    def _ed_conv_fwd(self, i: int, x: Tensor, lds_pad: int = 0):
+        """Layer i of the frozen encoder, fp32: Conv1d -> folded BatchNorm (z kept) -> GELU (ed_model.py:24-46).  lds_pad:
+        the occupancy cap of the side branch (ED_SIDE_LDS_PAD)."""
         ci, co, k = self.ed_chans[i]
         if self.ed_wino_f[i]:
-            ops.conv_wino3(x, self.ed_wino_wf[i], self.ed_a[i], scale=self.ed_scale[i], shift=self.ed_shift[i],
+            ops.conv_wino3(x, self.ed_wino_wf[i], self.ed_a[i], lds_pad=lds_pad, scale=self.ed_scale[i], shift=self.ed_shift[i],
                            zout=self.ed_z[i], act=ACT_GELU)
         else:
-            ops.conv_gather(x, self.ed_wt[i], self.ed_a[i], co, k, 1, k, co * k, scale=self.ed_scale[i],
+            ops.conv_gather(x, self.ed_wt[i], self.ed_a[i], co, k, 1, k, co * k, lds_pad=lds_pad, scale=self.ed_scale[i],
                             shift=self.ed_shift[i], zout=self.ed_z[i], act=ACT_GELU)
 
-    def _ed_conv_dgrad(self, i: int, out: Tensor):
+    def _ed_conv_dgrad(self, i: int, out: Tensor, lds_pad: int = 0):
         """Layer i's input gradient from ed_dz[i], fp32; for i > 0 times GELU'(z) and the BatchNorm scale of layer i-1."""
         epi = dict(gref=self.ed_z[i - 1], gact=ACT_GELU, gscale=self.ed_scale[i - 1]) if i > 0 else {}
         if self.ed_wino_d[i]:
-            ops.conv_wino3(self.ed_dz[i], self.ed_wino_wd[i], out, **epi)
+            ops.conv_wino3(self.ed_dz[i], self.ed_wino_wd[i], out, lds_pad=lds_pad, **epi)
         else:
-            ops.conv1d_dgrad(self.ed_dz[i], self.ED.p[f"encoder.conv.{i}.net.0.weight"], out, 1, **epi)
+            ops.conv1d_dgrad(self.ed_dz[i], self.ED.p[f"encoder.conv.{i}.net.0.weight"], out, 1, lds_pad=lds_pad, **epi)
 
-    def _ed_fwd(self, notes: Tensor):
+    def _ed_fwd(self, notes: Tensor, lds_pad: int = 0):
         """EmotionDiscriminator.forward in eval mode (ed_model.py:63-69,92-95,147-165)."""
         P = self.ED.p
         if self.ed_mode == "notes" and self.ed_dtype == "bf16":
@@ -910,7 +887,7 @@ class GanEngine:
         elif self.ed_mode == "notes":
             x = notes
             for i in range(len(self.ed_chans)):
-                self._ed_conv_fwd(i, x)
+                self._ed_conv_fwd(i, x, lds_pad)
                 x = self.ed_a[i]
             ops.meanT_fwd(x, self.ed_pool)
             ops.linear_fwd(self.ed_pool, P["encoder.project.weight"], self.ed_proj, bias=P["encoder.project.bias"])
@@ -923,7 +900,7 @@ class GanEngine:
             feat = self.ed_ca[j]
         ops.linear_fwd(feat, P["classifier.head.weight"], self.logits, bias=P["classifier.head.bias"])
 
-    def _ed_bwd(self, dnotes: Tensor):
+    def _ed_bwd(self, dnotes: Tensor, lds_pad: int = 0):
         """Input gradient of the frozen ED: dlogits -> dnotes (notes mode) or -> ed_dfeat (latent mode)."""
         P = self.ED.p
         n = len(self.ed_cz)
@@ -937,12 +914,11 @@ class GanEngine:
             return
         ops.linear_dgrad(g, w, self.ed_dproj)
         ops.linear_dgrad(self.ed_dproj, P["encoder.project.weight"], self.ed_dpool)
-        self._ed_bwd_convs(dnotes)
+        self._ed_bwd_convs(dnotes, lds_pad=lds_pad)
 
-    def _ed_bwd_convs(self, dnotes: Tensor, mean=None):
+    def _ed_bwd_convs(self, dnotes: Tensor, mean=None, lds_pad: int = 0):
         """From the pooled features' gradient back to the notes: pooling backward (times conv3's GELU' and BatchNorm scale)
         and the four convolutions' data-gradients.  mean: a scalar mean riding in the pooling-backward launch."""
-        P = self.ED.p
         last = len(self.ed_chans) - 1
         if self.ed_dtype == "bf16":
             ops.meanT_bwd_bf16(self.ed_dpool, self.ed_dz[last], self.ed_z[last], ACT_GELU, self.ed_scale[last])
@@ -953,15 +929,16 @@ class GanEngine:
             return
         ops.meanT_bwd(self.ed_dpool, self.ed_dz[last], gref=self.ed_z[last], gact=ACT_GELU, gscale=self.ed_scale[last], mean=mean)
         for i in range(last, 0, -1):
-            self._ed_conv_dgrad(i, self.ed_dz[i - 1])
-        self._ed_conv_dgrad(0, dnotes)
+            self._ed_conv_dgrad(i, self.ed_dz[i - 1], lds_pad)
+        self._ed_conv_dgrad(0, dnotes, lds_pad)
 
     # -------------------------------------------------------------------------------------
     # D-step  (src/gan/train_gan.py:183-205)
     # -------------------------------------------------------------------------------------
-    def d_backward(self, forward: bool = True):
+    def d_backward(self, forward: bool = True, side=None):
         """forward=False: the fake batch (rows [2B, 3B) of X0) and the embedding of the critic-step half already exist
-        (dg_forward ran the 2B-row generator pass)."""
+        (dg_forward ran the 2B-row generator pass).  side: a stream for the convolutions' weight-gradient launch
+        (_fork_branches); d_update waits for it."""
         B = self.B
         P, G = self.D.p, self.D.g
         if forward:
@@ -994,16 +971,15 @@ class GanEngine:
                              db=G["conv.2.bias"], defer=True),
             ops.conv1d_wgrad(self.A2[B:], self.dZ3[B:], G["conv.4.weight"], 2, self.TAN2, self.dZ3[:B],
                              db=G["conv.4.bias"], defer=True)]
-        if self._d_wgrad_side:
+        if side is not None:
             # forked step graph: this launch (+ its slab reduction), 70 us of the critic step, goes INTO the emotion branch's
             # stream -- that branch has the slack since its three-tap layers run on minimal filtering -- beside the three
-            # small dependent launches below; d_update waits for it
-            cur = torch.cuda.current_stream()
-            self.ed_side.wait_stream(cur)
-            with torch.cuda.stream(self.ed_side):
+            # small dependent launches below
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
                 ops.wgrad_multi(wjobs)
                 self._d_wgrad_ev = torch.cuda.Event()
-                self._d_wgrad_ev.record(self.ed_side)
+                self._d_wgrad_ev.record(side)
         else:
             ops.wgrad_multi(wjobs)
         if not tz3_pooled:
@@ -1057,15 +1033,8 @@ class GanEngine:
 
     def dg_fork_step_rng(self, draw: bool = True):
         """dg_step_rng with the frozen emotion discriminator's branch as a PARALLEL BRANCH of the same graph, on the side
-        stream (MELO_ED_FLOW=ingraph; the default of the bf16-stored branch, which is too short for the split flow).  The
-        branch needs only the generated batch and is needed only where the generator's backward starts; the main branch
-        is captured FIRST: hipGraphLaunch feeds a graph's branches to their hardware queues in capture order and the
-        branch fed second starts 100-300 us after the fork -- that must not be the critical path (emotion branch
-        captured first: 0.947 ms/step; critic step first: 0.911; one stream: 0.958).  Launching the forked graph costs the
-        host 0.87 ms per step against 0.64 for the plain one -- within 5 % of the fp32 step's GPU time, which is why the fp32
-        engine takes the split flow (0.58 ms of host time for 0.926) instead."""
-        if self.ed_side is None:
-            return self.dg_step_rng()
+        stream (single-GPU production path when generator steps follow each other: DataParallel.step).  The branch needs
+        only the generated batch and is needed only where the generator's backward starts."""
         cur = torch.cuda.current_stream()
         if draw:                                      # draw=False: the randoms were injected (parity tests)
             self.draw_randoms_both()
@@ -1074,11 +1043,7 @@ class GanEngine:
         self._fork_branches()
         cur.wait_stream(self.ed_side)                 # join: from here on dnotes needs the emotion branch's part
         self.g_critic_back()
-        self._tail_fork = os.environ.get("MELO_TAIL_FORK", "1") == "1"
-        try:
-            self.g_backward_b()
-        finally:
-            self._tail_fork = False
+        self.g_backward_b(side=self.ed_side)
         self.g_update()
 
     def _fork_branches(self):
@@ -1086,81 +1051,27 @@ class GanEngine:
         stream) beside the frozen emotion discriminator's branch (side stream).  Measured with mg_stamp inside the replayed
         graph (tools/step_stamps.py; the profiler's timeline of a forked graph is NOT the truth -- DESIGN section 6): the
         branch starts ~10 us after the fork; a forked hipGraph keeps TWO branches concurrent (a third stream delayed the
-        branch's first node by 236 us); capture order does not matter.  Since the branch's three-tap layers run on minimal
-        filtering it has ~70 us of slack against this stream, so the critic's convolution weight gradients (one launch + slab
-        reduction, ~70 us) are enqueued INTO the branch's stream behind its classifier-tail chain (order "dwgrad_side", the
-        default: 77.2 k samples/s against 76.3 k for "main_first", three alternations on one box; behind the pooling backward:
-        the same; one launch later: no gain).  Other orders kept for experiments: main_first, ed_first, interleave."""
-        order = os.environ.get("MELO_FORK_ORDER", "dwgrad_side")
-        if order == "ed_first" or (order == "interleave" and not self._chain_ed):
-            with torch.cuda.stream(self.ed_side):
-                self.g_ed_branch_side()
-            order = "done"
-        if order == "interleave":
-            self._require_fold()
-            self._il = self._ed_steps(self.ed_side_lds_pad, self.ed_side_lds_pad_bwd)
-        if order == "dwgrad_side" and self._chain_ed and self.ed_mode == "notes" and self.ed_dtype == "fp32":
-            self._require_fold()
-            il = self._ed_steps(self.ed_side_lds_pad, self.ed_side_lds_pad_bwd)
-            n_first = len(self.ed_chans) + int(os.environ.get("MELO_DWGRAD_AFTER", "1"))   # forward convs + the tail chain
-            with torch.cuda.stream(self.ed_side):
-                self._stamp(2)
-                for _ in range(n_first):
-                    next(il)
-            self._d_wgrad_side = True
-            try:
-                self.d_backward(forward=False)
-            finally:
-                self._d_wgrad_side = False
-            with torch.cuda.stream(self.ed_side):
-                for _ in il:
-                    pass
-                self._stamp(3)
+        branch's first node by 236 us); capture order does not matter.  Where the branch is the fp32 notes-mode chain, its
+        three-tap layers run on minimal filtering and it has ~70 us of slack against this stream, so the critic's convolution
+        weight gradients (one launch + slab reduction, ~70 us) are enqueued INTO the branch's stream behind its
+        classifier-tail chain (77.2 k samples/s against 76.3 k with the whole branch behind the critic step, three
+        alternations on one box; behind the pooling backward: the same; one launch later: no gain)."""
+        side = self.ed_side
+        if not (self._chain_ed and self.ed_mode == "notes" and self.ed_dtype == "fp32"):
+            self.d_backward(forward=False)
             self.d_update()
             self.g_critic_front()
-            return
-        self.d_backward(forward=False)
-        self.d_update()
-        self.g_critic_front()
-        if order == "interleave":
-            while self._il is not None:          # whatever the main branch's ticks did not reach
-                self._tick()
-        elif order != "done":
-            with torch.cuda.stream(self.ed_side):
+            with torch.cuda.stream(side):
                 self.g_ed_branch_side()
-
-    def dg_fork_rest(self):
-        """Everything behind the 2B-row generator pass as ONE graph whose ROOT is the fork: the emotion branch on the side
-        stream beside the critic step + critic pass, the join, the generator's backward and update (flow "fork2": two graphs
-        per batch, dg_forward_rng + this)."""
-        cur = torch.cuda.current_stream()
-        self.ed_side.wait_stream(cur)
-        self._fork_branches()
-        cur.wait_stream(self.ed_side)
-        self.g_critic_back()
-        self.g_backward_b()
-        self.g_update()
-
-    # ---- the split flow (DataParallel.step on one GPU, the default MELO_ED_FLOW=split): the emotion branch as its own graph ----
-    def dg_forward_rng(self):
-        self.draw_randoms_both()
-        self.dg_forward()
-
-    def d_step_g_critic_front(self):
-        self.d_backward(forward=False)
-        self.d_update()
-        self.g_critic_front()
-
-    def g_finish(self):
-        self.g_critic_back()
-        self.g_backward_b()
-        self.g_update()
-
-    # the same pieces for the data-parallel step order (collectives in between: DataParallel._step)
-    def d_backward_nofwd(self):
-        self.d_backward(forward=False)
-
-    def d_update_g_critic_front(self):
+            return
+        self._require_fold()
+        with torch.cuda.stream(side):
+            self._stamp(2)
+            self._ed_chain_front(ED_SIDE_LDS_PAD)     # the forward convolutions + the classifier-tail chain
+        self.d_backward(forward=False, side=side)
+        with torch.cuda.stream(side):
+            self._ed_chain_back(ED_SIDE_LDS_PAD)
+            self._stamp(3)
         self.d_update()
         self.g_critic_front()
 
@@ -1169,14 +1080,6 @@ class GanEngine:
         self.draw_randoms_both()
         self.dg_forward()
         self.d_backward(forward=False)
-
-    def g_backward_a_rng(self):
-        self.draw_randoms(with_alpha=False)
-        self.g_backward_a()
-
-    def big_grad_slice(self):
-        """(offset, numel) of decoder.pre.2.weight's gradient inside the flat G+E_num gradient buffer."""
-        return self.GE.offsets["G.decoder.pre.2.weight"]
 
     def p2_grad_slice(self):
         """(offset, numel) of decoder.pre.2's weight AND bias gradients (adjacent, at the front of the flat buffer):
@@ -1187,21 +1090,10 @@ class GanEngine:
 
     def _adam(self, fp, lr):
         """The optimiser step; after draw_randoms() the Adam state is already advanced (fp.ticked)."""
-        lo, wq = 0, self._wq_tab["D" if fp is self.D else "GE"]
-        if fp is self.GE and self._ge_head_done:          # [0, head) went out with g_backward_b's side branch
-            lo, wq, self._ge_head_done = self._ge_head, self._wq_tab["GE_rest"], False
-        ops.adam_flat(fp.data[lo:], fp.grad[lo:], fp.m[lo:], fp.v[lo:], fp.state, lr, *self.betas, grad_scale=1.0 / self.world_size,
-                      ticked_rng_step=self.rng_step if fp.ticked is True else None, ticked=bool(fp.ticked), wq=wq)
+        ops.adam_flat(fp.data, fp.grad, fp.m, fp.v, fp.state, lr, *self.betas, grad_scale=1.0 / self.world_size,
+                      ticked_rng_step=self.rng_step if fp.ticked is True else None, ticked=bool(fp.ticked),
+                      wq=self._wq_tab["D" if fp is self.D else "GE"])
         fp.ticked = False
-
-    def _adam_ge_head(self):
-        """decoder.pre.2's share of the generator update, on its own: an elementwise update, so the split changes no bit.
-        Only with the state advanced by the step's draw (fp.ticked): this launch must not advance it."""
-        h = self._ge_head
-        fp = self.GE
-        ops.adam_flat(fp.data[:h], fp.grad[:h], fp.m[:h], fp.v[:h], fp.state, self.lr_g, *self.betas,
-                      grad_scale=1.0 / self.world_size, ticked=True)
-        self._ge_head_done = True
 
     def d_update(self):
         if self._d_wgrad_ev is not None:
@@ -1243,61 +1135,47 @@ class GanEngine:
         self.g_critic_chain()
 
     def g_ed_branch_side(self):
-        """g_ed_branch for the side stream (the split / in-graph fork flows): its convolutions keep ONE workgroup per CU
-        resident instead of three, so the critical path's kernels on the main stream -- many of them small and dependent --
-        find free registers and wave slots at once instead of waiting for 15-50-us workgroups to retire.  The branch has the
+        """g_ed_branch for the side stream (the forked step): its convolutions keep ONE workgroup per CU resident instead of
+        three (ED_SIDE_LDS_PAD), so the critical path's kernels on the main stream -- many of them small and dependent -- find
+        free registers and wave slots at once instead of waiting for 15-50-us workgroups to retire.  The branch has the
         slack: it is needed only where the generator's backward starts.  Measured (cfg2, same box, alternating):
         0.913 -> 0.895 ms per step."""
-        self._require_fold()
         self._stamp(2)
-        if self._chain_ed:
-            for _ in self._ed_steps(self.ed_side_lds_pad, self.ed_side_lds_pad_bwd):
-                pass
-        else:
-            with ops.conv_lds_pad(self.ed_side_lds_pad):
-                self.g_ed_branch()
+        self.g_ed_branch(ED_SIDE_LDS_PAD)
         self._stamp(3)
 
-    def g_ed_branch(self):
+    def g_ed_branch(self, lds_pad: int = 0):
         """The frozen emotion discriminator's forward, cross-entropy and input gradient on the generated batch: the only
         part of the generator step that does not touch the critic -- under data parallelism it runs while the critic's
-        gradient all-reduce is in flight (DataParallel.step)."""
+        gradient all-reduce is in flight (DataParallel.step).  lds_pad: the convolutions' occupancy cap (g_ed_branch_side)."""
         self._require_fold()
         if self._chain_ed:
-            return self._ed_branch_chain()
-        self._ed_fwd(self.notes)
+            self._ed_chain_front(lds_pad)
+            self._ed_chain_back(lds_pad)
+            return
+        self._ed_fwd(self.notes, lds_pad)
         ops.softmax_ce(self.logits, self.emot_idx, self.emo, self.dlogits, self.lambda_emo)
-        self._ed_bwd(self.dnotes if self.ed_mode == "notes" else None)
+        self._ed_bwd(self.dnotes if self.ed_mode == "notes" else None, lds_pad)
 
-    def _ed_branch_chain(self):
-        for _ in self._ed_steps(0):
-            pass
-
-    def _ed_steps(self, lds_pad: int, lds_pad_bwd: Optional[int] = None):
+    def _ed_chain_front(self, lds_pad: int):
         """g_ed_branch with the classifier's tail -- pooling, project, MLP, head, cross-entropy and every data-gradient back
-        to the pooled features (ed_model.py:61,86-95,147-165) -- as ONE row-chain launch between the convolutions' forward
-        and their data-gradients (was: 10 launches of ~5 us).  The loss scalar (the mean of the per-sample terms) rides in
-        the pooling-backward launch.  A GENERATOR that yields after every launch, so that the forked step graph can capture
-        the branch's launches INTERLEAVED with the main branch's (dg_fork_step_rng); lds_pad: the convolutions' occupancy
-        cap when the branch runs beside the critical path (g_ed_branch_side)."""
+        to the pooled features (ed_model.py:61,86-95,147-165) -- as ONE row-chain launch behind the convolutions' forward
+        (was: 10 launches of ~5 us); _ed_chain_back runs the convolutions' data-gradients.  The fp32 branch's loss scalar (the
+        mean of the per-sample terms) rides in the pooling-backward launch there.  lds_pad: the convolutions' occupancy cap."""
         P = self.ED.p
         notes, bf16 = self.ed_mode == "notes", self.ed_dtype == "bf16"
         ch = ops.Chain(self.B)
         if notes:
             x = self.notes
             for i in range(len(self.ed_chans)):
-                ci, co, k = self.ed_chans[i]
                 if bf16:
                     ops.conv_s1_bf16(x, self.ed_wb_f[i], self.ed_a[i], scale=self.ed_scale[i], shift=self.ed_shift[i],
                                      zout=self.ed_z[i], act=ACT_GELU)
                 else:
-                    with ops.conv_lds_pad(lds_pad):
-                        self._ed_conv_fwd(i, x)
-                yield
+                    self._ed_conv_fwd(i, x, lds_pad)
                 x = self.ed_a[i]
             if bf16:
                 ops.meanT_fwd_bf16(x, self.ed_pool)
-                yield
                 ch.load(0, self.ed_pool)
             else:
                 ch.mean_t(0, x, out=self.ed_pool)
@@ -1323,45 +1201,19 @@ class GanEngine:
             cur, w = nxt(cur), P[f"classifier.net.{3 * j}.weight"]
         if not notes:
             ch.linear_dgrad(cur, nxt(cur), w, out=self.ed_dfeat)
-            ch.launch()
-            yield
-            ops.mean_scaled(self.ed_loss_rows, self.emo, 1.0)
-            yield
-            return
-        ch.linear_dgrad(cur, nxt(cur), w, out=self.ed_dproj)
-        cur = nxt(cur)
-        ch.linear_dgrad(cur, nxt(cur), P["encoder.project.weight"], out=self.ed_dpool)
+        else:
+            ch.linear_dgrad(cur, nxt(cur), w, out=self.ed_dproj)
+            cur = nxt(cur)
+            ch.linear_dgrad(cur, nxt(cur), P["encoder.project.weight"], out=self.ed_dpool)
         ch.launch()
-        yield
-        if bf16:
+        if not notes or bf16:
             ops.mean_scaled(self.ed_loss_rows, self.emo, 1.0)
-            yield
-        yield from self._ed_bwd_convs_steps(self.dnotes, None if bf16 else (self.ed_loss_rows, self.emo, 1.0),
-                                            lds_pad if lds_pad_bwd is None else lds_pad_bwd)
 
-    def _ed_bwd_convs_steps(self, dnotes: Tensor, mean, lds_pad: int):
-        """_ed_bwd_convs, one launch per step (see _ed_steps)."""
-        P = self.ED.p
-        last = len(self.ed_chans) - 1
-        if self.ed_dtype == "bf16":
-            ops.meanT_bwd_bf16(self.ed_dpool, self.ed_dz[last], self.ed_z[last], ACT_GELU, self.ed_scale[last])
-            yield
-            for i in range(last, 0, -1):
-                ops.conv_s1_bf16(self.ed_dz[i], self.ed_wb_d[i], self.ed_dz[i - 1], gref=self.ed_z[i - 1], gact=ACT_GELU,
-                                 gscale=self.ed_scale[i - 1])
-                yield
-            ops.conv_s1_bf16(self.ed_dz[0], self.ed_wb_d[0], dnotes)   # fp32 out: the generator's gradient stays fp32
-            yield
-            return
-        ops.meanT_bwd(self.ed_dpool, self.ed_dz[last], gref=self.ed_z[last], gact=ACT_GELU, gscale=self.ed_scale[last], mean=mean)
-        yield
-        for i in range(last, 0, -1):
-            with ops.conv_lds_pad(lds_pad):
-                self._ed_conv_dgrad(i, self.ed_dz[i - 1])
-            yield
-        with ops.conv_lds_pad(lds_pad):
-            self._ed_conv_dgrad(0, dnotes)
-        yield
+    def _ed_chain_back(self, lds_pad: int):
+        """The chained branch's convolution data-gradients (notes mode; see _ed_chain_front)."""
+        if self.ed_mode == "notes":
+            mean = None if self.ed_dtype == "bf16" else (self.ed_loss_rows, self.emo, 1.0)
+            self._ed_bwd_convs(self.dnotes, mean, lds_pad)
 
     def g_critic_chain(self):
         """Critic forward + input gradient on the generated batch (with the UPDATED critic), added to the emotion
@@ -1392,13 +1244,12 @@ class GanEngine:
         # BatchNorm backward: the two column sums ride in the data-gradient launch that produces the incoming gradient (conv16's
         # bnb rider), so the BatchNorm's own backward is ONE launch instead of a reduction pass plus an apply pass.  (Round 2
         # measured the rider as "no faster than the reduction pass" when that pass cost one of three launches; with two
-        # launches of ~8 us at the dependent-launch floor on the tail's critical path it is -- MELO_BNB_RIDER=0: the old path.)
-        rider = os.environ.get("MELO_BNB_RIDER", "1") == "1"
+        # launches of ~8 us at the dependent-launch floor on the tail's critical path it is.)  Where conv16 does not run the
+        # launch, the two-pass form follows.
         for (dy_src, wname, da, a_, z_, dz_, bn, i) in (
                 (dn, "G.decoder.deconv.6.weight", self.d_ad3, self.a_d3, self.z_d3, self.d_zd3, "decoder.deconv.4", 1),
                 (self.d_zd3, "G.decoder.deconv.3.weight", self.d_ad0, self.a_d0, self.z_d0, self.d_zd0, "decoder.deconv.1", 0)):
-            r = self._conv5s2("convT_dgrad", dy_src, self.GE, wname, da,
-                              bnb=(a_, z_, self.bn_mean[i], self.bn_invstd[i], ACT_RELU) if rider else None)
+            r = self._conv5s2("convT_dgrad", dy_src, self.GE, wname, da, bnb=(a_, z_, self.bn_mean[i], self.bn_invstd[i], ACT_RELU))
             if r.bnb is not None:
                 ops.bn_train_bwd_parts(r.bnb[0], r.bnb[1], da, a_, z_, dz_, PG(bn + ".weight"), self.bn_mean[i], self.bn_invstd[i],
                                        GG(bn + ".weight"), GG(bn + ".bias"), ACT_RELU)
@@ -1419,7 +1270,11 @@ class GanEngine:
         self.d_update()
         self.g_critic_chain()
 
-    def g_backward_b(self, extra_jobs=()):
+    def g_backward_b(self, extra_jobs=(), side=None):
+        """side: the forked step graph's second fork (dg_fork_step_rng): pre.2's and the deconvolutions' weight gradients go
+        to that stream BESIDE the small dependent launches below (pre.2's data-gradient, the back chain, the LayerNorm
+        parameters), which leave the chip nearly empty.  None: the same launches on this stream -- a launch's slice plan
+        depends on its job list, and every flow must produce the same bits."""
         B = self.B
         PG, GG = self._gp, (lambda k: self.GE.g["G." + k])
         PE, GEg = self._ep, (lambda k: self.GE.g["E." + k])
@@ -1443,33 +1298,19 @@ class GanEngine:
         big.append(ops.convT1d_wgrad(self.y0, self.d_zd0, GG("decoder.deconv.0.weight"), db=GG("decoder.deconv.0.bias"),
                                      defer=True))
         # (with the in-graph collectives of data parallelism too: they stay on THIS stream -- one communicator, one stream --
-        # only launches go to the side; decoder.pre.2's gradient is global from the gathered factors, so its share of the
-        # update does not wait for C3)
-        tail_fork = self._tail_fork and self.ed_side is not None
-        split = tail_fork and self._ge_head and self.GE.ticked and os.environ.get("MELO_ADAM_SPLIT", "0") == "1"
+        # only launches go to the side)
         cur = torch.cuda.current_stream()
 
-        def side(fn):
-            """The forked step graph's second fork: pre.2's and the deconvolutions' gradients (and pre.2's share of the update)
-            on the side stream BESIDE the small dependent launches below (pre.2's data-gradient, the back chain, the LayerNorm
-            parameters), which leave the chip nearly empty.  Other flows: the same launches on this stream -- a launch's
-            slice plan depends on its job list, and every flow must produce the same bits."""
-            if tail_fork:
-                self.ed_side.wait_stream(cur)
-                with torch.cuda.stream(self.ed_side):
-                    fn()
-            else:
+        def on_side(fn):
+            if side is None:
+                return fn()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
                 fn()
         if p2_job is not None:
-            side(lambda: ops.wgrad_multi([p2_job], tag="_side"))
-        side(lambda: ops.wgrad_multi(big, tag="_side2"))
+            on_side(lambda: ops.wgrad_multi([p2_job], tag="_side"))
+        on_side(lambda: ops.wgrad_multi(big, tag="_side2"))
         ops.linear_dgrad(self.d_p2, PG("decoder.pre.2.weight"), self.d_p0, gref=self.a_p0, gact=ACT_RELU)
-        if split:
-            # MELO_ADAM_SPLIT=1 (off by default): decoder.pre.2's share of the update (89 % of its bytes) as a launch of the side
-            # branch, behind its gradient AND behind the launch above, the last reader of pre.2's weights in this step.  It was
-            # worth 13 us when the tail's side branch was new; since the critic's weight gradients moved into the emotion
-            # branch's stream the undivided update is faster (77.6 k vs 76.7 k samples/s, four alternations)
-            side(self._adam_ge_head)
         jobs.append(ops.linear_wgrad(self.lat, self.d_p0, GG("decoder.pre.0.weight"), db=GG("decoder.pre.0.bias"), defer=True))
         jobs.append(ops.linear_wgrad(self.a_n0, self.d_lat, GG("noise_to_latent.net.2.weight"),
                                      db=GG("noise_to_latent.net.2.bias"), defer=True))
@@ -1500,8 +1341,8 @@ class GanEngine:
             ch.launch()
             ops.layernorm_bwd_params(self.d_ex0, self.e_xhat, GEg("net.0.weight"), GEg("net.0.bias"))
             ops.wgrad_multi(jobs)
-            if tail_fork:
-                torch.cuda.current_stream().wait_stream(self.ed_side)
+            if side is not None:
+                cur.wait_stream(side)
             return
         ops.linear_dgrad(self.d_p0, PG("decoder.pre.0.weight"), self.d_lat)
         if self.ed_mode != "notes":
@@ -1524,8 +1365,8 @@ class GanEngine:
             ops.linear_dgrad(self.d_ez1, PE("net.1.weight"), self.d_ex0)
         ops.layernorm_bwd_params(self.d_ex0, self.e_xhat, GEg("net.0.weight"), GEg("net.0.bias"))
         ops.wgrad_multi(jobs)
-        if tail_fork:
-            torch.cuda.current_stream().wait_stream(self.ed_side)
+        if side is not None:
+            cur.wait_stream(side)
 
     def enable_p2_gather(self, world: int):
         """Data parallelism without all-reducing decoder.pre.2.weight's gradient (16.8 of the 18.8 MB at cfg2): that
@@ -1566,20 +1407,14 @@ class GanEngine:
         # An update graph exists in several forms (Adam state advanced by the preceding draw -- with or without the
         # Philox counter to advance -- or by itself); a replayed graph does not run the Python that tracks which one
         # applies, so it is tracked here by sub-step name.
-        fp_upd = {"d_update": self.D, "g_update": self.GE, "d_update_g_critic_chain": self.D,
-                  "d_step_g_critic_front": self.D, "g_finish": self.GE, "d_update_g_critic_front": self.D}.get(name)
-        if name == "dg_fork_rest":          # both updates inside, both states advanced by dg_forward_rng's draw
-            try:
-                return self._run_graph(name, fn)
-            finally:
-                self.D.ticked = self.GE.ticked = False
+        fp_upd = {"d_update": self.D, "g_update": self.GE, "d_update_g_critic_chain": self.D}.get(name)
         key = name + (f"#{fp_upd.ticked}" if fp_upd is not None and fp_upd.ticked else "")
         try:
             return self._run_graph(key, fn)
         finally:
             if name.endswith("_step_rng"):                      # draw and update(s) both inside: nothing left pending
                 self.D.ticked = self.GE.ticked = False
-            elif name in ("dg_forward_d_backward_rng", "dg_forward_rng"):   # the fused draw: both updates are still to come
+            elif name == "dg_forward_d_backward_rng":         # the fused draw: both updates are still to come
                 self.D.ticked, self.GE.ticked = True, "nobump"
             elif name.endswith("_rng"):
                 (self.D if name.startswith("d_") else self.GE).ticked = True

@@ -4,8 +4,8 @@ Why not torch.distributed's collectives.  A `dist.all_reduce` runs on (or is ord
 stream, records a completion event its watchdog thread polls, and cannot be part of a hipGraph this library captures: the
 data-parallel step therefore used to be six graphs with four host-issued collectives between them (+38..69 us per step on
 one GPU before any byte moved).  `ncclAllReduce` / `ncclAllGather` called directly take a stream argument and are
-capturable like any kernel launch: with them the N > 1 step IS the N = 1 step -- one graph per batch (or the split flow's
-four) -- with three collective nodes inside.  On ROCm `librccl.so` exports the NCCL API (xGMI between the GPUs of a node).
+capturable like any kernel launch: with them the N > 1 step IS the N = 1 step -- one graph per batch -- with three
+collective nodes inside.  On ROCm `librccl.so` exports the NCCL API (xGMI between the GPUs of a node).
 
 The unique id travels over the existing torch.distributed group (any backend), once, at start-up.
 """

@@ -99,25 +99,11 @@ def _conv_work(lib, B, Tout, N, Cin, device):
     return workspace(lib.mg_conv_workspace_bytes(B, Tout, N), device, "conv")
 
 
-class conv_lds_pad:
-    """with ops.conv_lds_pad(nbytes): the window-GEMM launches inside take `nbytes` more LDS per workgroup -- fewer resident
-    workgroups per CU -- for a branch that runs beside another stream's critical path (mg_conv_set_lds_pad)."""
-
-    def __init__(self, nbytes: int):
-        self.nbytes = int(nbytes)
-
-    def __enter__(self):
-        L.check(L.load().mg_conv_set_lds_pad(self.nbytes), "mg_conv_set_lds_pad")
-
-    def __exit__(self, *a):
-        L.load().mg_conv_set_lds_pad(0)
-        return False
-
-
 def conv_gather(x: Tensor, w: Tensor, y: Tensor, N: int, K: int, stride: int, w_sn: int, w_sc: int,
-                flip: bool = False, **epi) -> Tensor:
+                flip: bool = False, lds_pad: int = 0, **epi) -> Tensor:
     """Generic gather window-GEMM (see mg_conv1d_gather).  x: (B, Tin, Cin); y: (B, Ty, N) with
-    Ty >= Tout (rows beyond Tout are left untouched -- the generator's zero-pad branch)."""
+    Ty >= Tout (rows beyond Tout are left untouched -- the generator's zero-pad branch).  lds_pad: bytes of extra LDS per
+    workgroup -- fewer resident workgroups per CU -- for a branch that runs beside another stream's critical path."""
     _chk(x, "x")
     _chk(w, "w")
     _chk(y, "y")
@@ -146,7 +132,7 @@ def conv_gather(x: Tensor, w: Tensor, y: Tensor, N: int, K: int, stride: int, w_
     def launch():
         return lib.mg_conv1d_gather(_p(x), _p(w), _p(y), B, Tin, Cin, N, K, stride, 1 if flip else 0, w_sn, w_sc,
                                     Tin * Cin, y.shape[1] * N, C.byref(e), _p(work),
-                                    work.numel() if work is not None else 0, _stream())
+                                    work.numel() if work is not None else 0, lds_pad, _stream())
     with _observe(sym, 2.0 * B * Tout * N * Cin * K, launch):
         rc = launch()
     L.check(rc, "mg_conv1d_gather")
@@ -184,9 +170,9 @@ def wino3_weights_multi(jobs):
     L.check(L.load().mg_wino3_weights_multi(arr, len(jobs), _stream()), "mg_wino3_weights_multi")
 
 
-def conv_wino3(x: Tensor, wt: Tensor, y: Tensor, **epi) -> Tensor:
+def conv_wino3(x: Tensor, wt: Tensor, y: Tensor, lds_pad: int = 0, **epi) -> Tensor:
     """Stride-1 three-tap convolution (padding 1) through minimal filtering (mg_conv1d_wino3).  x: (B, T, Cin);
-    wt: wino3_weights(...) (Cin/4, 4, N, 4); y: (B, T, N)."""
+    wt: wino3_weights(...) (Cin/4, 4, N, 4); y: (B, T, N).  lds_pad: as for conv_gather."""
     _chk(x, "x")
     _chk(wt, "wt")
     _chk(y, "y")
@@ -197,7 +183,7 @@ def conv_wino3(x: Tensor, wt: Tensor, y: Tensor, **epi) -> Tensor:
     e = epilogue((B, T, N), N, **epi)
     lib = L.load()
     def launch():
-        return lib.mg_conv1d_wino3(_p(x), _p(wt), _p(y), B, T, Cin, N, C.byref(e), _stream())
+        return lib.mg_conv1d_wino3(_p(x), _p(wt), _p(y), B, T, Cin, N, C.byref(e), lds_pad, _stream())
     with _observe(lambda: "wino3_kernel", 2.0 * B * T * N * Cin * 3, launch):      # the direct form's FLOPs (algorithmic)
         rc = launch()
     L.check(rc, "mg_conv1d_wino3")
@@ -243,15 +229,16 @@ def conv1d_fwd(x, w, y, stride, **epi):
     return conv_gather(x, w, y, Cout, K, stride, Cin * K, K, **epi)
 
 
-def conv1d_dgrad(dy, w, dx, stride, **epi):
-    """Data gradient of nn.Conv1d; w: (Cout, Cin, K); dy: (B, Tout, Cout) -> dx: (B, Tin, Cin)."""
+def conv1d_dgrad(dy, w, dx, stride, lds_pad: int = 0, **epi):
+    """Data gradient of nn.Conv1d; w: (Cout, Cin, K); dy: (B, Tout, Cout) -> dx: (B, Tin, Cin).  lds_pad: stride 1 only
+    (conv_gather)."""
     Cout, Cin, K = w.shape
     if dy.shape[2] != Cout:
         raise ValueError("conv1d_dgrad: channel mismatch")
     if stride == 1:
-        return conv_gather(dy, w, dx, Cin, K, 1, K, Cin * K, flip=True, **epi)
-    if K != 5:
-        raise ValueError("stride-2 dgrad needs K=5")
+        return conv_gather(dy, w, dx, Cin, K, 1, K, Cin * K, flip=True, lds_pad=lds_pad, **epi)
+    if K != 5 or lds_pad:
+        raise ValueError("stride-2 dgrad needs K=5 and takes no lds_pad")
     odd = dx.shape[1] == 2 * dy.shape[1] - 1
     return conv_scatter2(dy, w, dx, Cin, K, Cin * K, odd=odd, **epi)
 

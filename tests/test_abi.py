@@ -27,12 +27,12 @@ def test_library_exports_every_declared_symbol():
     assert set(_lib.SIGNATURES) <= set(names), set(_lib.SIGNATURES) - set(names)
 
 
-def test_bad_arguments_are_rejected_on_the_host():
+def test_bad_arguments_are_rejected_before_any_launch():
     """Argument validation happens before any launch, so it can be exercised without a GPU."""
     import melo_gan_amd  # noqa: F401
     from melo_gan_amd import _lib
     lib = _lib.load()
-    rc = lib.mg_conv1d_gather(None, None, None, 1, 1, 1, 1, 5, 1, 0, 5, 1, 0, 0, None, None, 0, None)
+    rc = lib.mg_conv1d_gather(None, None, None, 1, 1, 1, 1, 5, 1, 0, 5, 1, 0, 0, None, None, 0, 0, None)
     assert rc == -1 and b"null" in lib.mg_last_error()
     rc = lib.mg_wgrad(None, None, 0, None, None, 0, None, None, 0, 1, 1, 1, 1, 1, 1, None, 0, None)
     assert rc == -1
@@ -53,6 +53,19 @@ def test_bad_arguments_are_rejected_on_the_host():
     st[0].dst_pitch, st[0].src_rows = 0, 2
     assert lib.mg_stage_rows(st, 1, 4, None) == -1                      # unindexed source shorter than the batch
     assert lib.mg_dhead_fwd_bwd(None, None, None, None, None, None, None, None, 4, 4, 8, 8, 0, None) == -1
+
+
+def test_lds_pad_outside_its_range_is_rejected_on_the_host():
+    """The occupancy cap is a launch argument of the two window-GEMM entry points that take it: 0..120 KiB, checked before
+    any launch (non-null dummy addresses, so that the null-tensor check does not answer first)."""
+    import melo_gan_amd  # noqa: F401
+    from melo_gan_amd import _lib
+    lib = _lib.load()
+    x, w, y = 256, 512, 1024
+    for pad in (-1, 120 * 1024 + 1):
+        rc = lib.mg_conv1d_gather(x, w, y, 4, 256, 64, 128, 3, 1, 0, 192, 3, 0, 0, None, None, 0, pad, None)
+        assert rc == -1 and b"lds_pad" in lib.mg_last_error(), pad
+        assert lib.mg_conv1d_wino3(x, w, y, 4, 256, 64, 128, None, pad, None) == -1 and b"lds_pad" in lib.mg_last_error(), pad
 
 
 def test_ops_refuse_cpu_tensors():

@@ -100,18 +100,25 @@ def test_rejects_unsupported_shapes():
         ops.conv_wino3(x, wt, y)
 
 
-def test_occupancy_cap_does_not_change_the_result():
+def test_lds_pad_does_not_change_the_result():
+    """lds_pad (the emotion branch's occupancy cap beside the critical path) changes the launch's LDS size, not a bit of its
+    result: minimal filtering, the direct window GEMM's forward and its stride-1 flipped data-gradient."""
     ops = _ops()
     g = torch.Generator().manual_seed(3)
     x = torch.randn(4, 256, 64, generator=g).cuda()
     w = torch.randn(128, 64, 3, generator=g).cuda()
+    dy = torch.randn(4, 256, 128, generator=g).cuda()
     wt = ops.wino3_weights(w, 128, 64, 192, 3)
-    y0, y1 = torch.empty(4, 256, 128, device="cuda"), torch.empty(4, 256, 128, device="cuda")
-    ops.conv_wino3(x, wt, y0)
-    with ops.conv_lds_pad(42000):
-        ops.conv_wino3(x, wt, y1)
-    torch.cuda.synchronize()
-    assert torch.equal(y0, y1)
+    wcnk = w.permute(1, 0, 2).contiguous()                  # (Cin, Cout, 3): the engine's forward layout of these weights
+    runs = (lambda y, pad: ops.conv_wino3(x, wt, y, lds_pad=pad),
+            lambda y, pad: ops.conv_gather(x, wcnk, y, 128, 3, 1, 3, 128 * 3, lds_pad=pad),
+            lambda y, pad: ops.conv1d_dgrad(dy, w, y, 1, lds_pad=pad))
+    for run, shape in zip(runs, ((4, 256, 128), (4, 256, 128), (4, 256, 64))):
+        y0, y1 = torch.empty(shape, device="cuda"), torch.empty(shape, device="cuda")
+        run(y0, 0)
+        run(y1, 42000)
+        torch.cuda.synchronize()
+        assert torch.equal(y0, y1)
 
 
 def test_multi_filter_transform_equals_the_single_launches():

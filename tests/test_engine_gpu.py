@@ -343,34 +343,33 @@ def test_fused_step_matches_the_two_separate_steps(engine_mod):
     assert float(e4.D.state[0].item()) == 4.0 and float(e4.GE.state[0].item()) == 4.0
 
 
-def test_split_flow_equals_the_single_graph_flow(engine_mod):
-    """DataParallel.step on one GPU: back-to-back generator steps run the emotion branch as its own graph on a side stream
-    (four graphs per batch: "split") or as a parallel branch of the one graph ("ingraph"); parameters, optimiser state and
-    losses must equal the one-graph flow bit for bit, also when critic-only batches (which fall back to the one-graph
-    flow) are mixed in."""
+@pytest.mark.parametrize("case", ["gan_c128_t64_b4", "gan_c4_t16_cond_lat"])
+def test_forked_flow_equals_the_single_graph_flow(engine_mod, case):
+    """DataParallel.step on one GPU: back-to-back generator steps run the emotion branch as a parallel branch of the one
+    graph, on the side stream (dg_fork_step_rng); parameters, optimiser state and losses must equal the one-graph flow
+    (dg_step_rng / d_step_rng per batch) bit for bit, also when critic-only batches (which take the one-graph flow there
+    too) are mixed in.  The notes-mode case takes _fork_branches' order with the critic's weight gradients on the side
+    stream, the latent-mode case the one with the whole branch beside the critic step."""
     from melo_gan_amd.gan.dp import DataParallel
-    g = load("gan_c128_t64_b4")
+    g = load(case)
     res = []
-    for flow in ("none", "split", "ingraph"):
-        os.environ["MELO_ED_FLOW"] = flow
-        try:
-            S, eng, cfg, batch = make(engine_mod, g, use_graph=True)
-            dp = DataParallel(eng, 1, None)
-            eng.seed(5)
-            with torch.cuda.stream(eng.stream):
-                for k, g_step in enumerate((True, True, True, False, True, True, False, False, True, True, True)):
-                    eng.set_batch(*[t.cuda() for t in batch])
+    for forked in (False, True):
+        S, eng, cfg, batch = make(engine_mod, g, use_graph=True)
+        dp = DataParallel(eng, 1, None)
+        eng.seed(5)
+        with torch.cuda.stream(eng.stream):
+            for g_step in (True, True, True, False, True, True, False, False, True, True, True):
+                eng.set_batch(*[t.cuda() for t in batch])
+                if forked:
                     dp.step(True, g_step=g_step)
-            torch.cuda.synchronize()
-            res.append((eng.D.data.clone(), eng.GE.data.clone(), eng.GE.m.clone(), float(eng.loss_d_out[0]), float(eng.adv),
-                        float(eng.emo), {k: v.clone() for k, v in eng.Gbuf.items()}, set(eng._graphs)))
-        finally:
-            os.environ.pop("MELO_ED_FLOW", None)
-    a, b, c = res
-    assert any(k.startswith("g_finish") for k in b[7]) and not any(k.startswith("g_finish") for k in a[7])   # the split flow ran
-    assert "dg_fork_step_rng" in c[7]                                                                        # the forked graph ran
-    for o in (b, c):
-        assert torch.equal(a[0], o[0]) and torch.equal(a[1], o[1]) and torch.equal(a[2], o[2])
-        assert a[3:6] == o[3:6]
-        for k in a[6]:
-            assert torch.equal(a[6][k], o[6][k]), k
+                else:
+                    eng.run("dg_step_rng" if g_step else "d_step_rng", True)
+        torch.cuda.synchronize()
+        res.append((eng.D.data.clone(), eng.GE.data.clone(), eng.GE.m.clone(), float(eng.loss_d_out[0]), float(eng.adv),
+                    float(eng.emo), {k: v.clone() for k, v in eng.Gbuf.items()}, set(eng._graphs)))
+    a, b = res
+    assert "dg_fork_step_rng" in b[7] and "dg_fork_step_rng" not in a[7]          # the forked graph ran
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
+    assert a[3:6] == b[3:6]
+    for k in a[6]:
+        assert torch.equal(a[6][k], b[6][k]), k

@@ -3,8 +3,8 @@
  * cfg2 (B=64, T=256, C=128): the production sequence of `dg_step_rng` -- ONE 2B-row generator pass
    (`mg_bn_train_fwd_groups` / conv16 statistics epilogue at 128 rows, conv.4 with the fused temporal mean, the 3B-row
    tile plans) + critic step + generator step -- with injected randoms: teacher-forced at the critic update (every
-   quantity judged from identical inputs), and the `split` / `ingraph` side-stream flows free-running (the engine's own
-   critic update feeds its generator step) against the oracle's two consecutive sub-steps.
+   quantity judged from identical inputs), and the forked side-stream flow free-running (the engine's own critic update
+   feeds its generator step) against the oracle's two consecutive sub-steps.
  * cfg4 (B=256, T=256, C=4): one VAE step against `O.ae_step`.
  * f-2 at the cfg2 shape (B=64, T=256, C=128): one emotion-discriminator pre-training step against `O.ed_step`.
 
@@ -132,31 +132,20 @@ def test_fused_production_flow_full_size_matches_oracle():
     assert_update_matches(eng.GE.p, ge_old, S.PGE, rg["grads"], eng.lr_g, skip=NOISE_PARAMS_G, what="GE")
 
 
-@pytest.mark.parametrize("flow", ["split", "ingraph"])
+@pytest.mark.parametrize("flow", ["ingraph"])
 def test_side_stream_flows_full_size_match_oracle(flow):
-    """The split flow (emotion branch on the side stream beside the critic step) and the in-graph fork, launched as the
-    production step launches them but without the draw, FREE-RUNNING: the engine's own critic update feeds its generator
-    step.  Against the oracle's d_step followed by g_step.  The generator step then starts from a critic that differs from
-    the oracle's in the elements whose first Adam step is a coin toss (|g| at rounding level: +-lr either way, in the
-    reference as well), hence the looser bounds on what depends on the updated critic: adv 1e-3, gradients + 1e-2."""
+    """The in-graph fork (emotion branch on the side stream beside the critic step), launched as the production step
+    launches it but without the draw, FREE-RUNNING: the engine's own critic update feeds its generator step.  Against the
+    oracle's d_step followed by g_step.  The generator step then starts from a critic that differs from the oracle's in the
+    elements whose first Adam step is a coin toss (|g| at rounding level: +-lr either way, in the reference as well), hence
+    the looser bounds on what depends on the updated critic: adv 1e-3, gradients + 1e-2.  `flow`: the one remaining
+    side-stream flow (the split flow's case was removed with it)."""
     S, eng, cfg, (real, numeric, latent, emot), R = fresh()
     torch.set_num_threads(16)
     d_old = {k: v.detach().cpu().clone() for k, v in eng.D.p.items()}
     ge_old = {k: v.detach().cpu().clone() for k, v in eng.GE.p.items()}
-    side = eng.ed_side
-    assert side is not None
     with torch.cuda.stream(eng.stream):
-        cur = torch.cuda.current_stream()
-        if flow == "split":
-            eng.dg_forward()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                eng.g_ed_branch_side()
-            eng.d_step_g_critic_front()
-            cur.wait_stream(side)
-            eng.g_finish()
-        else:
-            eng.dg_fork_step_rng(draw=False)
+        eng.dg_fork_step_rng(draw=False)
         torch.cuda.synchronize()
     rd = O.d_step(S, real, latent, numeric, R["noise_d"], R["alpha"], R["dm_d"])
     check_d_side(eng, rd)
@@ -184,25 +173,21 @@ def test_side_stream_flows_full_size_match_oracle(flow):
         assert float(upd.abs().max()) <= 1.001 * eng.lr_g, k
 
 
-def test_production_graphs_full_size_equal_eager_and_each_other(monkeypatch):
-    """dg_step_rng replayed == eager, and the default flow (the forked graph: emotion branch on the side stream) and the
-    split flow's four graphs == the one graph, bit for bit, at cfg2."""
+def test_production_graphs_full_size_equal_eager_and_the_fork():
+    """dg_step_rng replayed == eager, and the default flow (the forked graph: emotion branch on the side stream) == the one
+    graph, bit for bit, at cfg2."""
     import melo_gan_amd  # noqa: F401
     from melo_gan_amd.gan.engine import GanEngine
     from melo_gan_amd.gan.dp import DataParallel
     cfg, ed_cfg = O.default_gan_cfg(B, T, C), O.default_ed_cfg(C)
     S = O.build_gan_state(cfg, ed_cfg, "weights_init", seed=3)
     batch = O.synthetic_batch(B, T, C, cfg["LATENT_DIM"], 6, 42)
-    engs = [GanEngine(cfg, ed_cfg, "cuda", B) for _ in range(4)]
+    engs = [GanEngine(cfg, ed_cfg, "cuda", B) for _ in range(3)]
     for e in engs:
         e.load_state(S.PE, S.PG, S.BG, S.PD, S.PED, S.BED)
         e.seed(77)
-    e_eager, e_graph, e_fork, e_split = engs
+    e_eager, e_graph, e_fork = engs
     dp_fork = DataParallel(e_fork, 1, None)
-    monkeypatch.setenv("MELO_ED_FLOW", "split")
-    dp_split = DataParallel(e_split, 1, None)
-    monkeypatch.delenv("MELO_ED_FLOW")
-    assert dp_fork._ed_flow == "ingraph" and dp_split._ed_flow == "split"
     with torch.cuda.stream(e_graph.stream):
         for e in engs:
             e.set_batch(*(t.cuda() for t in batch))
@@ -210,11 +195,9 @@ def test_production_graphs_full_size_equal_eager_and_each_other(monkeypatch):
             e_eager.run("dg_step_rng", False)
             e_graph.run("dg_step_rng", True)
             dp_fork.step(True)
-            dp_split.step(True)
         torch.cuda.synchronize()
     assert "dg_fork_step_rng" in e_fork._graphs                          # the forked graph ran
-    assert any(k.startswith("g_finish") for k in e_split._graphs)        # the split flow ran
-    for o in (e_graph, e_fork, e_split):
+    for o in (e_graph, e_fork):
         assert torch.equal(e_eager.D.data, o.D.data) and torch.equal(e_eager.GE.data, o.GE.data)
         assert torch.equal(e_eager.notes, o.notes) and torch.equal(e_eager.loss_d_out, o.loss_d_out)
     assert torch.isfinite(e_eager.GE.data).all() and torch.isfinite(e_eager.loss_d_out).all()

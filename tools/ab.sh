@@ -1,7 +1,7 @@
 #!/bin/bash
 # Alternating A/B of bench.py settings on ONE box in ONE call (the pool's boxes differ by ~2 %, runs drift by ~0.5 %: only
 # same-call alternations of 300 steps resolve a 5-us change of the 0.82-ms step -- DESIGN section 7 has the casualties of
-# anything less).   gpurun -- 'bash tools/ab.sh 4 "A=1" "MELO_TAIL_FORK=0" ...'   -> samples/s per setting and round, then means
+# anything less).   bash tools/ab.sh 4 "A=1" "MELO_ED_WINO=0" ...   -> samples/s per setting and round, then means
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 N=$1; shift
 declare -A SUM

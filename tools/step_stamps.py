@@ -1,6 +1,6 @@
 """Where a production step's time goes WITHOUT a profiler attached: MELO_STAMPS=1 puts one-lane nodes into the step's graph(s)
 that write the device's 100-MHz clock (mg_stamp); this runs the bench's step loop and prints the stamps of the steps' medians.
-usage: [MELO_ED_FLOW=split|ingraph|fork2] python tools/step_stamps.py [steps]"""
+usage: python tools/step_stamps.py [steps]"""
 import os, sys, time
 os.environ["MELO_STAMPS"] = "1"
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -51,7 +51,7 @@ r = torch.stack(rec).double()
 names = ["start", "fork", "ed_first", "ed_last", "main_at_join", "after_join", "end"]
 rel = (r - r[:, :1]) / 100.0          # us
 med = rel.median(0).values
-print(f"flow={os.environ.get('MELO_ED_FLOW', 'default')} pad={os.environ.get('MELO_ED_PAD', '')}  per-step-sync {dt_sync:.4f} ms  free-running {dt_free:.4f} ms/step")
+print(f"per-step-sync {dt_sync:.4f} ms  free-running {dt_free:.4f} ms/step")
 for i, n in enumerate(names):
     print(f"  {n:13s} {med[i]:8.1f} us   (free-running last step: {(free_last[i] - free_last[0]).item() / 100.0:8.1f})")
 print(f"  branch: starts {med[2] - med[1]:.1f} us after the fork, runs {med[3] - med[2]:.1f} us; main reaches the join {med[4] - med[1]:.1f} us after the fork "

@@ -24,10 +24,10 @@ for name, ci, co in (("conv1", 64, 128), ("conv2", 128, 256), ("conv3", 256, 256
     dx = torch.empty(B, T, ci).cuda()
     gf = 2.0 * B * T * ci * co * 3 / 1e9
     for pad in (0, 42000):
-        with ops.conv_lds_pad(pad):
-            t_d = timed(lambda: ops.conv_gather(x, wcnk, a, co, 3, 1, 3, co * 3, scale=sc, shift=sh, zout=z, act=ops.ACT_GELU))
-            t_w = timed(lambda: ops.conv_wino3(x, wt_f, a, scale=sc, shift=sh, zout=z, act=ops.ACT_GELU))
-            b_d = timed(lambda: ops.conv1d_dgrad(dy, w, dx, 1, gref=zp, gact=ops.ACT_GELU, gscale=gs))
-            b_w = timed(lambda: ops.conv_wino3(dy, wt_d, dx, gref=zp, gact=ops.ACT_GELU, gscale=gs))
+        t_d = timed(lambda: ops.conv_gather(x, wcnk, a, co, 3, 1, 3, co * 3, lds_pad=pad, scale=sc, shift=sh, zout=z,
+                                            act=ops.ACT_GELU))
+        t_w = timed(lambda: ops.conv_wino3(x, wt_f, a, lds_pad=pad, scale=sc, shift=sh, zout=z, act=ops.ACT_GELU))
+        b_d = timed(lambda: ops.conv1d_dgrad(dy, w, dx, 1, lds_pad=pad, gref=zp, gact=ops.ACT_GELU, gscale=gs))
+        b_w = timed(lambda: ops.conv_wino3(dy, wt_d, dx, lds_pad=pad, gref=zp, gact=ops.ACT_GELU, gscale=gs))
         print(f"{name} {ci:3d}->{co:3d} pad={pad:5d}  fwd direct {t_d:6.1f} us ({gf / t_d * 1e3:6.1f} TF)  wino {t_w:6.1f} us ({gf / t_w * 1e3:6.1f} TF alg.)"
               f" | dgrad direct {b_d:6.1f} us  wino {b_w:6.1f} us ({gf / b_w * 1e3:6.1f} TF alg.)", flush=True)
