@@ -485,6 +485,53 @@ int mg_stage_rows(const mg_stage_job* jobs, int n_jobs, int n_rows, mg_stream_t 
 int mg_stage_rows_cursor(const mg_stage_job* jobs, int n_jobs, int n_rows, const int64_t* order, long order_len,
                          const uint64_t* counter, const uint64_t* base, mg_stream_t stream);
 
+/* ---- the classifier's / VAE's training data plane: stage a batch AND augment it in one pass ----
+ * mg_stage_augment does mg_stage_rows_cursor's work for one notes array (src_rows, T, note_dim) fp32 and, when labels is not
+ * NULL, its int64 label array, and applies one augmentation program to the notes on the way through registers (no second
+ * pass, no intermediate buffer).  Row r of the batch comes from order[p] (order NULL: p), with p by `rule`:
+ *   MG_STAGE_BATCH  p = ((counter[0] - base[0]) * n_rows + r) mod order_len    batch number (counter - base) of n_rows
+ *   MG_STAGE_LAST   p = order_len - n_rows + r                                 the fixed last n_rows positions (the trailing
+ *                                                                              partial batch; counter / base may be NULL)
+ * Capturable: a replay stages the batch the counter then names.
+ *   MG_AUG_ED (src/emotion_discriminator/ed_dataset.py:299-314, in its order): noise_std > 0: columns 1, 2, 3 of every time
+ *     row += noise_std * N(0,1); dropout_prob > 0: a time row is kept with probability 1 - p, else ALL its columns become 0;
+ *     pitch_shift_prob > 0: per sample, with that probability, column 0 of every row += +1 or -1 (equal odds; dropped rows too).
+ *   MG_AUG_AE (src/ae/dataset.py:11-38,89-104): five per-sample gates with odds 0.3 / 0.3 / 0.2 / 0.3 / 0.2, in order: columns
+ *     1, 2 *= 1 + U(-tempo_jitter, tempo_jitter) (one factor per sample); column 0 += randint(-pitch_shift, pitch_shift)
+ *     (inclusive); time rows dropped with probability note_dropout; column 3 += N(0, velocity_jitter); column 1 +=
+ *     N(0, timing_jitter) then max(., 0) -- the last two also on dropped rows.  (The reference's nan_to_num is a no-op on
+ *     finite input and is not restated.)
+ *   A parameter of 0 switches its step off; with all of them 0 the output is a plain copy, bit for bit.
+ * Random numbers: Philox4x32-10, key = seed, counter = (t, 0x41554700 | need, serial lo, serial hi) with
+ *   serial = (serial_base ? serial_base[0] : 0) + p   -- the trainer sets serial_base = epoch index * split size, so serial
+ *   counts the samples staged since the start of training;  t = time row (0 for per-sample draws);
+ *   need 0, 1: per-sample gates and draws; 2: a time row's keep/drop uniform (word 0); 3: a time row's four N(0,1);
+ *   4: mg_weighted_order (t = i, serial = epoch).
+ *   A sample's draws depend on (seed, serial, t) only: not on n_rows, r, the rest of the batch, or eager / replayed launch.
+ *   mg_rng_fill's counter word 1 is below 0x40000000 and mg_gen_inputs' is 0x47454E00 | {0, 1}: the streams are disjoint under
+ *   one seed. */
+enum { MG_AUG_ED = 0, MG_AUG_AE = 1 };
+enum { MG_STAGE_BATCH = 0, MG_STAGE_LAST = 1 };
+typedef struct mg_augment {
+    int program;                                     /* MG_AUG_ED / MG_AUG_AE */
+    float noise_std, dropout_prob, pitch_shift_prob; /* ED */
+    float tempo_jitter, note_dropout, velocity_jitter, timing_jitter; /* AE */
+    int pitch_shift;                                 /* AE, semitones >= 0 */
+    uint64_t seed;
+} mg_augment;
+int mg_stage_augment(const float* notes, const int64_t* labels, long src_rows, int T, int note_dim, float* notes_out,
+                     int64_t* labels_out, int n_rows, const int64_t* order, long order_len, const uint64_t* counter,
+                     const uint64_t* base, const uint64_t* serial_base, int rule, const mg_augment* aug, mg_stream_t stream);
+/* torch.utils.data.WeightedRandomSampler(weights, num_samples = m, replacement = True) (ed_dataset.py:505-549) on the device:
+ * order[i], i < m, = the first row whose inclusive fp64 prefix sum cdf[row] exceeds u * cdf[n - 1] (binary search, clamped to
+ * n - 1), u a 53-bit uniform from the Philox block keyed by (seed, epoch, i) -- the `order` mg_stage_augment reads. */
+int mg_weighted_order(const double* cdf, long n, int64_t* order, long m, uint64_t seed, uint64_t epoch, mg_stream_t stream);
+/* The running sums of an epoch's metrics (src/emotion_discriminator/train_ed.py:75-82) after one batch, capturable:
+ *   acc[0] += loss[0] * rows ;  acc[1] += #{r : argmax(logits[r, :]) == labels[r]}      (fp32, rounded like the torch ops
+ *   they replace; first-index argmax, NaN counts as the maximum, as torch.argmax). */
+int mg_ed_metrics_acc(const float* logits, const int64_t* labels, const float* loss, int rows, int n_classes, float* acc,
+                      mg_stream_t stream);
+
 /* ---- per-step random inputs (replaces torch.randn / torch.rand / nn.Dropout's bernoulli draws:
  *      src/gan/train_gan.py:188,218; src/gan/utils.py:76; src/gan/feature_encoder.py:34) in ONE launch:
  *      normal[n_normal] ~ N(0,1), uniform[n_uniform] ~ U(0,1), mask{0,1} = keep-mask * 1/(1-p_drop).

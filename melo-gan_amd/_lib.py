@@ -46,6 +46,15 @@ class StageJob(C.Structure):
 MAX_STAGE_JOBS = 8
 
 
+class Augment(C.Structure):
+    _fields_ = [("program", i32), ("noise_std", f32), ("dropout_prob", f32), ("pitch_shift_prob", f32), ("tempo_jitter", f32),
+                ("note_dropout", f32), ("velocity_jitter", f32), ("timing_jitter", f32), ("pitch_shift", i32), ("seed", C.c_uint64)]
+
+
+AUG_ED, AUG_AE = 0, 1
+STAGE_BATCH, STAGE_LAST = 0, 1
+
+
 class WinoWJob(C.Structure):
     _fields_ = [("w", vp), ("wt", vp), ("N", i32), ("Cin", i32), ("w_sn", i64), ("w_sc", i64), ("flip", i32)]
 
@@ -144,6 +153,9 @@ SIGNATURES = {
     "mg_transpose_bcl_blc": (i32, [vp, vp, i32, i32, i32, vp, i32, vp]),
     "mg_stage_rows": (i32, [vp, i32, i32, vp]),
     "mg_stage_rows_cursor": (i32, [vp, i32, i32, vp, i64, vp, vp, vp]),
+    "mg_stage_augment": (i32, [vp, vp, i64, i32, i32, vp, vp, i32, vp, i64, vp, vp, vp, i32, C.POINTER(Augment), vp]),
+    "mg_weighted_order": (i32, [vp, i64, vp, i64, C.c_uint64, C.c_uint64, vp]),
+    "mg_ed_metrics_acc": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "mg_act_bwd": (i32, [vp, vp, i32, vp, vp, i64, vp]),
     "mg_rng_fill": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp]),
     "mg_rng_fill_tick": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp, f32, f32, vp]),

@@ -8,8 +8,10 @@ CHECKPOINT_DIR, LOG_DIR; same checkpoints: ae_best.pth {'epoch','model_state'}, 
 Per batch (train_ae.py:110-122): forward, MSE + beta*KLD, backward, clip_grad_norm_(1.0), AdamW -- all inside
 VaeEngine.  Per epoch (train_ae.py:101-107,126-199): KL warm-up beta, validation with beta=1, ReduceLROnPlateau
 (factor 0.5, patience 5, min_lr 1e-6), best-checkpoint, early stopping.  Data: row-aligned
-<SPLITS_DIR>/{train,val}/notes.npy arrays kept in HBM (the reference's per-file .npz loader with in-loader
-augmentation -- all augmentations are disabled by its config -- is host I/O and out of scope).  Per epoch the first
+<SPLITS_DIR>/{train,val}/notes.npy arrays kept in HBM (the reference's per-file .npz loader is host I/O and out of
+scope).  AUGMENT.{tempo_jitter, pitch_shift, note_dropout, velocity_jitter, timing_jitter} (ae/dataset.py:11-38,89-104,
+training split only): when any is non-zero the training batch is gathered AND augmented by one launch on the device
+(ops.stage_augment, program 'ae'); with all of them zero (the committed config) the gather is index_select.  Per epoch the first
 (up to) 6 validation rolls are reconstructed in eval mode and written as <RECON_DIR>/ep<E>_val<NNN>_{in,out}.mid
 (train_ae.py:94,173-188; RECON_FREQ, RECON_DIR) through melo_gan_amd.midi.
 """
@@ -42,7 +44,18 @@ def state_dict(eng: VaeEngine):
     return sd
 
 
+def augment_from_cfg(cfg, seed: int = 0):
+    """The AUGMENT block as ops.augment_spec's struct, or None when it is absent or all zero.  Unknown keys and values out
+    of range raise ValueError (no GPU needed)."""
+    acfg = cfg.get("AUGMENT") or {}
+    if not isinstance(acfg, dict):
+        raise ValueError(f"AUGMENT must be a mapping, got {type(acfg).__name__}")
+    aug = ops.augment_spec("ae", seed, **acfg)
+    return aug if any(acfg.get(k, 0) != 0 for k in ops.AUG_AE_KEYS) else None
+
+
 def train(cfg, synthetic: int = 0):
+    aug = augment_from_cfg(cfg, int(cfg.get("SEED", 0)))
     if not torch.cuda.is_available():
         raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -65,6 +78,9 @@ def train(cfg, synthetic: int = 0):
     gen = torch.Generator().manual_seed(0)
     eps = torch.empty(B, eng.latent, device=dev)
     acc = torch.zeros(3, device=dev)
+    if aug is not None:        # the augmented gather's cursor: batch number, and the serial of the epoch's first sample
+        batch_no, zero, serial0 = (torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(3))
+        xb = torch.empty(B, T, 4, device=dev)
     with torch.cuda.stream(eng.stream):
         for epoch in range(1, cfg["EPOCHS"] + 1):
             beta = final_beta if epoch >= warm else min(final_beta, (epoch / warm) * final_beta)
@@ -72,7 +88,13 @@ def train(cfg, synthetic: int = 0):
             acc.zero_()
             nb = len(train_x) // B
             for i in range(nb):
-                eng.step(train_x.index_select(0, perm[i * B:(i + 1) * B]), eps.normal_(), beta)
+                if aug is None:
+                    eng.step(train_x.index_select(0, perm[i * B:(i + 1) * B]), eps.normal_(), beta)
+                else:
+                    batch_no.fill_(i)
+                    serial0.fill_((epoch - 1) * len(train_x))
+                    ops.stage_augment(train_x, None, xb, None, B, perm, len(train_x), batch_no, zero, serial0, aug)
+                    eng.step(xb, eps.normal_(), beta)
                 acc += eng.loss
             tr = (acc / max(1, nb)).tolist()
             acc.zero_()

@@ -1098,6 +1098,191 @@ __global__ __launch_bounds__(SCORE_THREADS) void emotion_score_kernel(const floa
     }
 }
 
+// ---------------- batch staging with augmentation (train_ed / train_ae data plane) ----------------
+// stage_rows_cursor_kernel's work for one (notes, labels) pair, with one of two augmentation programs applied to the notes
+// while they pass through registers (include/melo_gan_hip.h, mg_stage_augment).  Philox counter layout, key = seed:
+//   (t, AUG_TAG | need, serial lo, serial hi)      serial = serial_base + position in the epoch's order
+//   need AUG_GATES / AUG_GATES2: the sample's gates and per-sample draws (t = 0)
+//   need AUG_DROP:  word 0 = the keep/drop uniform of time row t        need AUG_NOISE: four N(0,1) of time row t
+//   need AUG_ORDER: weighted_order_kernel's draw i (t = i, serial = epoch)
+// Counter word 1 of rng_fill_kernel is (block >> 32) ^ (jid << 28) < 0x40000000 and gen_inputs_kernel's is GEN_TAG | {0, 1}:
+// no counter is shared with either under one seed.  A draw depends on (seed, serial, t) alone -- not on the batch size, the
+// row's place in the batch or the launch mode.
+constexpr unsigned AUG_TAG = 0x41554700u;
+enum { AUG_GATES = 0, AUG_GATES2 = 1, AUG_DROP = 2, AUG_NOISE = 3, AUG_ORDER = 4 };
+constexpr int AUG_THREADS = 256, AUG_UNROLL = 4;        // 16-byte loads in flight per thread
+
+__device__ __forceinline__ void aug_draw(unsigned (&c)[4], unsigned t, unsigned need, unsigned long long serial,
+                                         unsigned long long seed) {
+    c[0] = t; c[1] = AUG_TAG | need; c[2] = (unsigned)serial; c[3] = (unsigned)(serial >> 32);
+    philox4(c, (unsigned)seed, (unsigned)(seed >> 32));
+}
+
+// What the gates of one sample decided (computed by every thread from the sample's key: nothing is exchanged).
+struct AugSample {
+    bool any, noise, drop, scale, jit_v, jit_t;
+    float shift, factor, p_drop, s0, s1;     // s0 / s1: ED noise_std (columns 1-3) | AE velocity / timing sigma
+};
+
+__device__ __forceinline__ AugSample aug_sample(const mg_augment& A, unsigned long long serial) {
+    AugSample S = {};
+    S.factor = 1.f;
+    unsigned c[4];
+    if (A.program == MG_AUG_ED) {               // ed_dataset.py:299-314
+        S.noise = A.noise_std > 0.f;
+        S.drop = A.dropout_prob > 0.f;
+        S.p_drop = A.dropout_prob;
+        S.s0 = A.noise_std;
+        if (A.pitch_shift_prob > 0.f) {
+            aug_draw(c, 0u, AUG_GATES, serial, A.seed);
+            if (u01(c[0]) < A.pitch_shift_prob) S.shift = (c[1] & 1u) ? 1.f : -1.f;
+        }
+    } else {                                    // ae/dataset.py:89-104, fixed odds 0.3 / 0.3 / 0.2 / 0.3 / 0.2
+        unsigned g[4];
+        aug_draw(c, 0u, AUG_GATES, serial, A.seed);
+        aug_draw(g, 0u, AUG_GATES2, serial, A.seed);
+        if (A.tempo_jitter > 0.f && u01(c[0]) < 0.3f) {
+            S.scale = true;
+            S.factor = 1.f + (2.f * u01(g[1]) - 1.f) * A.tempo_jitter;
+        }
+        if (A.pitch_shift > 0 && u01(c[1]) < 0.3f) {        // randint(-p, p), both ends included
+            const unsigned span = 2u * (unsigned)A.pitch_shift + 1u;
+            S.shift = (float)((int)(((unsigned long long)g[2] * span) >> 32) - A.pitch_shift);
+        }
+        S.drop = A.note_dropout > 0.f && u01(c[2]) < 0.2f;
+        S.p_drop = A.note_dropout;
+        S.jit_v = A.velocity_jitter > 0.f && u01(c[3]) < 0.3f;
+        S.jit_t = A.timing_jitter > 0.f && u01(g[0]) < 0.2f;
+        S.s0 = A.velocity_jitter;
+        S.s1 = A.timing_jitter;
+    }
+    S.any = S.noise || S.drop || S.scale || S.jit_v || S.jit_t || S.shift != 0.f;
+    return S;
+}
+
+// One 16-byte piece (columns 4q .. 4q+3 of time row t).  Only columns 0-3 are ever altered besides the row dropout.
+__device__ __forceinline__ float4 aug_apply(float4 v, const mg_augment& A, const AugSample& S, unsigned t, bool head,
+                                            unsigned long long serial) {
+    unsigned c[4];
+    float g[4];
+    if (A.program == MG_AUG_ED) {
+        if (S.noise && head) {
+            aug_draw(c, t, AUG_NOISE, serial, A.seed);
+            box_muller4(c, g);
+            v.y = __fadd_rn(v.y, __fmul_rn(S.s0, g[0]));
+            v.z = __fadd_rn(v.z, __fmul_rn(S.s0, g[1]));
+            v.w = __fadd_rn(v.w, __fmul_rn(S.s0, g[2]));
+        }
+        if (S.drop) {
+            aug_draw(c, t, AUG_DROP, serial, A.seed);
+            if (!(u01(c[0]) >= S.p_drop)) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (head && S.shift != 0.f) v.x = __fadd_rn(v.x, S.shift);
+        return v;
+    }
+    if (head) {
+        if (S.scale) { v.y = __fmul_rn(v.y, S.factor); v.z = __fmul_rn(v.z, S.factor); }
+        if (S.shift != 0.f) v.x = __fadd_rn(v.x, S.shift);
+    }
+    if (S.drop) {
+        aug_draw(c, t, AUG_DROP, serial, A.seed);
+        if (!(u01(c[0]) > S.p_drop)) v = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (head && (S.jit_v || S.jit_t)) {
+        aug_draw(c, t, AUG_NOISE, serial, A.seed);
+        box_muller4(c, g);
+        if (S.jit_v) v.w = __fadd_rn(v.w, __fmul_rn(S.s0, g[0]));
+        if (S.jit_t) v.y = fmaxf(__fadd_rn(v.y, __fmul_rn(S.s1, g[1])), 0.f);
+    }
+    return v;
+}
+
+// blockIdx.y = batch row, blockIdx.x strides over the sample's T * Q 16-byte pieces (Q = note_dim / 4)
+__global__ __launch_bounds__(AUG_THREADS) void stage_augment_kernel(
+    const float4* __restrict__ src, const int64_t* __restrict__ labels, long src_rows, int T, int Q, float4* __restrict__ dst,
+    int64_t* __restrict__ labels_out, int n_rows, const int64_t* __restrict__ order, long order_len,
+    const unsigned long long* __restrict__ counter, const unsigned long long* __restrict__ base,
+    const unsigned long long* __restrict__ serial_base, int rule, const mg_augment A) {
+    const int r = blockIdx.y;
+    long pos;
+    if (rule == MG_STAGE_LAST) {
+        pos = order_len - n_rows + r;
+    } else {
+        const unsigned long long k = counter[0] - base[0];
+        pos = (long)((k * (unsigned long long)n_rows + (unsigned long long)r) % (unsigned long long)order_len);
+    }
+    long sr = order ? order[pos] : pos;
+    sr = sr < 0 ? 0 : (sr >= src_rows ? src_rows - 1 : sr);
+    if (labels && blockIdx.x == 0 && threadIdx.x == 0) labels_out[r] = labels[sr];
+    const unsigned long long serial = (serial_base ? serial_base[0] : 0ull) + (unsigned long long)pos;
+    const AugSample S = aug_sample(A, serial);
+    const int n = T * Q;
+    const float4* s = src + sr * (long)n;
+    float4* d = dst + (long)r * n;
+    const int e0 = blockIdx.x * (AUG_THREADS * AUG_UNROLL) + threadIdx.x;
+    float4 v[AUG_UNROLL];
+#pragma unroll
+    for (int u = 0; u < AUG_UNROLL; ++u) {
+        const int e = e0 + u * AUG_THREADS;
+        v[u] = s[e < n ? e : n - 1];
+    }
+    if (S.any) {
+#pragma unroll
+        for (int u = 0; u < AUG_UNROLL; ++u) {
+            const int e = e0 + u * AUG_THREADS;
+            const int t = e / Q;
+            if (e < n) v[u] = aug_apply(v[u], A, S, (unsigned)t, e - t * Q == 0, serial);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < AUG_UNROLL; ++u) {
+        const int e = e0 + u * AUG_THREADS;
+        if (e < n) d[e] = v[u];
+    }
+}
+
+// WeightedRandomSampler(weights, num_samples = m, replacement = True) (ed_dataset.py:536-537) by inverse-CDF search:
+// order[i] = the first row whose inclusive prefix sum exceeds u * cdf[n - 1], u a 53-bit uniform keyed by (seed, epoch, i).
+__global__ __launch_bounds__(256) void weighted_order_kernel(const double* __restrict__ cdf, long n, int64_t* __restrict__ order,
+                                                             long m, unsigned long long seed, unsigned long long epoch) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    unsigned c[4];
+    aug_draw(c, (unsigned)i, AUG_ORDER, epoch, seed);
+    const unsigned long long bits = ((unsigned long long)(c[0] >> 5) << 26) | (unsigned long long)(c[1] >> 6);
+    const double x = (double)bits * (1.0 / 9007199254740992.0) * cdf[n - 1];
+    long lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const long mid = (lo + hi) >> 1;
+        if (cdf[mid] > x) hi = mid;
+        else lo = mid + 1;
+    }
+    order[i] = lo < n - 1 ? lo : n - 1;
+}
+
+// train_ed.run_epoch's two running sums after a batch, in its order and roundings (fp32, no contraction):
+//   acc[0] += loss * rows ;  acc[1] += number of rows whose first-index argmax (NaN counts as the maximum) is the label.
+__global__ __launch_bounds__(64) void ed_metrics_acc_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ loss, int rows, int C,
+                                                            float* __restrict__ acc) {
+    float hits = 0.f;       // a count: exact in fp32, so the order of the sum does not matter
+    for (int r = threadIdx.x; r < rows; r += 64) {
+        const float* z = logits + (long)r * C;
+        float mx = z[0];
+        int am = 0;
+        for (int j = 1; j < C; ++j) {
+            const float v = z[j];
+            if (v > mx || (isnan(v) && !isnan(mx))) { mx = v; am = j; }
+        }
+        hits += (long)am == labels[r] ? 1.f : 0.f;
+    }
+    hits = wave_sum(hits);
+    if (threadIdx.x == 0) {
+        acc[0] = __fadd_rn(acc[0], __fmul_rn(loss[0], (float)rows));
+        acc[1] = __fadd_rn(acc[1], hits);
+    }
+}
+
 // ---------------- Adam ----------------
 __global__ void adam_advance_kernel(double* state, double beta1, double beta2) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -1766,6 +1951,63 @@ int mg_emotion_score(const float* logits, int rows, int n_classes, const int32_t
     hipLaunchKernelGGL(emotion_score_kernel, dim3(1), dim3(SCORE_THREADS), 0, ST, logits, rows, n_classes, (const int*)target,
                        p_target, (int*)pred, acc);
     MG_CHECK_LAUNCH("emotion_score");
+    return MG_OK;
+}
+
+int mg_stage_augment(const float* notes, const int64_t* labels, long src_rows, int T, int note_dim, float* notes_out,
+                     int64_t* labels_out, int n_rows, const int64_t* order, long order_len, const uint64_t* counter,
+                     const uint64_t* base, const uint64_t* serial_base, int rule, const mg_augment* aug, mg_stream_t stream) {
+    MG_CHECK_ARG(notes && notes_out, "mg_stage_augment: null notes / notes_out");
+    MG_CHECK_ARG((labels == nullptr) == (labels_out == nullptr), "mg_stage_augment: labels and labels_out go together");
+    MG_CHECK_ARG(aug, "mg_stage_augment: null aug");
+    MG_CHECK_ARG(src_rows > 0, "mg_stage_augment: src_rows must be positive");
+    MG_CHECK_ARG(n_rows > 0 && n_rows <= 65535, "mg_stage_augment: n_rows must be in 1..65535");
+    MG_CHECK_ARG(order_len > 0 && (order || order_len <= src_rows), "mg_stage_augment: order_len must be positive (and within "
+                 "the source when there is no order)");
+    MG_CHECK_ARG(T > 0 && note_dim >= 4 && note_dim % 4 == 0 && (long)T * (note_dim / 4) < (1L << 30),
+                 "mg_stage_augment: row bytes: T > 0 and note_dim a positive multiple of 4 (16-byte pieces), T * note_dim < 2^32");
+    MG_CHECK_ARG((((uintptr_t)notes | (uintptr_t)notes_out) & 15) == 0, "mg_stage_augment: notes / notes_out must be 16-byte aligned");
+    MG_CHECK_ARG(rule == MG_STAGE_BATCH || rule == MG_STAGE_LAST, "mg_stage_augment: unknown position rule %d", rule);
+    if (rule == MG_STAGE_BATCH) MG_CHECK_ARG(counter && base, "mg_stage_augment: the batch rule needs counter and base");
+    else MG_CHECK_ARG(n_rows <= order_len, "mg_stage_augment: the last-rows rule needs n_rows <= order_len");
+    MG_CHECK_ARG(aug->program == MG_AUG_ED || aug->program == MG_AUG_AE, "mg_stage_augment: unknown program %d", aug->program);
+    const float probs[3] = {aug->dropout_prob, aug->pitch_shift_prob, aug->note_dropout};
+    const char* pname[3] = {"dropout_prob", "pitch_shift_prob", "note_dropout"};
+    for (int i = 0; i < 3; ++i)
+        MG_CHECK_ARG(probs[i] >= 0.f && probs[i] <= 1.f, "mg_stage_augment: %s must be in [0, 1]", pname[i]);
+    const float sig[4] = {aug->noise_std, aug->tempo_jitter, aug->velocity_jitter, aug->timing_jitter};
+    const char* sname[4] = {"noise_std", "tempo_jitter", "velocity_jitter", "timing_jitter"};
+    for (int i = 0; i < 4; ++i)
+        MG_CHECK_ARG(sig[i] >= 0.f && sig[i] < INFINITY, "mg_stage_augment: %s must be finite and not negative", sname[i]);
+    MG_CHECK_ARG(aug->pitch_shift >= 0 && aug->pitch_shift <= (1 << 20), "mg_stage_augment: pitch_shift must be in 0..2^20");
+    const int Q = note_dim / 4;
+    const long bx = mg_cdiv((long)T * Q, AUG_THREADS * AUG_UNROLL);
+    hipLaunchKernelGGL(stage_augment_kernel, dim3((unsigned)bx, (unsigned)n_rows), dim3(AUG_THREADS), 0, ST,
+                       reinterpret_cast<const float4*>(notes), labels, src_rows, T, Q, reinterpret_cast<float4*>(notes_out),
+                       labels_out, n_rows, order, order_len, reinterpret_cast<const unsigned long long*>(counter),
+                       reinterpret_cast<const unsigned long long*>(base), reinterpret_cast<const unsigned long long*>(serial_base),
+                       rule, *aug);
+    MG_CHECK_LAUNCH("stage_augment");
+    return MG_OK;
+}
+
+int mg_weighted_order(const double* cdf, long n, int64_t* order, long m, uint64_t seed, uint64_t epoch, mg_stream_t stream) {
+    MG_CHECK_ARG(cdf && order, "mg_weighted_order: null cdf / order");
+    MG_CHECK_ARG(n > 0, "mg_weighted_order: n must be positive");
+    MG_CHECK_ARG(m > 0 && m <= 0x7FFFFFFFL, "mg_weighted_order: m must be in 1..2^31-1");
+    hipLaunchKernelGGL(weighted_order_kernel, dim3((unsigned)mg_cdiv(m, 256)), dim3(256), 0, ST, cdf, n, order, m,
+                       (unsigned long long)seed, (unsigned long long)epoch);
+    MG_CHECK_LAUNCH("weighted_order");
+    return MG_OK;
+}
+
+int mg_ed_metrics_acc(const float* logits, const int64_t* labels, const float* loss, int rows, int n_classes, float* acc,
+                      mg_stream_t stream) {
+    MG_CHECK_ARG(logits && labels && loss && acc, "mg_ed_metrics_acc: null logits / labels / loss / acc");
+    MG_CHECK_ARG(rows > 0 && rows < (1 << 24), "mg_ed_metrics_acc: rows must be in 1..2^24-1");
+    MG_CHECK_ARG(n_classes >= 1, "mg_ed_metrics_acc: n_classes must be positive");
+    hipLaunchKernelGGL(ed_metrics_acc_kernel, dim3(1), dim3(64), 0, ST, logits, labels, loss, rows, n_classes, acc);
+    MG_CHECK_LAUNCH("ed_metrics_acc");
     return MG_OK;
 }
 

@@ -109,6 +109,9 @@ class EdEngine:
         self.stream = share.stream if share is not None else torch.cuda.Stream(device=d)
         self._graphs = {}
         self._tails: Dict[int, "EdEngine"] = {}
+        # the resident training split of the staged step (attach_split); a tail stages from its owner's
+        self._owner = share if share is not None else self
+        self.split_x = self.split_y = self.order = self.batch_base = self.serial_base = self.metrics = self.aug = None
 
     # ---- state in / out ---------------------------------------------------------------------------------
     def init_weights(self, seed: int = 42):
@@ -131,11 +134,11 @@ class EdEngine:
 
     def set_lr(self, lr: float):
         """ReduceLROnPlateau: the learning rate is a launch argument of the AdamW kernel, baked into every captured
-        graph that contains the update ('update', 'update#ticked' and the one-graph training step 'step_rng'): those
-        are dropped and re-captured with the new rate on their next run.  Engines sharing this one's parameters
+        graph that contains the update ('update', 'update#ticked' and the one-graph training steps 'step_rng' and
+        'step_staged'): those are dropped and re-captured with the new rate on their next run.  Engines sharing this one's parameters
         (tail()) follow."""
         self.lr = float(lr)
-        for k in [k for k in self._graphs if k.startswith("update") or k == "step_rng"]:
+        for k in [k for k in self._graphs if k.startswith("update") or k in ("step_rng", "step_staged")]:
             del self._graphs[k]
         for t in self._tails.values():
             t.set_lr(lr)
@@ -186,6 +189,39 @@ class EdEngine:
     def set_batch(self, x: Tensor, y: Tensor):
         self.x.copy_(x, non_blocking=True)
         self.y.copy_(y, non_blocking=True)
+
+    def attach_split(self, x: Tensor, y: Tensor, aug=None):
+        """Make (x, y) -- (n, T, C) fp32 and (n,) int64, resident on the device -- the split step_staged stages its batches
+        from, augmented by `aug` (ops.augment_spec(...); None: everything off, keyed by this engine's seed).  Captured staged
+        steps hold the old addresses and parameters and are dropped."""
+        if self._owner is not self:
+            raise ValueError("attach_split: attach to the full-batch engine; its tails share the split")
+        ops._chk(x, "x")
+        ops._chk(y, "y", (x.shape[0],), torch.int64)
+        if x.dim() != 3 or tuple(x.shape[1:]) != (self.T, self.C) or x.shape[0] == 0:
+            raise ValueError(f"attach_split: x must be (n > 0, {self.T}, {self.C}), got {tuple(x.shape)}")
+        self.split_x, self.split_y = x, y
+        self.aug = aug if aug is not None else ops.augment_spec("ed", self.rng_seed)
+        self.order = torch.arange(x.shape[0], dtype=torch.int64, device=self.dev)
+        self.batch_base = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.serial_base = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.metrics = torch.zeros(2, device=self.dev)
+        for e in (self, *self._tails.values()):
+            e._graphs.pop("step_staged", None)
+
+    def set_epoch(self, order: Optional[Tensor], epoch_index: int):
+        """Start an epoch of staged steps: `order` (n int64 row indices, host or device; None: the order buffer was written
+        in place, e.g. by ops.weighted_order) becomes the epoch's order, the batch cursor restarts at the current step
+        counter, the augmentation serials at epoch_index * n, and the epoch's metrics at zero."""
+        if self.split_x is None:
+            raise ValueError("set_epoch: no split attached (attach_split)")
+        if order is not None:
+            if order.dtype != torch.int64 or order.shape != self.order.shape:
+                raise ValueError(f"set_epoch: order must be {tuple(self.order.shape)} int64")
+            self.order.copy_(order)
+        self.batch_base.copy_(self.rng_step)
+        self.serial_base.fill_(int(epoch_index) * self.order.numel())
+        self.metrics.zero_()
 
     def set_masks(self, masks: Sequence[Tensor]):
         """Injected classifier dropout masks, already scaled by 1/(1-p) (parity tests)."""
@@ -292,6 +328,19 @@ class EdEngine:
         self.backward_rng()
         self.update()
 
+    def step_staged(self):
+        """step_rng with its batch staged (and augmented) from the attached split by the device-side cursor, and the epoch's
+        metrics accumulated, as ONE capturable sequence: a replay trains on the NEXT batch of the epoch's order.  The full
+        engine takes batch number (step counter - base); a tail takes the last `B` positions of the order."""
+        o = self._owner
+        if o.split_x is None:
+            raise ValueError("step_staged: no split attached (attach_split)")
+        ops.stage_augment(o.split_x, o.split_y, self.x, self.y, self.B, o.order, o.order.numel(), self.rng_step, o.batch_base,
+                          o.serial_base, o.aug, last=self is not o)
+        self.backward_rng()
+        self.update()
+        ops.ed_metrics_acc(self.logits, self.y, self.loss, self.B, o.metrics)
+
     def update(self):
         fp = self.P
         ops.adam_flat(fp.data, fp.grad, fp.m, fp.v, fp.state, self.lr, *self.betas,
@@ -326,7 +375,7 @@ class EdEngine:
         finally:
             if name.endswith("_rng"):
                 self.P.ticked = True
-            if name in ("update", "step_rng"):
+            if name in ("update", "step_rng", "step_staged"):
                 self.P.ticked = False
 
     def forward_eval(self):

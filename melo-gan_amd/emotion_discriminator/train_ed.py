@@ -10,6 +10,14 @@ Data: the row-aligned arrays the GAN trainer already uses, `<splits_dir>/<stem o
 reference's loaders (no drop_last, ed_dataset.py:542-558) an epoch ends with the trailing partial batch, run by a second
 engine of that batch size over the same parameters (EdEngine.tail); metrics are sample-weighted (train_ed.py:75-82).
 --synthetic N trains on N random rolls (smoke runs without the git-ignored dataset).  input_mode must be 'notes'.
+
+Training epochs run the engine's staged step (EdEngine.step_staged): one graph replay per batch stages the batch from the
+resident split by a device-side cursor, augments it in the same pass, trains on it and adds to the epoch's metrics.  The
+reference's data-plane keys act on the train split only, as there (ed_dataset.py:499,505):
+  augment, augment_cfg.{noise_std, dropout_prob, pitch_shift_prob}   ed_dataset.py:299-314, applied on the device
+  use_weighted_sampler                                               ed_dataset.py:505-549: the epoch's order is drawn on the
+                                                                     device with weight 1 / class count, with replacement
+  preload                                                            needs nothing here: the split is resident in HBM
 """
 import argparse
 import os
@@ -69,6 +77,40 @@ def synthetic_split(n, T, Cn, seed, device):
     return torch.from_numpy(x).to(device), torch.from_numpy(y).to(device)
 
 
+def augment_from_cfg(cfg: dict):
+    """The `augment` / `augment_cfg` keys (ed_dataset.py:299-314,499) as ops.augment_spec's struct, or None when `augment` is
+    off.  Unknown keys inside augment_cfg and values out of range raise ValueError (no GPU needed)."""
+    if not cfg.get("augment", False):
+        return None
+    acfg = cfg.get("augment_cfg") or {}
+    if not isinstance(acfg, dict):
+        raise ValueError(f"augment_cfg must be a mapping, got {type(acfg).__name__}")
+    return ops.augment_spec("ed", int(cfg.get("seed", 42)), **acfg)
+
+
+def sampler_weights(labels) -> torch.Tensor:
+    """ed_dataset.py:531-536: one fp64 weight per row, 1 / (rows of its class)."""
+    lab = torch.as_tensor(labels, dtype=torch.int64).cpu()
+    return 1.0 / torch.bincount(lab).to(torch.float64)[lab]
+
+
+def run_epoch_staged(eng: EdEngine, epoch_index: int, use_graph: bool, gen=None, cdf=None):
+    """One training epoch over the split attached to `eng` (EdEngine.attach_split) by the staged step: the same batches, in
+    the same order, from the same generator as run_epoch's host path when cdf is None; with cdf (ops.sampler_cdf) the order
+    is the weighted sampler's and never visits the host.  epoch_index (from 0) keys the augmentation and the sampler."""
+    n, B = eng.order.numel(), eng.B
+    if cdf is None:
+        eng.set_epoch(torch.randperm(n, generator=gen), epoch_index)
+    else:
+        ops.weighted_order(cdf, eng.order, eng.rng_seed, epoch_index)
+        eng.set_epoch(None, epoch_index)
+    for lo in range(0, n, B):
+        rows = min(B, n - lo)
+        (eng if rows == B else eng.tail(rows)).run("step_staged", use_graph)
+    loss, a = (eng.metrics / n).tolist()
+    return loss, a
+
+
 def run_epoch(eng: EdEngine, x, y, train: bool, use_graph: bool, gen=None):
     """train_ed.py:51-82: sample-weighted mean loss and accuracy of one pass; one device->host read per epoch."""
     n, B = x.shape[0], eng.B
@@ -108,6 +150,7 @@ def save_checkpoint(eng: EdEngine, cfg: dict, epoch: int, is_best: bool):
 def train(cfg: dict, synthetic: int = 0, use_graph: bool = True):
     if cfg.get("input_mode", "latent") != "notes":
         raise ValueError("melo_gan_amd.emotion_discriminator.train_ed: input_mode must be 'notes'")
+    aug = augment_from_cfg(cfg)                # ValueError on a bad augment_cfg, before the GPU is touched
     if not torch.cuda.is_available():
         raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
     seed_everything(cfg.get("seed", 42))
@@ -120,6 +163,14 @@ def train(cfg: dict, synthetic: int = 0, use_graph: bool = True):
         (xt, yt), (xv, yv) = load_split(cfg, "train", device), load_split(cfg, "val", device)
     eng = EdEngine(cfg, device, int(cfg.get("batch_size", 64)), T)
     eng.init_weights(cfg.get("seed", 42))
+    if xt.shape[0] == 0:
+        raise ValueError("train: the training split is empty")
+    eng.attach_split(xt.contiguous(), yt.contiguous(), aug)
+    cdf = None
+    if cfg.get("use_weighted_sampler", False):
+        cdf = ops.sampler_cdf(yt)
+        counts = {c: k for c, k in enumerate(torch.bincount(yt.cpu()).tolist()) if k}
+        print(f"[ed_dataset] Using WeightedRandomSampler: classes={counts}, samples={xt.shape[0]}")
     sch = cfg.get("scheduler") or {}
     plateau = None
     if str(sch.get("name", "")).lower() == "reducelronplateau":
@@ -133,7 +184,7 @@ def train(cfg: dict, synthetic: int = 0, use_graph: bool = True):
           cfg.get("metric_for_best", "val_loss"))
     with torch.cuda.stream(eng.stream):
         for epoch in range(1, epochs + 1):
-            tl, ta = run_epoch(eng, xt, yt, True, use_graph, gen)
+            tl, ta = run_epoch_staged(eng, epoch - 1, use_graph, gen, cdf)
             vl, va = run_epoch(eng, xv, yv, False, use_graph)
             metric = vl if by_loss else va
             if plateau is not None:

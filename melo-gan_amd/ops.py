@@ -1293,6 +1293,109 @@ def _cursor_jobs(jobs, n_rows, order, order_len):
     return arr
 
 
+AUG_ED_KEYS = ("noise_std", "dropout_prob", "pitch_shift_prob")
+AUG_AE_KEYS = ("tempo_jitter", "pitch_shift", "note_dropout", "velocity_jitter", "timing_jitter")
+
+
+def augment_spec(program: str, seed: int = 0, **params) -> "L.Augment":
+    """The augmentation program of stage_augment as the C struct: program 'ed' (ed_dataset.py:299-314; noise_std, dropout_prob,
+    pitch_shift_prob) or 'ae' (ae/dataset.py:89-104; tempo_jitter, pitch_shift, note_dropout, velocity_jitter, timing_jitter).
+    Missing parameters are 0 (= that step off).  Unknown names and values out of range raise ValueError; no GPU is needed."""
+    keys = {"ed": AUG_ED_KEYS, "ae": AUG_AE_KEYS}.get(program)
+    if keys is None:
+        raise ValueError(f"augment_spec: unknown program {program!r} (expected 'ed' or 'ae')")
+    unknown = sorted(set(params) - set(keys))
+    if unknown:
+        raise ValueError(f"augment_spec: unknown {program} augmentation key(s) {unknown}; known: {list(keys)}")
+    a = L.Augment()
+    a.program, a.seed = (L.AUG_ED if program == "ed" else L.AUG_AE), int(seed) & 0xFFFFFFFFFFFFFFFF
+    for k in keys:
+        v = params.get(k, 0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise ValueError(f"augment_spec: {k} must be a number, got {v!r}")
+        if k == "pitch_shift":
+            if v != int(v) or not 0 <= v <= 1 << 20:
+                raise ValueError(f"augment_spec: pitch_shift must be an integer in 0..2^20, got {v!r}")
+            v = int(v)
+        elif k in ("dropout_prob", "pitch_shift_prob", "note_dropout"):
+            if not 0.0 <= v <= 1.0:
+                raise ValueError(f"augment_spec: {k} must be a probability in [0, 1], got {v!r}")
+        elif not 0.0 <= v < float("inf"):
+            raise ValueError(f"augment_spec: {k} must be finite and not negative, got {v!r}")
+        setattr(a, k, v)
+    return a
+
+
+def stage_augment(notes, labels, notes_out, labels_out, n_rows, order, order_len, counter, base, serial_base, aug, last=False):
+    """Stage a batch and augment it in the same pass (mg_stage_augment): notes_out[r] = augment(notes[order[p]]) and
+    labels_out[r] = labels[order[p]] (labels / labels_out may both be None), p = ((counter - base) * n_rows + r) % order_len, or
+    with last=True the fixed last n_rows positions of the order.  order None: the identity.  counter / base / serial_base: int64
+    device scalars (1,); a sample's draws are keyed by (aug.seed, serial_base + p).  aug: augment_spec(...)."""
+    _chk(notes, "notes")
+    if notes.dim() != 3:
+        raise ValueError("stage_augment: notes must be (rows, T, note_dim)")
+    _chk(notes_out, "notes_out")
+    if notes_out.dim() != 3 or notes_out.shape[1:] != notes.shape[1:] or notes_out.shape[0] < n_rows or n_rows <= 0:
+        raise ValueError(f"stage_augment: row mismatch {tuple(notes.shape)} -> {tuple(notes_out.shape)} for {n_rows} rows")
+    if (labels is None) != (labels_out is None):
+        raise ValueError("stage_augment: labels and labels_out go together")
+    if labels is not None:
+        _chk(labels, "labels", (notes.shape[0],), torch.int64)
+        _chk(labels_out, "labels_out", dtype=torch.int64)
+        if labels_out.dim() != 1 or labels_out.shape[0] < n_rows:
+            raise ValueError("stage_augment: labels_out shorter than the batch")
+    if order is not None:
+        _chk(order, "order", dtype=torch.int64)
+        if order.numel() < order_len:
+            raise ValueError("stage_augment: order shorter than order_len")
+    for t, nm in ((counter, "counter"), (base, "base"), (serial_base, "serial_base")):
+        if t is not None:
+            _chk(t, nm, (1,), torch.int64)
+    if not isinstance(aug, L.Augment):
+        raise ValueError("stage_augment: aug must come from augment_spec()")
+    L.check(L.load().mg_stage_augment(_p(notes), _p(labels), notes.shape[0], notes.shape[1], notes.shape[2], _p(notes_out),
+                                      _p(labels_out), n_rows, _p(order), int(order_len), _p(counter), _p(base), _p(serial_base),
+                                      L.STAGE_LAST if last else L.STAGE_BATCH, C.byref(aug), _stream()), "mg_stage_augment")
+
+
+def sampler_cdf(labels: Tensor) -> Tensor:
+    """The WeightedRandomSampler weights of ed_dataset.py:531-537 (1 / count of the row's class) as an inclusive fp64 prefix sum
+    on the labels' device -- weighted_order's distribution.  Built once per run."""
+    lab = labels.detach().to("cpu", torch.int64)
+    if lab.dim() != 1 or lab.numel() == 0 or int(lab.min()) < 0:
+        raise ValueError("sampler_cdf: labels must be a non-empty 1-D tensor of class indices >= 0")
+    counts = torch.bincount(lab)
+    w = 1.0 / counts.to(torch.float64)[lab]
+    return torch.cumsum(w, 0).to(labels.device)
+
+
+def weighted_order(cdf, order, seed, epoch):
+    """order[i] ~ the distribution whose inclusive prefix sum is cdf (fp64), with replacement (mg_weighted_order), keyed by
+    (seed, epoch, i): WeightedRandomSampler(replacement=True), ed_dataset.py:537."""
+    _chk(cdf, "cdf", dtype=torch.float64)
+    _chk(order, "order", dtype=torch.int64)
+    if cdf.dim() != 1 or order.dim() != 1:
+        raise ValueError("weighted_order: cdf and order must be 1-D")
+    L.check(L.load().mg_weighted_order(_p(cdf), cdf.numel(), _p(order), order.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                       int(epoch) & 0xFFFFFFFFFFFFFFFF, _stream()), "mg_weighted_order")
+    return order
+
+
+def ed_metrics_acc(logits, labels, loss, rows, acc):
+    """acc[0] += loss * rows; acc[1] += #(argmax(logits[:rows]) == labels[:rows]) in one capturable launch
+    (mg_ed_metrics_acc; train_ed.py:75-82)."""
+    _chk(logits, "logits")
+    if logits.dim() != 2 or not 0 < rows <= logits.shape[0]:
+        raise ValueError("ed_metrics_acc: logits must be (>= rows, classes)")
+    _chk(labels, "labels", dtype=torch.int64)
+    if labels.dim() != 1 or labels.shape[0] < rows:
+        raise ValueError("ed_metrics_acc: labels shorter than rows")
+    _chk(loss, "loss", (1,))
+    _chk(acc, "acc", (2,))
+    L.check(L.load().mg_ed_metrics_acc(_p(logits), _p(labels), _p(loss), rows, logits.shape[1], _p(acc), _stream()),
+            "mg_ed_metrics_acc")
+
+
 def transpose_bcl_blc(x, y, gref=None, gact=ACT_NONE):
     """y[b, l, c] = x[b, c, l] (* act'(gref[b, l, c]) if gref is given: the activation backward behind the view)."""
     _chk(x, "x")
