@@ -226,6 +226,12 @@ int mg_linear(const float* x, const float* w, float* y, int M, int K, int N, int
  * (src/gan/models.py:70-73) -- no transpose launch.  perm_L = 0: mg_linear. */
 int mg_linear_perm(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, int w_sc,
                    const mg_epilogue* epi, int perm_L, void* work, size_t work_bytes, mg_stream_t stream);
+/* Host only: what mg_linear_perm launches for these arguments (the same decision function).  Returns 0: the 64x64-tile window
+ * GEMM conv_wgemm_kernel<1,1,false,true,TM,TN> (the permuted forward with many rows and columns; MG_LINEAR_SKINNY_ONLY=1
+ * disables that route), 1: linear_skinny_kernel<*kcontig, *vec>, followed by linear_finish_kernel when *ksplit > 1;
+ * negative: an argument error.  x_aligned / w_aligned: whether the pointer is 16-byte aligned. */
+int mg_linear_route(int M, int K, int N, int w_sn, int w_sc, int perm_L, int x_aligned, int w_aligned,
+                    int* kcontig, int* vec, int* ksplit);
 
 /* ---- stride-1 three-tap Conv1d (padding 1) by minimal filtering F(2,3) along time (csrc/conv_wino.hip) ----
  * Same result as mg_conv1d_gather(K = 3, stride = 1) up to rounding (the operands are transformed: a few ulp), with 2/3 of
@@ -256,6 +262,17 @@ int mg_wino3_weights_multi(const mg_wino3_wjob* jobs, int n_jobs, mg_stream_t st
  * 12: 64x128, 11: 64x64).  m_rows = B*Tout (gather) or B*Tin (scatter2).  Lets a profiler label
  * launches by kernel symbol. */
 int mg_conv_tile_config(long m_rows, int N, int scatter2);
+/* Host only: the split of the channel reduction a window-GEMM call plans (the planner mg_conv1d_gather / mg_conv1d_scatter2
+ * launch with; MG_SPLITK_TARGET read per call).  Tm = the rows the time tiling covers (Tout for gather, Tin for scatter2),
+ * work_bytes = the workspace the call would be given (0: none).  *ksplit = blockIdx.z slabs (> 1: conv_finish_kernel sums
+ * them and runs the epilogue), *cps = channel chunks (16 channels; 64 for K = 1) per slab.  Calls that route to the thin
+ * kernels (mg_conv_thin_route) do not use this plan. */
+int mg_conv_plan(int B, int Tm, int Tout, int N, int Cin, int K, int stride, int scatter2, size_t work_bytes,
+                 int* ksplit, int* cps);
+/* Host only: which conv_finish_kernel<VEC> a split launch is followed by (the launch's own predicate): 1 = the 16-byte one,
+ * 0 = the scalar one.  ybs = the batch stride of y in elements; tensors_aligned = the workspace, y and every elementwise
+ * epilogue tensor given (zout, gref, emul) start on a 16-byte boundary. */
+int mg_conv_finish_vec(int N, long ybs, int tensors_aligned);
 
 /* The layers with a <= 8 channel reduction or output side (NOTE_DIM = 4, reference config/gan_config.yaml:43-44: critic
  * conv.0 src/gan/models.py:129, generator deconv.6 src/gan/models.py:67-70, emotion discriminator conv0

@@ -103,6 +103,9 @@ SIGNATURES = {
     "mg_linear": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(Epilogue), vp, sz, vp]),
     "mg_linear_perm": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(Epilogue), i32, vp, sz, vp]),
     "mg_conv_tile_config": (i32, [i64, i32, i32]),
+    "mg_conv_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, sz, C.POINTER(i32), C.POINTER(i32)]),
+    "mg_conv_finish_vec": (i32, [i32, i64, i32]),
+    "mg_linear_route": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "mg_conv_thin_route": (i32, [vp, i64, i32, i32, i32, i32, i32]),
     "mg_wb_relayout": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "mg_conv1d_s1_bf16_supported": (i32, [i32, i32, i32, i32, i32]),
@@ -196,6 +199,11 @@ def load():
         raise RuntimeError(
             f"{LIB_PATH} is missing: build it with `python melo-gan_amd/build.py` "
             "(or __graft_entry__.build()).  There is no fallback path.")
+    # torch first: its wheel carries its own libamdhip64.so (soname libamdhip64.so.7), which then also satisfies this
+    # library's dependency.  Loaded the other way round -- build() followed by smoke() in one process did -- the process
+    # ends up with the system's HIP runtime and torch's side by side, and whichever opens the device second reports
+    # "no ROCm-capable device is detected" at its first launch.
+    import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported

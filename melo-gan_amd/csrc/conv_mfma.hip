@@ -640,6 +640,47 @@ __global__ void conv_finish_kernel(const float* __restrict__ part, float* __rest
     }
 }
 
+// The host-side plan of one window-GEMM launch: the time / batch tiling of the grid and the split of the channel
+// reduction over blockIdx.z.  launch_cfg and the mg_conv_plan query both take it from here.
+struct ConvPlan {
+    int tt_log2, n_ttiles;
+    unsigned gx, gy;
+    int ksplit, cps;
+};
+ConvPlan conv_plan(int B, int Tm, int Tout, int N, int Cin, int BM, int BN, int BKC, bool has_work, size_t work_bytes) {
+    ConvPlan c{};
+    int lg = mg_ilog2_ceil(Tm);
+    const int lgbm = mg_ilog2_ceil(BM);
+    if (lg > lgbm) lg = lgbm;
+    c.tt_log2 = lg;
+    const int TT = 1 << lg, TB = BM >> lg;
+    c.n_ttiles = (int)mg_cdiv(Tm, TT);
+    c.gx = (unsigned)(c.n_ttiles * mg_cdiv(B, TB));
+    c.gy = (unsigned)mg_cdiv(N, BN);
+    // split-K over workgroups when the output tiling alone leaves most of the 256 CUs idle
+    const int nchunks = (int)mg_cdiv(Cin, BKC);
+    const long n_wgs = (long)c.gx * c.gy;
+    const long total = (long)B * Tout * N;
+    c.ksplit = 1;
+    c.cps = nchunks;
+    long wg_target = 256, wg_max = 192;
+    if (const char* f = getenv("MG_SPLITK_TARGET")) { wg_target = atol(f); wg_max = wg_target * 3 / 4; }
+    if (has_work && n_wgs < wg_max && nchunks >= 4) {
+        int ks = 1;
+        while (ks < 8 && n_wgs * ks < wg_target && nchunks / (ks * 2) >= 2) ks *= 2;
+        if (ks > 1 && work_bytes >= (size_t)ks * total * sizeof(float)) {
+            c.cps = (int)mg_cdiv(nchunks, ks);
+            c.ksplit = (int)mg_cdiv(nchunks, c.cps);
+        }
+    }
+    return c;
+}
+
+// conv_finish_kernel<true> (four channels per thread, 16-byte loads / stores) or <false>: launch_cfg and the
+// mg_conv_finish_vec query both decide here.  aligned: the slabs, y and every elementwise epilogue tensor given start on a
+// 16-byte boundary.
+bool finish_vec(int N, long ybs, bool aligned) { return (N % 4 == 0) && (ybs % 4 == 0) && aligned; }
+
 // lds_pad: extra LDS per workgroup = fewer resident workgroups per CU, for launches that run BESIDE another stream's
 // critical path (the frozen emotion discriminator's branch): they leave wave slots, registers and LDS to it.  A pad that
 // would take the launch past 160 KiB is ignored.
@@ -650,12 +691,11 @@ int launch_cfg(const ConvP& p0, long lds_pad, hipStream_t stream) {
     constexpr int BKC = ChunkOf<K>::value, SX = BKC + 4;
     constexpr int SA = TR2 ? 1 : S;
     constexpr int NR = TR2 ? 3 : K;
-    int lg = mg_ilog2_ceil(p.Tm);
-    const int lgbm = mg_ilog2_ceil(BM);
-    if (lg > lgbm) lg = lgbm;
+    const ConvPlan plan = conv_plan(p.B, p.Tm, p.Tout, p.N, p.Cin, BM, BN, BKC, p.work != nullptr, p.work_bytes);
+    const int lg = plan.tt_log2;
     p.tt_log2 = lg;
     const int TT = 1 << lg, TB = BM >> lg;
-    p.n_ttiles = (int)mg_cdiv(p.Tm, TT);
+    p.n_ttiles = plan.n_ttiles;
     p.nt_magic = p.n_ttiles > 1 ? (unsigned)((1ULL << 32) / (unsigned)p.n_ttiles) : 0xFFFFFFFFu;
     const int R = (TT - 1) * SA + NR;
     constexpr int PP = (BN + (K == 5 ? 5 : K == 3 ? 3 : 1)) * 4;     // the larger (padded, CNK) weight plane of the kernel
@@ -678,33 +718,20 @@ int launch_cfg(const ConvP& p0, long lds_pad, hipStream_t stream) {
         }
         attr_set[nck] = true;
     }
-    dim3 grid((unsigned)(p.n_ttiles * mg_cdiv(p.B, TB)), (unsigned)mg_cdiv(p.N, BN));
-    // split-K over workgroups when the output tiling alone leaves most of the 256 CUs idle
-    const int nchunks = (int)mg_cdiv(p.Cin, BKC);
-    const long n_wgs = (long)grid.x * grid.y;
+    dim3 grid(plan.gx, plan.gy);
     const long total = (long)p.B * p.Tout * p.N;
-    p.ksplit = 1;
-    p.cps = nchunks;
-    long wg_target = 256, wg_max = 192;
-    if (const char* f = getenv("MG_SPLITK_TARGET")) { wg_target = atol(f); wg_max = wg_target * 3 / 4; }
-    if (p.work && n_wgs < wg_max && nchunks >= 4) {
-        int ks = 1;
-        while (ks < 8 && n_wgs * ks < wg_target && nchunks / (ks * 2) >= 2) ks *= 2;
-        if (ks > 1 && p.work_bytes >= (size_t)ks * total * sizeof(float)) {
-            p.ksplit = ks;
-            p.cps = (int)mg_cdiv(nchunks, ks);
-            p.ksplit = (int)mg_cdiv(nchunks, p.cps);
-            p.part = (float*)p.work;
-            grid.z = (unsigned)p.ksplit;
-        }
+    p.ksplit = plan.ksplit;
+    p.cps = plan.cps;
+    if (p.ksplit > 1) {
+        p.part = (float*)p.work;
+        grid.z = (unsigned)p.ksplit;
     }
     hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, p);
     MG_CHECK_LAUNCH("conv_wgemm");
     if (p.ksplit > 1) {
         const mg_epilogue& E = p.e;
         auto al16 = [](const void* q) { return q == nullptr || ((((uintptr_t)q) & 15) == 0); };
-        const bool vec = (p.N % 4 == 0) && (p.ybs % 4 == 0) && al16(p.part) && al16(p.y) && al16(E.zout) && al16(E.gref) &&
-                         al16(E.emul);
+        const bool vec = finish_vec(p.N, p.ybs, al16(p.part) && al16(p.y) && al16(E.zout) && al16(E.gref) && al16(E.emul));
         if (vec)
             hipLaunchKernelGGL(conv_finish_kernel<true>, dim3((unsigned)mg_cdiv(total / 4, 256)), dim3(256), 0, stream,
                                (const float*)p.part, p.y, total, p.Tout, p.N, p.ybs, p.ksplit, p.e);
@@ -864,3 +891,19 @@ extern "C" int mg_dbg_set_stamps(long long* buf) {
 extern "C" int mg_conv_tile_config(long m_rows, int N, int scatter2) {
     return scatter2 ? scatter_tile(m_rows, N) : gather_tile(m_rows, N);
 }
+
+extern "C" int mg_conv_plan(int B, int Tm, int Tout, int N, int Cin, int K, int stride, int scatter2, size_t work_bytes,
+                            int* ksplit, int* cps) {
+    MG_CHECK_ARG(B > 0 && Tm > 0 && Tout > 0 && N > 0 && Cin > 0, "mg_conv_plan: bad shape");
+    MG_CHECK_ARG(K == 1 || K == 3 || K == 5, "mg_conv_plan: K=%d unsupported", K);
+    MG_CHECK_ARG(scatter2 ? (K == 5 && stride == 2) : (stride == 1 || (stride == 2 && K == 5)),
+                 "mg_conv_plan: K=%d stride=%d unsupported", K, stride);
+    const int t = scatter2 ? scatter_tile((long)B * Tm, N) : gather_tile((long)B * Tm, N);
+    const ConvPlan c = conv_plan(B, Tm, Tout, N, Cin, 64 * (t / 10), 64 * (t % 10),
+                                 K == 1 ? ChunkOf<1>::value : ChunkOf<5>::value, work_bytes > 0, work_bytes);
+    if (ksplit) *ksplit = c.ksplit;
+    if (cps) *cps = c.cps;
+    return MG_OK;
+}
+
+extern "C" int mg_conv_finish_vec(int N, long ybs, int tensors_aligned) { return finish_vec(N, ybs, tensors_aligned != 0) ? 1 : 0; }

@@ -181,7 +181,45 @@ int plan_ksplit(int M, int N, int K) {
     return ks;
 }
 
+// Which kernel a Linear call runs and how its K range is cut: mg_linear_perm and the mg_linear_route query both decide here.
+struct LinRoute {
+    bool window_gemm;     // the permuted forward on the 64x64-tile window GEMM (mg_conv_linear_perm); nothing below applies
+    bool kcontig, vec;    // linear_skinny_kernel<W_KCONTIG, VEC>
+    int ksplit, kw;       // blockIdx.z slabs; K range per wave
+};
+LinRoute linear_route(int M, int K, int N, int w_sn, int w_sc, int perm_L, bool x_aligned, bool w_aligned) {
+    LinRoute r{};
+    // The permuted forward (decoder.pre.2) with enough rows and columns for the 64x64-tile kernel to fill the chip by its
+    // output tiling alone: 13.2 us there against 20.3 here at the fused step's 2B = 128 rows (64 rows: 12.8 against 11.1)
+    if (perm_L > 1 && w_sc == 1 && M >= 128 && (K & 63) == 0 && (N & 63) == 0 && mg_cdiv(M, 64) * (long)(N / 64) >= 192 &&
+        x_aligned && w_aligned && (w_sn & 3) == 0 && !getenv("MG_LINEAR_SKINNY_ONLY")) {
+        r.window_gemm = true;
+        r.ksplit = 1;
+        return r;
+    }
+    r.ksplit = plan_ksplit(M, N, K);
+    r.kcontig = (w_sc == 1);
+    // vector path: every wave's K range is a multiple of 8 inside K, rows 16-byte aligned
+    const int waves = NW * r.ksplit;
+    r.vec = (K % (8 * waves) == 0) && x_aligned && (!r.kcontig || (w_aligned && (w_sn & 3) == 0));
+    r.kw = r.vec ? K / waves : (int)(mg_cdiv(mg_cdiv(K, waves), 8) * 8);
+    return r;
+}
+bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
+
 }  // namespace
+
+extern "C" int mg_linear_route(int M, int K, int N, int w_sn, int w_sc, int perm_L, int x_aligned, int w_aligned,
+                               int* kcontig, int* vec, int* ksplit) {
+    MG_CHECK_ARG(perm_L >= 0 && (perm_L == 0 || N % perm_L == 0), "mg_linear_route: perm_L must divide N");
+    MG_CHECK_ARG(M > 0 && K > 0 && N > 0 && w_sn > 0 && w_sc > 0, "mg_linear_route: bad shape");
+    MG_CHECK_ARG(w_sn == 1 || w_sc == 1, "mg_linear_route: one weight stride must be 1");
+    const LinRoute r = linear_route(M, K, N, w_sn, w_sc, perm_L, x_aligned != 0, w_aligned != 0);
+    if (kcontig) *kcontig = r.kcontig;
+    if (vec) *vec = r.vec;
+    if (ksplit) *ksplit = r.ksplit;
+    return r.window_gemm ? 0 : 1;
+}
 
 extern "C" size_t mg_linear_workspace_bytes(int M, int N, int K) {
     const int ks = plan_ksplit(M, N, K);
@@ -201,10 +239,8 @@ extern "C" int mg_linear_perm(const float* x, const float* w, float* y, int M, i
     MG_CHECK_ARG(perm_L >= 0 && (perm_L == 0 || N % perm_L == 0), "mg_linear_perm: perm_L must divide N");
     MG_CHECK_ARG(M > 0 && K > 0 && N > 0 && w_sn > 0 && w_sc > 0, "mg_linear: bad shape");
     MG_CHECK_ARG(w_sn == 1 || w_sc == 1, "mg_linear: one weight stride must be 1");
-    // The permuted forward (decoder.pre.2) with enough rows and columns for the 64x64-tile kernel to fill the chip by its
-    // output tiling alone: 13.2 us there against 20.3 here at the fused step's 2B = 128 rows (64 rows: 12.8 against 11.1)
-    if (perm_L > 1 && w_sc == 1 && M >= 128 && (K & 63) == 0 && (N & 63) == 0 && mg_cdiv(M, 64) * (long)(N / 64) >= 192 &&
-        ((((uintptr_t)x) | ((uintptr_t)w)) & 15) == 0 && (w_sn & 3) == 0 && !getenv("MG_LINEAR_SKINNY_ONLY"))
+    const LinRoute r = linear_route(M, K, N, w_sn, w_sc, perm_L, al16(x), al16(w));
+    if (r.window_gemm)
         return mg_conv_linear_perm(x, w, y, M, K, N, w_sn, epi, perm_L, (hipStream_t)stream);
     LinP p{};
     p.x = x; p.w = w; p.y = y; p.M = M; p.K = K; p.N = N; p.w_sn = w_sn; p.w_sc = w_sc;
@@ -212,13 +248,9 @@ extern "C" int mg_linear_perm(const float* x, const float* w, float* y, int M, i
     p.perm_L = perm_L > 1 ? perm_L : 0;
     p.perm_C = p.perm_L ? N / p.perm_L : 0;
     if (p.e.scale && !p.e.shift) { mg_set_error("mg_linear: scale without shift"); return MG_EARG; }
-    p.ksplit = plan_ksplit(M, N, K);
-    const bool kcontig = (w_sc == 1);
-    // vector path: every wave's K range is a multiple of 8 inside K, rows 16-byte aligned
-    const int waves = NW * p.ksplit;
-    const bool vec = (K % (8 * waves) == 0) && ((((uintptr_t)x) & 15) == 0) &&
-                     (!kcontig || ((((uintptr_t)w) & 15) == 0 && (w_sn & 3) == 0));
-    p.kw = vec ? K / waves : (int)(mg_cdiv(mg_cdiv(K, waves), 8) * 8);
+    p.ksplit = r.ksplit;
+    const bool kcontig = r.kcontig, vec = r.vec;
+    p.kw = r.kw;
     if (p.ksplit > 1) {
         const size_t need = (size_t)p.ksplit * M * N * sizeof(float);
         if (!work || work_bytes < need) { mg_set_error("mg_linear: workspace too small (%zu < %zu)", work_bytes, need); return MG_EWORK; }

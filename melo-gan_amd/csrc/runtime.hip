@@ -14,7 +14,7 @@ void mg_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int mg_version(void) { return 102; }
+int mg_version(void) { return 103; }
 const char* mg_last_error(void) { return g_err; }
 
 int mg_graph_begin(mg_stream_t stream) {

@@ -94,9 +94,15 @@ _THIN_SYMBOLS = {1: "thin_in_kernel%.0s", 2: "thin_out_kernel<%s,4>", 3: "thin_o
 
 def _conv_work(lib, B, Tout, N, Cin, device):
     """Split-K scratch for small-output convolutions (only they can use it: <= 8 MB of output)."""
+    need = conv_work_bytes(B, Tout, N, Cin)
+    return workspace(need, device, "conv") if need else None
+
+
+def conv_work_bytes(B, Tout, N, Cin) -> int:
+    """Bytes of split-K scratch conv_gather / conv_scatter2 offer the library for a shape (0: none)."""
     if Cin < 64 or B * Tout * N > (1 << 21):
-        return None
-    return workspace(lib.mg_conv_workspace_bytes(B, Tout, N), device, "conv")
+        return 0
+    return L.load().mg_conv_workspace_bytes(B, Tout, N)
 
 
 def conv_gather(x: Tensor, w: Tensor, y: Tensor, N: int, K: int, stride: int, w_sn: int, w_sc: int,
@@ -137,6 +143,26 @@ def conv_gather(x: Tensor, w: Tensor, y: Tensor, N: int, K: int, stride: int, w_
         rc = launch()
     L.check(rc, "mg_conv1d_gather")
     return y
+
+
+def conv_plan(B: int, Tin: int, Cin: int, N: int, K: int, stride: int, scatter2: bool = False, odd: bool = False):
+    """(ksplit, cps) of the launch conv_gather / conv_scatter2 make for an x of (B, Tin, Cin) (mg_conv_plan): the blockIdx.z
+    slabs of the channel reduction (> 1: conv_finish_kernel sums them and runs the epilogue) and the channel chunks per slab,
+    given the workspace the op itself offers.  Host only; reads MG_SPLITK_TARGET / MG_FORCE_TILE as the launch does."""
+    Tout = (2 * Tin - (1 if odd else 0)) if scatter2 else (Tin + 2 * ((K - 1) // 2) - K) // stride + 1
+    ks, cps = C.c_int(), C.c_int()
+    L.check(L.load().mg_conv_plan(B, Tin if scatter2 else Tout, Tout, N, Cin, K, stride, 1 if scatter2 else 0,
+                                  conv_work_bytes(B, Tout, N, Cin), C.byref(ks), C.byref(cps)), "mg_conv_plan")
+    return ks.value, cps.value
+
+
+def conv_finish_vec(y: Tensor, N: int, *tensors) -> bool:
+    """Whether the split launch conv_gather / conv_scatter2 make into y (B, Ty, N) is finished by conv_finish_kernel<true>
+    (mg_conv_finish_vec, the launch's own predicate); tensors: the elementwise epilogue tensors given (None allowed).  The
+    split-K scratch the op offers is the "conv" workspace of the current stream."""
+    work = workspace(1, y.device, "conv")
+    aligned = all(t is None or t.data_ptr() % 16 == 0 for t in (work, y) + tensors)
+    return bool(L.load().mg_conv_finish_vec(N, y.shape[1] * N, int(aligned)))
 
 
 def wino3_supported(B: int, T: int, Cin: int, N: int) -> bool:
@@ -380,13 +406,29 @@ def conv16(x: Tensor, wq: Tensor, y: Tensor, N: int, transposed: bool, odd: bool
 SKINNY_MAX_ROWS = 512      # Linear layers with at most this many rows use the skinny-GEMM kernel
 
 
+def linear_route(M: int, K: int, N: int, w_sn: int, w_sc: int, perm_L: int = 0, x_aligned: bool = True, w_aligned: bool = True):
+    """(symbol, ksplit) of the launch mg_linear_perm makes (mg_linear_route): the window GEMM a permuted forward with many
+    rows is routed to, or linear_skinny_kernel<W_KCONTIG,VEC>; ksplit > 1: linear_finish_kernel follows.  x_aligned /
+    w_aligned: the tensor starts on a 16-byte boundary.  Host only; reads MG_LINEAR_SKINNY_ONLY / MG_FORCE_TILE as the launch
+    does."""
+    lib = L.load()
+    kc, vec, ks = C.c_int(), C.c_int(), C.c_int()
+    rc = lib.mg_linear_route(M, K, N, w_sn, w_sc, perm_L, int(x_aligned), int(w_aligned), C.byref(kc), C.byref(vec), C.byref(ks))
+    if rc < 0:
+        L.check(rc, "mg_linear_route")
+    if rc == 0:
+        return "conv_wgemm_kernel<1,1,false,true,%s>" % {22: "2,2", 12: "1,2", 11: "1,1"}[lib.mg_conv_tile_config(M, N, 0)], 1
+    return "linear_skinny_kernel<%s,%s>" % ("true" if kc.value else "false", "true" if vec.value else "false"), ks.value
+
+
 def _linear(x, w, y, K, N, w_sn, w_sc, epi, perm_L=0):
     M = x.shape[0]
     e = epilogue((M, N), N, **epi)
     lib = L.load()
     need = lib.mg_linear_workspace_bytes(M, N, K)
     work = workspace(need, x.device, "linear") if need else None
-    with _observe(lambda: "linear_skinny_kernel", 2.0 * M * N * K):
+    sym = lambda: linear_route(M, K, N, w_sn, w_sc, perm_L, x.data_ptr() % 16 == 0, w.data_ptr() % 16 == 0)[0]  # noqa: E731
+    with _observe(sym, 2.0 * M * N * K):
         rc = lib.mg_linear_perm(_p(x), _p(w), _p(y), M, K, N, w_sn, w_sc, C.byref(e), perm_L, _p(work),
                                 work.numel() if work is not None else 0, _stream())
     L.check(rc, "mg_linear")

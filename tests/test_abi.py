@@ -75,3 +75,21 @@ def test_ops_refuse_cpu_tensors():
     from melo_gan_amd import ops
     with pytest.raises(ValueError):
         ops.conv1d_fwd(torch.zeros(1, 8, 4), torch.zeros(8, 4, 5), torch.zeros(1, 4, 8), 2)
+
+
+def test_loading_the_library_before_torch_leaves_one_hip_runtime():
+    """build() loads the library before anything has imported torch.  torch's wheel carries its own libamdhip64.so; if the
+    library pulled in the system's copy first, the process would hold two HIP runtimes and the second to open the device
+    would find none (smoke() after build() in one process).  _lib.load() therefore imports torch first: checked in a fresh
+    process by counting the runtimes mapped."""
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import melo_gan_amd\n"
+            "from melo_gan_amd import _lib\n"
+            "_lib.load()\n"
+            "import torch\n"
+            "print(len({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))\n" % ROOT)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.strip().splitlines()[-1] == "1", out.stdout
