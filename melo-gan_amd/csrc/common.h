@@ -4,6 +4,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdint.h>
+#include <atomic>
 #include "../../include/melo_gan_hip.h"
 
 #define MG_OK 0
@@ -104,8 +105,49 @@ __device__ __forceinline__ float mg_apply_epilogue(const mg_epilogue& E, float v
     return v;
 }
 
-// The same epilogue for a small per-thread set of values, as whole-set passes behind ONE uniform branch each: with the
-// activation switch evaluated per element hipcc computed erff and tanhf for every element and selected afterwards.
+// v[q] = act(v[q]) / v[q] *= act'(g[q]) over a small per-thread set (float[NV], f32x4, f32x16: anything with v[q]) as ONE
+// whole-set pass behind ONE uniform branch per activation kind: with the activation switch evaluated per element hipcc
+// computed erff and tanhf for every element of every launch and selected afterwards (4 us of a 16-us workgroup on the
+// B=64 window-GEMM layers).
+template <int NV, class V>
+__device__ __forceinline__ void mg_act_set(int act, V& v) {
+    if (act == MG_ACT_RELU) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_RELU, v[q]);
+    } else if (act == MG_ACT_LRELU) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_LRELU, v[q]);
+    } else if (act == MG_ACT_GELU) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_GELU, v[q]);
+    } else if (act == MG_ACT_TANH) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_TANH, v[q]);
+    }
+}
+template <int NV, class V, class G>
+__device__ __forceinline__ void mg_act_grad_set(int gact, V& v, const G& g) {
+    if (gact == MG_ACT_RELU) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_RELU, g[q]);
+    } else if (gact == MG_ACT_LRELU) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_LRELU, g[q]);
+    } else if (gact == MG_ACT_GELU) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_GELU, g[q]);
+    } else if (gact == MG_ACT_TANH) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_TANH, g[q]);
+    }
+}
+
+// mg_apply_epilogue for a small per-thread set of values with a channel of its own each (conv_finish_kernel,
+// linear_skinny.hip, conv_thin.hip), as whole-set passes.
+// Elementwise operands (here and in mg_epilogue_column) are loaded UNCONDITIONALLY with row-clamped indices (element 0
+// always exists), all NV in flight, and applied afterwards: behind `if (ok)` hipcc emitted branch + load + wait per
+// element -- NV dependent memory round trips, 8-12 us of the emotion discriminator's data-gradient launches.  Values of
+// rows outside the tensor are never stored.
 template <int NV>
 __device__ __forceinline__ void mg_apply_epilogue_set(const mg_epilogue& E, float (&v)[NV], const int (&n)[NV],
                                                       const long (&di)[NV], const bool (&ok)[NV]) {
@@ -121,38 +163,12 @@ __device__ __forceinline__ void mg_apply_epilogue_set(const mg_epilogue& E, floa
 #pragma unroll
         for (int q = 0; q < NV; ++q) if (ok[q]) E.zout[di[q]] = v[q];
     }
-    if (E.act == MG_ACT_RELU) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_RELU, v[q]);
-    } else if (E.act == MG_ACT_LRELU) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_LRELU, v[q]);
-    } else if (E.act == MG_ACT_GELU) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_GELU, v[q]);
-    } else if (E.act == MG_ACT_TANH) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) v[q] = mg_act(MG_ACT_TANH, v[q]);
-    }
-    // elementwise operands: unconditional clamped loads (all in flight), applied afterwards -- a load behind `if (ok)`
-    // compiles to branch + load + wait per element
+    mg_act_set<NV>(E.act, v);
     if (E.gref) {
         float g[NV];
 #pragma unroll
         for (int q = 0; q < NV; ++q) g[q] = E.gref[ok[q] ? di[q] : 0];
-        if (E.gact == MG_ACT_RELU) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_RELU, g[q]);
-        } else if (E.gact == MG_ACT_LRELU) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_LRELU, g[q]);
-        } else if (E.gact == MG_ACT_GELU) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_GELU, g[q]);
-        } else if (E.gact == MG_ACT_TANH) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) v[q] *= mg_act_grad(MG_ACT_TANH, g[q]);
-        }
+        mg_act_grad_set<NV>(E.gact, v, g);
     }
     if (E.emul) {
         float g[NV];
@@ -165,6 +181,63 @@ __device__ __forceinline__ void mg_apply_epilogue_set(const mg_epilogue& E, floa
 #pragma unroll
         for (int q = 0; q < NV; ++q) if (ok[q]) v[q] *= E.gscale[n[q]];
     }
+}
+
+// mg_apply_epilogue for NV accumulator values of ONE output column n (a lane of an MFMA tile kernel: f32x4, f32x16).
+// index(r, di) -> bool gives the dense output index of value r and whether it lies inside the tensor.  Runs bias .. gscale
+// in the header's order; `accumulate`, the final store and every rider (statistics, pool, mix, bnb, perm) stay with the
+// caller.
+template <int NV, class V, class Index>
+__device__ __forceinline__ void mg_epilogue_column(const mg_epilogue& E, V& a, int n, const Index& index) {
+    unsigned di;
+    if (E.bias) {
+        const float bias = E.bias[n];
+#pragma unroll
+        for (int r = 0; r < NV; ++r) a[r] += bias;
+    }
+    if (E.scale) {
+        const float scale = E.scale[n], shift = E.shift[n];
+#pragma unroll
+        for (int r = 0; r < NV; ++r) a[r] = a[r] * scale + shift;
+    }
+    if (E.zout) {
+#pragma unroll
+        for (int r = 0; r < NV; ++r)
+            if (index(r, di)) E.zout[di] = a[r];
+    }
+    mg_act_set<NV>(E.act, a);
+    if (E.gref) {
+        float g[NV];
+#pragma unroll
+        for (int r = 0; r < NV; ++r) g[r] = E.gref[index(r, di) ? di : 0u];
+        mg_act_grad_set<NV>(E.gact, a, g);
+    }
+    if (E.emul) {
+        float g[NV];
+#pragma unroll
+        for (int r = 0; r < NV; ++r) g[r] = E.emul[index(r, di) ? di : 0u];
+#pragma unroll
+        for (int r = 0; r < NV; ++r) a[r] *= g[r];
+    }
+    if (E.gscale) {
+        const float gscale = E.gscale[n];
+#pragma unroll
+        for (int r = 0; r < NV; ++r) a[r] *= gscale;
+    }
+}
+
+// The 160 KiB dynamic-LDS opt-in of the tile kernels, made once per (kernel, device): the attribute belongs to the
+// kernel's code object on ONE device, so a process that drives several devices sets it on each.  `done` is the caller's
+// static mask for THIS kernel, one bit per device id; ids past the mask set the attribute on every launch.  Costs one
+// hipGetDevice (a thread-local read) per eager launch; nothing under graph replay.
+inline int mg_lds_optin(const void* kernel, std::atomic<uint64_t>& done) {
+    int dev = 0;
+    MG_HIP(hipGetDevice(&dev));
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
+    if (done.load(std::memory_order_relaxed) & bit) return MG_OK;
+    MG_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    done.fetch_or(bit, std::memory_order_relaxed);
+    return MG_OK;
 }
 
 // conv_thin.hip: the window GEMMs with a <= 8 channel reduction or output side; MG_EUNSUP = not such a shape

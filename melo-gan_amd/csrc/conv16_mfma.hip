@@ -305,8 +305,10 @@ __global__ __launch_bounds__(256, 2) void conv16_kernel(const Conv16P p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) a[r] = mg_act(MG_ACT_TANH, a[r]);
             }
-            // elementwise operands: unconditional row-clamped loads, all in flight, applied afterwards (behind `if (ok)`
-            // hipcc emitted branch + load + wait per element); rows outside the tensor are never stored
+            // elementwise operands: unconditional row-clamped loads, all in flight (see mg_apply_epilogue_set in common.h).
+            // This kernel keeps the sequence of mg_epilogue_column as its own text: through the shared helpers hipcc stops
+            // pairing its four values into packed instructions and contracts 1 - q (GELU) and 1 - r * r (tanh') into FMAs,
+            // which moves results by an ulp ("Where the epilogue lives").
             if (E.gref) {
                 float g[4];
 #pragma unroll
@@ -452,15 +454,8 @@ int launch16(Conv16P p, hipStream_t stream) {
     if (TB * R * 4 > 256 * MAXX) return MG_EUNSUP;        // too many window rows for the staging plan (tiny Tm)
     const size_t lds = 2 * ((size_t)TB * R * SX + WSLAB) * sizeof(float) + 256 * 4 * sizeof(float);
     auto kernel = &conv16_kernel<TR2, RT, RID>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            mg_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return MG_EHIP;
-        }
-        attr_set = true;
-    }
+    static std::atomic<uint64_t> optin;
+    if (int rc = mg_lds_optin(reinterpret_cast<const void*>(kernel), optin)) return rc;
     dim3 grid((unsigned)(p.n_ttiles * mg_cdiv(p.B, TB)), (unsigned)mg_cdiv(p.N, BN));
     hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, p);
     MG_CHECK_LAUNCH("conv16");

@@ -310,19 +310,15 @@ int launch_bf16(const ConvBP& p, int xf32, int yf32, hipStream_t stream) {
     constexpr int XR = BM + K - 1;
     const size_t ldsb = (size_t)2 * (XR * PX + K * BN * PX) * sizeof(__bf16);
     dim3 grid((unsigned)((long)p.B * p.T / BM), (unsigned)(p.N / BN));
-    auto go = [&](auto kernel) -> int {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { mg_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return MG_EHIP; }
-            attr_set = true;
-        }
+    static std::atomic<uint64_t> optin[2][2];      // one mask per kernel: the four share a function type
+    auto go = [&](auto kernel, std::atomic<uint64_t>& done) -> int {
+        if (int rc = mg_lds_optin(reinterpret_cast<const void*>(kernel), done)) return rc;
         hipLaunchKernelGGL(kernel, grid, dim3(256), ldsb, stream, p);
         MG_CHECK_LAUNCH("conv_bf16");
         return MG_OK;
     };
-    if (xf32) return yf32 ? go(&conv_bf16_kernel<K, true, true>) : go(&conv_bf16_kernel<K, true, false>);
-    return yf32 ? go(&conv_bf16_kernel<K, false, true>) : go(&conv_bf16_kernel<K, false, false>);
+    if (xf32) return yf32 ? go(&conv_bf16_kernel<K, true, true>, optin[1][1]) : go(&conv_bf16_kernel<K, true, false>, optin[1][0]);
+    return yf32 ? go(&conv_bf16_kernel<K, false, true>, optin[0][1]) : go(&conv_bf16_kernel<K, false, false>, optin[0][0]);
 }
 
 }  // namespace

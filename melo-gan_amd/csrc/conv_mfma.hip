@@ -467,9 +467,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgemm_kernel(const ConvP p) {
     }
 
     // ---- epilogue ----
-    // Written as whole-tile passes over the accumulator registers, each selected by ONE uniform branch: with the
-    // activation switch inside the per-element loop hipcc evaluated erff/tanhf for every element of every launch
-    // and selected afterwards (4 us of a 16-us workgroup on the B=64 layers).
     MG_STAMP(3);
     const mg_epilogue& E = p.e;
     const long slab = (long)p.B * p.Tout * p.N;
@@ -511,6 +508,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgemm_kernel(const ConvP p) {
                         if (index(r, di, yi)) dst[di] = a[r];
                     continue;
                 }
+                // The sequence of mg_epilogue_column (common.h), kept as the kernel's own text around the two activation
+                // helpers: with the whole helper inlined here hipcc emits ~330 fewer instructions for the 64x64
+                // instantiations but holds ~23 more SGPRs and up to 11 more VGPRs, and <1,3,*,*,1,1> (88 -> 99 VGPRs) loses
+                // a wave per SIMD.
                 const int nw = conv_wrow(p, n);          // per-column vectors follow the weight row
                 if (E.bias) {
                     const float bias = E.bias[nw];
@@ -527,40 +528,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgemm_kernel(const ConvP p) {
                     for (int r = 0; r < 16; ++r)
                         if (index(r, di, yi)) E.zout[di] = a[r];
                 }
-                if (E.act == MG_ACT_RELU) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_RELU, a[r]);
-                } else if (E.act == MG_ACT_LRELU) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_LRELU, a[r]);
-                } else if (E.act == MG_ACT_GELU) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_GELU, a[r]);
-                } else if (E.act == MG_ACT_TANH) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_TANH, a[r]);
-                }
-                // Elementwise operands are loaded UNCONDITIONALLY, row-clamped (element 0 always exists), all sixteen in
-                // flight, and applied afterwards: behind `if (row is inside)` hipcc emitted branch + load + wait per
-                // element -- sixteen dependent memory round trips, 8-12 us of the emotion discriminator's data-gradient
-                // launches.  Values of rows outside the tensor are never stored.
+                mg_act_set<16>(E.act, a);
                 if (E.gref) {
                     float g[16];
 #pragma unroll
                     for (int r = 0; r < 16; ++r) g[r] = E.gref[index(r, di, yi) ? di : 0u];
-                    if (E.gact == MG_ACT_RELU) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_RELU, g[r]);
-                    } else if (E.gact == MG_ACT_LRELU) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_LRELU, g[r]);
-                    } else if (E.gact == MG_ACT_GELU) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_GELU, g[r]);
-                    } else if (E.gact == MG_ACT_TANH) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_TANH, g[r]);
-                    }
+                    mg_act_grad_set<16>(E.gact, a, g);
                 }
                 if (E.emul) {
                     float g[16];
@@ -708,16 +681,8 @@ int launch_cfg(const ConvP& p0, long lds_pad, hipStream_t stream) {
     }
     const bool nck = p.w_sc < p.w_sn;   // (c,k) contiguous for a fixed n
     auto kernel = nck ? &conv_wgemm_kernel<S, K, TR2, true, TM, TN> : &conv_wgemm_kernel<S, K, TR2, false, TM, TN>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[nck]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) {
-            mg_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return MG_EHIP;
-        }
-        attr_set[nck] = true;
-    }
+    static std::atomic<uint64_t> optin[2];
+    if (int rc = mg_lds_optin(reinterpret_cast<const void*>(kernel), optin[nck])) return rc;
     dim3 grid(plan.gx, plan.gy);
     const long total = (long)p.B * p.Tout * p.N;
     p.ksplit = plan.ksplit;

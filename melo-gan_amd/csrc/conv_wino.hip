@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void wino3_kernel(const WinoP p) {
         if (c0 >= p.Cin) break;
     }
 
-    // ---- output transform + the fused epilogue (whole-tile passes behind uniform branches, as in conv_mfma.hip) ----
+    // ---- output transform + the fused epilogue (mg_epilogue_column, one call per output phase) ----
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float m1 = acc[1][r], m2 = acc[2][r];
@@ -192,65 +192,8 @@ __global__ __launch_bounds__(256, 2) void wino3_kernel(const WinoP p) {
             di = lin0 + (unsigned)(dr * p.N);
             return LIN || (t0 + 2 * ip0 + ph + dr < p.T);
         };
+        mg_epilogue_column<16>(E, a, n, index);
         unsigned di;
-        if (E.bias) {
-            const float bias = E.bias[n];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] += bias;
-        }
-        if (E.scale) {
-            const float scale = E.scale[n], shift = E.shift[n];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] = a[r] * scale + shift;
-        }
-        if (E.zout) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if (index(r, di)) E.zout[di] = a[r];
-        }
-        if (E.act == MG_ACT_RELU) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_RELU, a[r]);
-        } else if (E.act == MG_ACT_LRELU) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_LRELU, a[r]);
-        } else if (E.act == MG_ACT_GELU) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_GELU, a[r]);
-        } else if (E.act == MG_ACT_TANH) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] = mg_act(MG_ACT_TANH, a[r]);
-        }
-        if (E.gref) {      // loaded unconditionally (row-clamped), all sixteen in flight, applied afterwards
-            float g[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) g[r] = E.gref[index(r, di) ? di : 0u];
-            if (E.gact == MG_ACT_RELU) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_RELU, g[r]);
-            } else if (E.gact == MG_ACT_LRELU) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_LRELU, g[r]);
-            } else if (E.gact == MG_ACT_GELU) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_GELU, g[r]);
-            } else if (E.gact == MG_ACT_TANH) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a[r] *= mg_act_grad(MG_ACT_TANH, g[r]);
-            }
-        }
-        if (E.emul) {
-            float g[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) g[r] = E.emul[index(r, di) ? di : 0u];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] *= g[r];
-        }
-        if (E.gscale) {
-            const float gscale = E.gscale[n];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[r] *= gscale;
-        }
         if (E.accumulate) {
             float g[16];
 #pragma unroll
@@ -372,12 +315,8 @@ int mg_conv1d_wino3(const float* x, const float* wt, float* y, int B, int T, int
     size_t lds = 2 * (size_t)BUF * sizeof(float);
     // occupancy cap of launches that run beside another stream's critical path (conv_mfma.hip: launch_cfg)
     if (lds_pad > 0 && lds + (size_t)lds_pad <= 160 * 1024) lds += (size_t)lds_pad;
-    static bool attr_set = false;
-    if (!attr_set) {
-        MG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-        attr_set = true;
-    }
+    static std::atomic<uint64_t> optin;
+    if (int rc = mg_lds_optin(reinterpret_cast<const void*>(&wino3_kernel), optin)) return rc;
     dim3 grid((unsigned)(B * p.tiles_per_seq), (unsigned)(N / 64));
     hipLaunchKernelGGL(wino3_kernel, grid, dim3(256), lds, (hipStream_t)stream, p);
     MG_CHECK_LAUNCH("wino3");
