@@ -627,6 +627,52 @@ int mg_grad_norm_clip(const float* g, long n, float max_norm, float* out, void* 
                       mg_stream_t stream);
 size_t mg_grad_norm_workspace_bytes(long n);
 
+/* ---- the latent-mode emotion classifier's training step in two launches (csrc/mlp_train.hip) ----
+ * The network is MLPClassifier (src/emotion_discriminator/ed_model.py:72-95): n_hidden x [Linear, GELU (exact erf),
+ * Dropout(p)] and a Linear head, on (rows, in_dim) latents; the loss is the mean cross-entropy of train_ed.py:51-82.
+ * Supported: n_hidden 1..4, in_dim and every width 1..512 (no multiple of anything), n_classes 2..32, rows >= 1; anything
+ * else returns -1 before a launch.  Exact fp32 on v_mfma_f32_16x16x4_f32; no atomics: reruns and replays give identical bits.
+ * Layer l < n_hidden is hidden layer l, layer n_hidden is the head; w[l] is (out, in) row-major as in the state_dict. */
+#define MG_MLP_MAX_HIDDEN 4
+typedef struct mg_mlp_cls {
+    int n_hidden, in_dim, width[MG_MLP_MAX_HIDDEN], n_classes;
+    const float* w[MG_MLP_MAX_HIDDEN + 1];  /* the weights the layers compute with (w_orig / sigma under spectral norm) */
+    const float* b[MG_MLP_MAX_HIDDEN + 1];
+    float* z[MG_MLP_MAX_HIDDEN];            /* (rows, width[l]) pre-activation x W^T + b */
+    float* a[MG_MLP_MAX_HIDDEN];            /* (rows, width[l]) GELU(z) * mask */
+    float* dz[MG_MLP_MAX_HIDDEN];           /* (rows, width[l]) d loss / d z = (dz[l+1] W[l+1]) * GELU'(z) * mask */
+    float* mask[MG_MLP_MAX_HIDDEN];         /* (rows, width[l]) dropout keep-mask / (1 - p) */
+} mg_mlp_cls;
+/* Launch A, the per-row half: a workgroup owns 16 rows and walks them through every layer with the activations in LDS,
+ * then the cross-entropy, then the data gradients back to hidden layer 0.  Writes z / a / dz of every hidden layer,
+ * logits (rows, n_classes), loss_rows[r] = logsumexp(logits[r]) - logits[r, y[r]] and dlogits = (softmax - onehot) / rows;
+ * a label outside [0, n_classes) makes its row's term and dlogits NaN (as mg_softmax_ce) and is never used as an index.
+ *   rows' source: x (rows, in_dim) / y (rows) as they are, or, with split_x != NULL, gathered from split_x (src_rows, in_dim) /
+ *     split_y by mg_stage_augment's position rules (`rule`, order, order_len, counter = step_counter, base) -- the staged
+ *     rows and labels are then also written to x / y.
+ *   train = 0 (eval): no masks, no backward: logits and loss_rows only (z / a are written where not NULL).
+ *   draw = 0: mask[l] is read.  draw = 1: mask[l] is drawn and written: Philox4x32-10 keyed by seed, counter = (e / 4,
+ *     (e / 4 >> 32) ^ (stream << 28), step lo, step hi), word e % 4, e = the element's index in (rows, width[l]), stream =
+ *     l for l < 2 -- element for element what mg_rng_fill(NULL, 0, NULL, 0, mask0, ., mask1, ., p_drop, seed, step_counter)
+ *     writes -- and l + 2 for l = 2, 3.  *step_counter is read, never written.
+ *   tick_state != NULL: the Adam state {step, beta1^step, beta2^step} is advanced as by mg_rng_fill_tick (not read here). */
+int mg_mlp_cls_fwd_bwd(const mg_mlp_cls* net, int rows, float* x, int64_t* y, const float* split_x, const int64_t* split_y,
+                       long src_rows, const int64_t* order, long order_len, const uint64_t* base, int rule, int train, int draw,
+                       float p_drop, uint64_t seed, const uint64_t* step_counter, double* tick_state, float beta1, float beta2,
+                       float* logits, float* loss_rows, float* dlogits, mg_stream_t stream);
+/* Launch B, the per-parameter half: the grid is tiled over every layer's (out, in) weight and its bias; a wave reduces its
+ * 16 x 16 tile over the rows in row order.  g[w_off[l] + o * in + i] = sum_r dz[l][r, o] * a[l-1][r, i] (a[-1] = x, dz[n_hidden]
+ * = dlogits) and g[b_off[l] + o] = sum_r dz[l][r, o], always; w_off / b_off: n_hidden + 1 element offsets into the flat
+ * buffers of n_flat floats (host arrays).  apply != 0: the same threads then apply AdamW to their elements of p / m / v from
+ * the gradient in registers -- mg_adam_flat_ticked's formula and `state` semantics (state is read, never written; weight
+ * decay decoupled).  One workgroup also writes loss[0] = (sum of loss_rows in row order) / rows, adds the batch to `metrics`
+ * (if not NULL) exactly as mg_ed_metrics_acc does, and advances *rng_step (if not NULL; apply mode only). */
+int mg_mlp_cls_wgrad_update(const mg_mlp_cls* net, int rows, const float* x, const float* dlogits, const long* w_off,
+                            const long* b_off, long n_flat, float* g, float* p, float* m, float* v, int apply, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, const double* state,
+                            const float* loss_rows, float* loss, const float* logits, const int64_t* y, float* metrics,
+                            uint64_t* rng_step, mg_stream_t stream);
+
 /* ---- VAE extras (src/ae/model.py:127-133, src/ae/train_ae.py:35-51) ---- */
 /* z = mu + eps*exp(0.5*logvar) */
 int mg_reparam_fwd(const float* mu, const float* logvar, const float* eps, float* z, long n, mg_stream_t stream);

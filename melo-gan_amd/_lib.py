@@ -83,6 +83,15 @@ class WqEntry(C.Structure):
 
 MAX_WQ_ENTRIES = 8
 
+MLP_MAX_HIDDEN, MLP_MAX_DIM, MLP_MAX_CLASSES = 4, 512, 32
+
+
+class MlpCls(C.Structure):
+    _fields_ = [("n_hidden", i32), ("in_dim", i32), ("width", i32 * MLP_MAX_HIDDEN), ("n_classes", i32),
+                ("w", vp * (MLP_MAX_HIDDEN + 1)), ("b", vp * (MLP_MAX_HIDDEN + 1)), ("z", vp * MLP_MAX_HIDDEN),
+                ("a", vp * MLP_MAX_HIDDEN), ("dz", vp * MLP_MAX_HIDDEN), ("mask", vp * MLP_MAX_HIDDEN)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header.
 SIGNATURES = {
     "mg_version": (i32, []),
@@ -169,6 +178,10 @@ SIGNATURES = {
     "mg_adam_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp]),
     "mg_adam_flat_ticked": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp, vp]),
     "mg_adam_flat_wq": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, i32, vp, vp, i32, vp]),
+    "mg_mlp_cls_fwd_bwd": (i32, [C.POINTER(MlpCls), i32, vp, vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, f32, C.c_uint64, vp, vp, f32, f32,
+                                 vp, vp, vp, vp]),
+    "mg_mlp_cls_wgrad_update": (i32, [C.POINTER(MlpCls), i32, vp, vp, C.POINTER(i64), C.POINTER(i64), i64, vp, vp, vp, vp, i32, f32, f32,
+                                      f32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mg_grad_norm_workspace_bytes": (sz, [i64]),
     "mg_grad_norm_clip": (i32, [vp, i64, f32, vp, vp, sz, vp]),
     "mg_reparam_fwd": (i32, [vp, vp, vp, vp, i64, vp]),

@@ -226,6 +226,25 @@ __device__ __forceinline__ void mg_epilogue_column(const mg_epilogue& E, V& a, i
     }
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds over a 4-word counter under a 2-word key; u01 maps a word to (0, 1).
+// The counter layouts are their users' (small_kernels.hip: rng_fill_kernel, gen_inputs_kernel, aug_draw; mlp_train.hip).
+__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
+    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
+    const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
+    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+__device__ __forceinline__ void philox4(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+
 // The 160 KiB dynamic-LDS opt-in of the tile kernels, made once per (kernel, device): the attribute belongs to the
 // kernel's code object on ONE device, so a process that drives several devices sets it on each.  `done` is the caller's
 // static mask for THIS kernel, one bit per device id; ids past the mask set the attribute on every launch.  Costs one

@@ -903,22 +903,7 @@ __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __rest
 // Philox4x32-10 counter-based generator.  key = (seed lo, seed hi), counter = (element block, stream id,
 // step lo, step hi); the step counter lives in device memory and is advanced by the kernel itself so a
 // captured hipGraph draws fresh numbers on every replay.
-__device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ __forceinline__ void philox4(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// philox4 / u01: csrc/common.h (csrc/mlp_train.hip draws its dropout masks from the same streams)
 // four N(0,1) draws from one Philox output block (Box-Muller on the pairs (c0, c1) and (c2, c3))
 __device__ __forceinline__ void box_muller4(const unsigned (&c)[4], float (&v)[4]) {
     const float r0 = sqrtf(-2.f * logf(u01(c[0]))), r1 = sqrtf(-2.f * logf(u01(c[2])));

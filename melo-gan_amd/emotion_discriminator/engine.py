@@ -36,7 +36,8 @@ class EdEngine:
         uses as its own -- the same model at a different batch size (the trailing partial batch of an epoch: the
         reference's loaders have no drop_last, ed_dataset.py:542-558)."""
         if cfg.get("input_mode", "latent") != "notes":
-            raise ValueError("EdEngine: only input_mode='notes' (the convolutional encoder) is pre-trained here")
+            raise ValueError("EdEngine pre-trains input_mode='notes' (the convolutional encoder); input_mode='latent' is "
+                             "latent_engine.EdLatentEngine (latent_engine.make_engine picks by input_mode)")
         self.cfg = cfg
         self.dev = d = torch.device(device)
         self.B = B = int(batch_size or cfg.get("batch_size", 64))

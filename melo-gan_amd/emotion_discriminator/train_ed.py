@@ -9,7 +9,13 @@ Data: the row-aligned arrays the GAN trainer already uses, `<splits_dir>/<stem o
 (kept resident in HBM); the reference's per-file manifest/.npz loader (ed_dataset.py) is out of scope.  Like the
 reference's loaders (no drop_last, ed_dataset.py:542-558) an epoch ends with the trailing partial batch, run by a second
 engine of that batch size over the same parameters (EdEngine.tail); metrics are sample-weighted (train_ed.py:75-82).
---synthetic N trains on N random rolls (smoke runs without the git-ignored dataset).  input_mode must be 'notes'.
+--synthetic N trains on N random rolls (smoke runs without the git-ignored dataset).
+
+input_mode 'notes' trains the convolutional encoder (EdEngine); 'latent' (the reference's default) trains the MLP on the
+(N, latent_dim) encoder latents that melo_gan_amd.ae.encode exports (EdLatentEngine: two launches per step).  The latents
+are looked up in the reference's order (ed_dataset.py:69-90): `{split}_encoder_feats_path`, `encoder_feats_path`, then
+`encoder_feats.npy` beside the split's emotion.npy.  Only a regular float array is read; the per-file mapping loaders are out
+of scope.  Latent mode has no augmentation (ed_dataset.py:322-323): `augment: true` is accepted and does nothing.
 
 Training epochs run the engine's staged step (EdEngine.step_staged): one graph replay per batch stages the batch from the
 resident split by a device-side cursor, augments it in the same pass, trains on it and adds to the epoch's metrics.  The
@@ -30,6 +36,7 @@ from .. import ops
 from ..gan import config as C
 from ..gan.utils import check_labels, emotion_to_index, seed_everything
 from .engine import EdEngine
+from .latent_engine import make_engine
 
 
 class Plateau:
@@ -52,11 +59,15 @@ class Plateau:
         return lr
 
 
-def load_split(cfg: dict, split: str, device):
+def split_dir(cfg: dict, split: str) -> str:
     key = f"{split}_split_csv"
     if not cfg.get(key):
         raise ValueError(f"Missing split csv for '{split}' in config; expected key '{key}'.")
-    d = os.path.join(cfg.get("splits_dir", os.path.dirname(cfg[key]) or "data/splits"), Path(cfg[key]).stem)
+    return os.path.join(cfg.get("splits_dir", os.path.dirname(cfg[key]) or "data/splits"), Path(cfg[key]).stem)
+
+
+def load_split(cfg: dict, split: str, device):
+    d = split_dir(cfg, split)
     paths = [os.path.join(d, n) for n in ("notes.npy", "emotion.npy")]
     if not all(os.path.exists(p) for p in paths):
         raise FileNotFoundError(f"{paths}: export the split to notes.npy / emotion.npy (the per-file .npz loader of the "
@@ -65,6 +76,52 @@ def load_split(cfg: dict, split: str, device):
     labels = check_labels(torch.tensor([emotion_to_index(e) for e in np.load(paths[1], allow_pickle=True)], dtype=torch.int64),
                           int(cfg.get("n_classes", 4)), f"{split} split labels").to(device)
     return notes, labels
+
+
+def resolve_encoder_feats(cfg: dict, split: str) -> str:
+    """ed_dataset.py:69-90: the split's own key, the global key, then encoder_feats.npy in the split's array directory."""
+    for key in (f"{split}_encoder_feats_path", "encoder_feats_path"):
+        if cfg.get(key):
+            return cfg[key]
+    return os.path.join(split_dir(cfg, split), "encoder_feats.npy")
+
+
+def latent_rows(feats, labels, latent_dim: int, where: str = "encoder_feats"):
+    """The (N, latent_dim) fp32 latents and their labels as the reference pairs them (ed_dataset.py:417-428): row i of the
+    array belongs to row i of the split; an array shorter than the split drops the split's trailing rows."""
+    feats = np.asarray(feats)
+    if feats.dtype == object or feats.dtype.kind not in "fiu":
+        raise ValueError(f"{where}: expected a regular float array (N, {latent_dim}), got dtype {feats.dtype}: the per-file "
+                         "mapping form of encoder_feats is not implemented -- export the latents with melo_gan_amd.ae.encode")
+    if feats.ndim != 2 or feats.shape[1] != latent_dim:
+        raise ValueError(f"{where}: expected shape (N, latent_dim = {latent_dim}), got {tuple(feats.shape)}")
+    n, m = feats.shape[0], len(labels)
+    if n < m:
+        print(f"[ed_dataset] encoder_feats ndarray shorter ({n}) than CSV ({m}): dropping last {m - n} rows.")
+        labels = labels[:n]
+    else:
+        print(f"[ed_dataset] encoder_feats ndarray length OK ({n}) for CSV ({m}).")
+        feats = feats[:m]
+    return np.ascontiguousarray(feats, dtype=np.float32), labels
+
+
+def load_latent_split(cfg: dict, split: str, device):
+    path, lab_path = resolve_encoder_feats(cfg, split), os.path.join(split_dir(cfg, split), "emotion.npy")
+    for p in (path, lab_path):
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"{p}: export the split's latents / labels to encoder_feats.npy (melo_gan_amd.ae.encode) and "
+                                    "emotion.npy")
+    labels = [emotion_to_index(e) for e in np.load(lab_path, allow_pickle=True)]
+    feats, labels = latent_rows(np.load(path, allow_pickle=True), labels, int(cfg.get("latent_dim", 128)), path)
+    labels = check_labels(torch.tensor(labels, dtype=torch.int64), int(cfg.get("n_classes", 4)), f"{split} split labels")
+    return torch.from_numpy(feats).to(device), labels.to(device)
+
+
+def synthetic_latent_split(n, D, seed, device):
+    """Learnable toy latents: x ~ N(0, 1), the class is the quadrant of (x0, x1) (x1 absent: of x0 alone)."""
+    x = np.random.default_rng(seed).standard_normal((n, D)).astype(np.float32)
+    y = 2 * (x[:, 0] > 0).astype(np.int64) + ((x[:, 1] > 0).astype(np.int64) if D > 1 else 0)
+    return torch.from_numpy(x).to(device), torch.from_numpy(y).to(device)
 
 
 def synthetic_split(n, T, Cn, seed, device):
@@ -148,20 +205,30 @@ def save_checkpoint(eng: EdEngine, cfg: dict, epoch: int, is_best: bool):
 
 
 def train(cfg: dict, synthetic: int = 0, use_graph: bool = True):
-    if cfg.get("input_mode", "latent") != "notes":
-        raise ValueError("melo_gan_amd.emotion_discriminator.train_ed: input_mode must be 'notes'")
-    aug = augment_from_cfg(cfg)                # ValueError on a bad augment_cfg, before the GPU is touched
+    mode = cfg.get("input_mode", "latent")
+    if mode not in ("latent", "notes"):
+        raise ValueError("melo_gan_amd.emotion_discriminator.train_ed: input_mode must be 'latent' or 'notes'")
+    latent = mode == "latent"
+    aug = None if latent else augment_from_cfg(cfg)      # ValueError on a bad augment_cfg, before the GPU is touched
+    if latent and cfg.get("augment", False):
+        print("[ed_dataset] augment: true has no effect with input_mode=latent (the reference augments notes only)")
     if not torch.cuda.is_available():
         raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
     seed_everything(cfg.get("seed", 42))
     device = torch.device("cuda", torch.cuda.current_device())
     T, Cn = int(cfg.get("max_notes", 512)), int(cfg.get("note_dim", 4))
-    if synthetic:
+    n_val = max(synthetic // 4, int(cfg.get("batch_size", 64)))
+    if synthetic and latent:
+        D = int(cfg.get("latent_dim", 128))
+        xt, yt = synthetic_latent_split(synthetic, D, cfg.get("seed", 42), device)
+        xv, yv = synthetic_latent_split(n_val, D, cfg.get("seed", 42) + 1, device)
+    elif synthetic:
         xt, yt = synthetic_split(synthetic, T, Cn, cfg.get("seed", 42), device)
-        xv, yv = synthetic_split(max(synthetic // 4, int(cfg.get("batch_size", 64))), T, Cn, cfg.get("seed", 42) + 1, device)
+        xv, yv = synthetic_split(n_val, T, Cn, cfg.get("seed", 42) + 1, device)
     else:
-        (xt, yt), (xv, yv) = load_split(cfg, "train", device), load_split(cfg, "val", device)
-    eng = EdEngine(cfg, device, int(cfg.get("batch_size", 64)), T)
+        load = load_latent_split if latent else load_split
+        (xt, yt), (xv, yv) = load(cfg, "train", device), load(cfg, "val", device)
+    eng = make_engine(cfg, device, int(cfg.get("batch_size", 64)), T)
     eng.init_weights(cfg.get("seed", 42))
     if xt.shape[0] == 0:
         raise ValueError("train: the training split is empty")
@@ -180,7 +247,7 @@ def train(cfg: dict, synthetic: int = 0, use_graph: bool = True):
     best, best_epoch = (float("inf") if by_loss else 0.0), 0
     gen = torch.Generator().manual_seed(cfg.get("seed", 42))
     print("Starting Emotion Discriminator Training")
-    print("Input mode:", cfg["input_mode"], "| Device:", device, "| Epochs:", epochs, "| Best metric target:",
+    print("Input mode:", mode, "| Device:", device, "| Epochs:", epochs, "| Best metric target:",
           cfg.get("metric_for_best", "val_loss"))
     with torch.cuda.stream(eng.stream):
         for epoch in range(1, epochs + 1):

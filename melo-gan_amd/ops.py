@@ -1438,6 +1438,157 @@ def ed_metrics_acc(logits, labels, loss, rows, acc):
             "mg_ed_metrics_acc")
 
 
+class MlpNet:
+    """The latent-mode classifier (MLPClassifier, ed_model.py:72-95) as mg_mlp_cls: `ws` / `bs` are the n_hidden + 1 weights
+    (out, in) and biases the layers compute with, z / a / dz / mask the per-hidden-layer (rows, width) buffers (None: eval
+    only).  Checks the kernels' domain -- 1..4 hidden layers, in_dim and widths in 1..512, 2..32 classes -- and every shape on
+    the host; keeps the tensors alive."""
+
+    def __init__(self, rows, ws, bs, z=None, a=None, dz=None, mask=None):
+        n = len(ws) - 1
+        if not 1 <= n <= L.MLP_MAX_HIDDEN or len(bs) != n + 1:
+            raise ValueError(f"MlpNet: 1..{L.MLP_MAX_HIDDEN} hidden layers and a head expected, got {n} hidden layer(s)")
+        if not isinstance(rows, int) or not 1 <= rows <= 1 << 24:
+            raise ValueError(f"MlpNet: rows must be in 1..2^24, got {rows!r}")
+        for w in ws:
+            _chk(w, "weight")
+            if w.dim() != 2:
+                raise ValueError("MlpNet: weights must be (out, in)")
+        self.rows, self.n_hidden, self.in_dim = rows, n, int(ws[0].shape[1])
+        self.widths = [int(w.shape[0]) for w in ws[:-1]]
+        self.n_classes = int(ws[-1].shape[0])
+        if not 1 <= self.in_dim <= L.MLP_MAX_DIM or any(not 1 <= h <= L.MLP_MAX_DIM for h in self.widths):
+            raise ValueError(f"MlpNet: in_dim and every hidden width must be in 1..{L.MLP_MAX_DIM}, got {self.in_dim}, {self.widths}")
+        if not 2 <= self.n_classes <= L.MLP_MAX_CLASSES:
+            raise ValueError(f"MlpNet: n_classes must be in 2..{L.MLP_MAX_CLASSES}, got {self.n_classes}")
+        prev = self.in_dim
+        for l, (w, b) in enumerate(zip(ws, bs)):
+            _chk(w, f"weight {l}", (w.shape[0], prev))
+            _chk(b, f"bias {l}", (w.shape[0],))
+            prev = int(w.shape[0])
+        c = self.c = L.MlpCls()
+        c.n_hidden, c.in_dim, c.n_classes = n, self.in_dim, self.n_classes
+        self.keep = [list(ws), list(bs)]
+        for l in range(n + 1):
+            c.w[l], c.b[l] = ws[l].data_ptr(), bs[l].data_ptr()
+        self.trainable = True
+        for l in range(n):
+            c.width[l] = self.widths[l]
+            for nm, lst in (("z", z), ("a", a), ("dz", dz), ("mask", mask)):
+                if lst is None:
+                    self.trainable = False
+                    continue
+                _chk(lst[l], f"{nm}[{l}]", (rows, self.widths[l]))
+                getattr(c, nm)[l] = lst[l].data_ptr()
+                self.keep.append(lst[l])
+        self.dz, self.a = dz, a
+
+
+def mlp_cls_fwd_bwd(net: MlpNet, x, y, logits, loss_rows, dlogits=None, train=True, draw=False, p_drop=0.0, seed=0,
+                    step_counter=None, tick_state=None, betas=None, stage=None):
+    """Launch A of the latent-mode classifier's step (mg_mlp_cls_fwd_bwd): forward, per-row cross-entropy and (train) the data
+    gradients of net.rows rows.  draw: the dropout masks are drawn on the device from (seed, *step_counter) and written to
+    the net's mask buffers, else read from them.  tick_state (+ betas): advance that Adam state, as rng_fill(tick_state=...).
+    stage = (split_x, split_y, order, order_len, base, last): gather the rows from the resident split by stage_augment's
+    position rules (counter = step_counter) and write them to x / y too."""
+    rows = net.rows
+    _chk(x, "x", (rows, net.in_dim))
+    _chk(y, "y", (rows,), torch.int64)
+    _chk(logits, "logits", (rows, net.n_classes))
+    _chk(loss_rows, "loss_rows", (rows,))
+    if train:
+        if not net.trainable:
+            raise ValueError("mlp_cls_fwd_bwd: training needs the net's z / a / dz / mask buffers")
+        if dlogits is None:
+            raise ValueError("mlp_cls_fwd_bwd: training needs dlogits")
+        _chk(dlogits, "dlogits", (rows, net.n_classes))
+    elif draw or tick_state is not None:
+        raise ValueError("mlp_cls_fwd_bwd: eval mode draws no masks and ticks no optimiser")
+    if step_counter is not None:
+        _chk(step_counter, "step_counter", (1,), torch.int64)
+    if draw:
+        if step_counter is None:
+            raise ValueError("mlp_cls_fwd_bwd: drawing the masks needs step_counter")
+        if not 0.0 <= p_drop < 1.0:
+            raise ValueError("mlp_cls_fwd_bwd: p_drop must be in [0, 1)")
+    b1 = b2 = 0.0
+    if tick_state is not None:
+        _chk(tick_state, "tick_state", (4,), torch.float64)
+        b1, b2 = betas
+    sx = sy = order = base = None
+    src_rows = order_len = rule = 0
+    if stage is not None:
+        sx, sy, order, order_len, base, last = stage
+        _chk(sx, "split_x")
+        if sx.dim() != 2 or sx.shape[1] != net.in_dim or sx.shape[0] == 0:
+            raise ValueError(f"mlp_cls_fwd_bwd: the split must be (n > 0, {net.in_dim}), got {tuple(sx.shape)}")
+        _chk(sy, "split_y", (sx.shape[0],), torch.int64)
+        src_rows, order_len, rule = sx.shape[0], int(order_len), (L.STAGE_LAST if last else L.STAGE_BATCH)
+        if order is not None:
+            _chk(order, "order", dtype=torch.int64)
+            if order.numel() < order_len:
+                raise ValueError("mlp_cls_fwd_bwd: order shorter than order_len")
+        elif order_len > src_rows:
+            raise ValueError("mlp_cls_fwd_bwd: order_len beyond the split")
+        if order_len <= 0 or (last and rows > order_len):
+            raise ValueError("mlp_cls_fwd_bwd: order_len must be positive (and hold the rows of the last-rows rule)")
+        if not last:
+            if step_counter is None or base is None:
+                raise ValueError("mlp_cls_fwd_bwd: the batch rule needs step_counter and base")
+            _chk(base, "base", (1,), torch.int64)
+    L.check(L.load().mg_mlp_cls_fwd_bwd(C.byref(net.c), rows, _p(x), _p(y), _p(sx), _p(sy), src_rows, _p(order), order_len, _p(base),
+                                        rule, 1 if train else 0, 1 if draw else 0, float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        _p(step_counter), _p(tick_state), b1, b2, _p(logits), _p(loss_rows), _p(dlogits), _stream()),
+            "mg_mlp_cls_fwd_bwd")
+
+
+def mlp_cls_wgrad_update(net: MlpNet, x, dlogits, w_off, b_off, g, loss_rows, loss, adam=None, metrics=None, logits=None, y=None,
+                         rng_step=None):
+    """Launch B (mg_mlp_cls_wgrad_update): every layer's weight and bias gradient into the flat buffer g at the element offsets
+    w_off / b_off (n_hidden + 1 each), loss[0] = mean(loss_rows), optionally the epoch metrics (ed_metrics_acc's sums; needs
+    logits and y).  adam = dict(p, m, v, state, lr, betas, eps, weight_decay): the same threads also apply AdamW (adam_flat's
+    ticked form: `state` was advanced by launch A) and rng_step, if given, is advanced."""
+    rows = net.rows
+    if not net.trainable:
+        raise ValueError("mlp_cls_wgrad_update: the net has no dz / a buffers")
+    _chk(x, "x", (rows, net.in_dim))
+    _chk(dlogits, "dlogits", (rows, net.n_classes))
+    _chk(g, "g")
+    _chk(loss_rows, "loss_rows", (rows,))
+    _chk(loss, "loss", (1,))
+    n = net.n_hidden + 1
+    if len(w_off) != n or len(b_off) != n:
+        raise ValueError(f"mlp_cls_wgrad_update: {n} weight and bias offsets expected")
+    dims = [net.in_dim] + net.widths + [net.n_classes]
+    spans = []
+    for l in range(n):
+        spans += [(int(w_off[l]), int(w_off[l]) + dims[l + 1] * dims[l]), (int(b_off[l]), int(b_off[l]) + dims[l + 1])]
+    spans.sort()
+    if spans[0][0] < 0 or spans[-1][1] > g.numel() or any(a[1] > b[0] for a, b in zip(spans, spans[1:])):
+        raise ValueError("mlp_cls_wgrad_update: the offsets must name disjoint tensors inside the flat buffer")
+    if metrics is not None:
+        _chk(metrics, "metrics", (2,))
+        _chk(logits, "logits", (rows, net.n_classes))
+        _chk(y, "y", (rows,), torch.int64)
+    p = m = v = state = None
+    lr = b1 = b2 = eps = wd = 0.0
+    if adam is not None:
+        p, m, v, state = adam["p"], adam["m"], adam["v"], adam["state"]
+        for nm, t in (("p", p), ("m", m), ("v", v)):
+            _chk(t, nm, tuple(g.shape))
+        _chk(state, "state", (4,), torch.float64)
+        lr, (b1, b2), eps, wd = float(adam["lr"]), adam["betas"], float(adam.get("eps", 1e-8)), float(adam.get("weight_decay", 0.0))
+        if rng_step is not None:
+            _chk(rng_step, "rng_step", (1,), torch.int64)
+    elif rng_step is not None:
+        raise ValueError("mlp_cls_wgrad_update: rng_step advances with the update only")
+    arr = lambda o: (L.i64 * n)(*[int(t) for t in o])  # noqa: E731
+    L.check(L.load().mg_mlp_cls_wgrad_update(C.byref(net.c), rows, _p(x), _p(dlogits), arr(w_off), arr(b_off), g.numel(), _p(g), _p(p),
+                                             _p(m), _p(v), 1 if adam is not None else 0, lr, b1, b2, eps, wd, _p(state), _p(loss_rows),
+                                             _p(loss), _p(logits), _p(y), _p(metrics), _p(rng_step), _stream()),
+            "mg_mlp_cls_wgrad_update")
+
+
 def transpose_bcl_blc(x, y, gref=None, gact=ACT_NONE):
     """y[b, l, c] = x[b, c, l] (* act'(gref[b, l, c]) if gref is given: the activation backward behind the view)."""
     _chk(x, "x")
