@@ -594,6 +594,49 @@ int mg_gen_inputs(const int32_t* emotion, const int32_t* sample, int rows, float
 int mg_emotion_score(const float* logits, int rows, int n_classes, const int32_t* target, float* p_target, int32_t* pred,
                      double* acc, mg_stream_t stream);
 
+/* ---- held-out evaluation of a trained GAN (melo_gan_amd.gan.evaluate) ----
+ * The reference judges a generator with host scripts over files: src/gan/analyze_midi.py:28-45 (mean / min / max of pitch,
+ * mean velocity of written .mid files, per emotion), src/gan/diagnose.py:53-80 (per-column range, mean and standard deviation
+ * of a split) and the classifier's loss and accuracy of src/emotion_discriminator/train_ed.py:31-32 (argmax == label).
+ * mg_eval_acc adds ONE evaluated batch to a device-resident accumulator that lives for a whole pass over a split: no host
+ * round trip per batch.  Capturable.  Rows whose emot_idx lies outside [0, n_classes) are padding and count nowhere.
+ *   real, fake      (B, T, C) fp32, 16-byte aligned, C a multiple of 4 in 4..1024
+ *   emot_idx        (B) int64, the true class
+ *   d_real, d_fake  (B) critic scores, or both NULL (their sums stay untouched)
+ *   logits_fake, logits_real   (B, n_classes) classifier logits of the generated / the real rolls, or NULL (that side untouched)
+ * Accumulator: mg_eval_acc_words(K = n_classes, C) 8-byte words, in this order:
+ *   int64   n[K]                        rows of true class k
+ *   int64   conf_fake[K][K], conf_real[K][K]       [true class][predicted class]; prediction = first index of the maximum,
+ *                                       NaN counts as the maximum (mg_ed_metrics_acc's and mg_emotion_score's rule)
+ *   double  d_sum[2]                    sum d_real, sum d_fake
+ *   double  cls[2][2][K]                [fake, real][cross-entropy, softmax probability of the true class][true class]: sums of
+ *                                       lse(z) - z[y] with mg_softmax_ce's row-maximum-subtracted log-sum-exp, and of
+ *                                       exp(z[y] - max) / sum exp(z - max), both evaluated in fp64 from the fp32 logits
+ *   double  nsum[2][K][C], nsq[2][K][C] [real, fake][true class][channel]: sum of x and of x * x over rows and time, every
+ *                                       element widened to fp64 before it is added
+ *   float   nmin[2][K][C], nmax[2][K][C]   fminf / fmaxf over the same elements (NaN elements are skipped); +inf / -inf when empty
+ * mg_eval_acc_reset writes the empty accumulator (zeros, +inf, -inf).
+ * Launch shape: a workgroup of 256 lanes takes one row and one chunk of its time axis, 16 bytes per lane with the channel
+ * innermost (C = 4: one time position per lane; C = 128: 32 lanes per position), about 512 workgroups per call; it reduces
+ * its lanes by a fixed tree and writes its partials to its own entry of `work` (mg_eval_acc_workspace_bytes; every entry
+ * is written before the fold reads it).  A second launch of the same call folds the entries in a fixed order into the
+ * accumulator.  No floating-point atomics: two runs, and an eager run and a graph replay, leave identical bits.  The integer
+ * counts use integer atomics.  tick != NULL: tick[0] += 1 (the batch counter that mg_stage_rows_cursor and mg_eval_noise of
+ * the NEXT batch read, so a pass replays one graph and nothing else). */
+long mg_eval_acc_words(int n_classes, int C);
+size_t mg_eval_acc_workspace_bytes(int B, int T, int C);
+int mg_eval_acc_reset(void* acc, int n_classes, int C, mg_stream_t stream);
+int mg_eval_acc(const float* real, const float* fake, int B, int T, int C, const int64_t* emot_idx, const float* d_real,
+                const float* d_fake, const float* logits_fake, const float* logits_real, int n_classes, void* acc, void* work,
+                size_t work_bytes, uint64_t* tick, mg_stream_t stream);
+/* The noise of an evaluation batch: row r belongs to split row i = (counter[0] - base[0]) * rows + r and gets
+ *   noise[r, 0:noise_dim] ~ N(0,1)   Philox4x32-10 keyed by `seed`, counter = (element block, 0x4556414C, i lo, i hi)
+ * (Box-Muller, as mg_gen_inputs), zeros when i >= n (the padded tail of the last batch).  A split row's noise depends on
+ * (seed, i) alone -- not on the batch size or on what else is evaluated -- so two checkpoints evaluated under one seed are a
+ * paired comparison.  Counter word 1 keeps the stream apart from mg_rng_fill's, mg_stage_augment's and mg_gen_inputs'. */
+int mg_eval_noise(float* noise, int rows, int noise_dim, const uint64_t* counter, const uint64_t* base, long n, uint64_t seed,
+                  mg_stream_t stream);
+
 /* ---- fused flat Adam / AdamW (torch.optim.Adam defaults; src/gan/train_gan.py:136-145,
  *      src/ae/train_ae.py:79).  state: double[4] = {step, beta1^step, beta2^step, unused},
  *      advanced on device so the launch is hipGraph-replayable.  grad_scale multiplies g first

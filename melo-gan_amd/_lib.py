@@ -175,6 +175,11 @@ SIGNATURES = {
     "mg_rng_fill_tick2_stage": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp, vp, f32, f32, vp, i32, i32, vp, i64, vp, vp]),
     "mg_gen_inputs": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, f32, vp, i32, C.c_uint64, vp]),
     "mg_emotion_score": (i32, [vp, i32, i32, vp, vp, vp, vp, vp]),
+    "mg_eval_acc_words": (i64, [i32, i32]),
+    "mg_eval_acc_workspace_bytes": (sz, [i32, i32, i32]),
+    "mg_eval_acc_reset": (i32, [vp, i32, i32, vp]),
+    "mg_eval_acc": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp, vp]),
+    "mg_eval_noise": (i32, [vp, i32, i32, vp, vp, i64, C.c_uint64, vp]),
     "mg_adam_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp]),
     "mg_adam_flat_ticked": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp, vp]),
     "mg_adam_flat_wq": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, i32, vp, vp, i32, vp]),

@@ -1,0 +1,490 @@
+#!/usr/bin/env python3
+"""Held-out evaluation of a trained GAN on the validation split -- is the generator producing different music for different
+emotions on data it was not trained on?  The reference answers with host scripts over files (src/gan/analyze_midi.py:28-45:
+pitch / velocity / density of written .mid files "to check if the GAN is actually learning different emotions";
+src/gan/diagnose.py:53-80: ranges and variance of a split; src/emotion_discriminator/evaluate_ed.py, an accidental copy of
+ed_model.py):
+
+    python -m melo_gan_amd.gan.evaluate --config config/gan_config.yaml \
+        [--ckpt <CHECKPOINT_DIR>/gan_final.pth | gan_epochNNNN.pth] [--split <VAL_SPLIT>] [--feats <ENCODER_FEATS_VAL>] \
+        [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--seed <SEED>] [--batch 64] \
+        [--out <LOG_DIR>/eval.json] [--synthetic N]
+
+One pass over the split in row order.  Per batch ONE replayed hipGraph: stage the batch by a device-side cursor -> noise
+(mg_eval_noise: Philox keyed by (seed, split row), so the report does not depend on the batch size) -> E_num -> G (eval:
+dropout off, BatchNorm on running statistics) -> critic on [real | fake] -> classifier on the real and the generated rolls
+(latent mode: on the generator's internal latent, fake side only, as train_gan.py:232-237) -> mg_eval_acc, which adds the
+batch to a device-resident accumulator and advances the cursor.  The host reads the accumulator once, when the pass ends.
+A full checkpoint (gan_epochNNNN.pth) carries the critic; gan_final.pth does not and the critic metrics are then null.
+Every input from outside is checked on the host before any GPU use.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import config as C
+from . import generate as G
+from .generate import EMOTIONS, GenerateError
+from .utils import check_labels, emotion_to_index
+
+DEFAULT_BATCH = 64
+SIDES = ("real", "fake")            # order of the accumulator's note statistics
+RAW_KEYS = ("n", "conf_fake", "conf_real", "d_sum", "cls", "nsum", "nsq", "nmin", "nmax")
+
+
+class EvaluateError(GenerateError):
+    """A bad input of the evaluator, found on the host before any GPU use."""
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# host checks
+# ---------------------------------------------------------------------------------------------------------------------
+def check_ed_config(ed_cfg: dict, cfg: dict, path: str = "ED config"):
+    try:
+        G.check_ed_config(ed_cfg, cfg)
+    except GenerateError as e:
+        raise EvaluateError(f"{path}: {e}") from e
+
+
+def check_checkpoint(ck, cfg: dict, path: str = "checkpoint") -> bool:
+    """G and E_num as the sampler needs them; returns whether the checkpoint also holds a critic ('D') of the config's shapes."""
+    from .engine import discriminator_spec
+    try:
+        G.check_generator_checkpoint(ck, cfg, path)
+    except GenerateError as e:
+        raise EvaluateError(str(e)) from e
+    if "D" not in ck:
+        return False
+    spec = discriminator_spec(int(cfg["NOTE_DIM"]), 256, int(cfg.get("ENCODER_OUT_DIM", 128)))
+    for k, shape in spec.items():
+        if k not in ck["D"]:
+            raise EvaluateError(f"{path}: D lacks {k}")
+        if tuple(ck["D"][k].shape) != tuple(shape):
+            raise EvaluateError(f"{path}: D.{k} has shape {tuple(ck['D'][k].shape)}, the GAN config implies {tuple(shape)}")
+    return True
+
+
+def check_split_arrays(notes, emotions, numeric, latent, cfg: dict, where: str = "split"):
+    """The row-aligned arrays of a split against the config; returns the class indices."""
+    T, Cn, nd, ld = int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg.get("NUMERIC_INPUT_DIM", 6)), int(cfg["LATENT_DIM"])
+    if notes.ndim != 3 or tuple(notes.shape[1:]) != (T, Cn):
+        raise EvaluateError(f"{where}: notes has shape {tuple(notes.shape)}, the GAN config implies (n, {T}, {Cn})")
+    n = notes.shape[0]
+    if n < 1:
+        raise EvaluateError(f"{where}: notes holds no rows")
+    if numeric.ndim != 2 or tuple(numeric.shape) != (n, nd):
+        raise EvaluateError(f"{where}: numeric_features has shape {tuple(numeric.shape)}, expected ({n}, {nd})")
+    if len(emotions) != n:
+        raise EvaluateError(f"{where}: emotion holds {len(emotions)} entries, notes {n} rows")
+    if latent is not None and tuple(latent.shape) != (n, ld):
+        raise EvaluateError(f"{where}: encoder features have shape {tuple(latent.shape)}, expected ({n}, {ld})")
+    try:
+        return check_labels(torch.tensor([emotion_to_index(e) for e in emotions], dtype=torch.int64), len(EMOTIONS),
+                            f"{where}: emotion labels")
+    except ValueError as e:
+        raise EvaluateError(str(e)) from e
+
+
+def load_split_arrays(cfg: dict, split_csv: str, feats: Optional[str], feats_required: bool = False):
+    """<SPLITS_DIR>/<split stem>/{notes,emotion,numeric_features}.npy (+ the encoder features), checked against the config."""
+    d = os.path.join(cfg.get("SPLITS_DIR", "data/splits"), Path(split_csv).stem)
+    arrs = {}
+    for k in ("notes", "emotion", "numeric_features"):
+        p = os.path.join(d, k + ".npy")
+        if not os.path.isfile(p):
+            raise EvaluateError(f"split array {p} does not exist")
+        try:
+            arrs[k] = np.load(p, mmap_mode="r" if k == "notes" else None, allow_pickle=(k == "emotion"))
+        except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
+            raise EvaluateError(f"cannot read split array {p}: {e}") from e
+    latent = None
+    if feats and os.path.isfile(feats):
+        try:
+            latent = np.load(feats)
+        except Exception as e:      # noqa: BLE001
+            raise EvaluateError(f"cannot read encoder features {feats}: {e}") from e
+    elif feats and feats_required:
+        raise EvaluateError(f"encoder features {feats} do not exist")
+    elif feats:         # from the config, as the trainer: tolerated, but said -- the latents are then zeros
+        print(f"[WARN] encoder features {feats} not found: the split's latents are zeros (they feed a conditioning-mode "
+              "generator and a latent-mode classifier)")
+    check_split_arrays(arrs["notes"], arrs["emotion"], arrs["numeric_features"], latent, cfg, d)
+    return arrs["notes"], arrs["emotion"], arrs["numeric_features"], latent
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the report
+# ---------------------------------------------------------------------------------------------------------------------
+def raw_from_acc(acc_host: torch.Tensor, n_classes: int, n_channels: int) -> dict:
+    """The accumulator (host copy) as named numpy arrays (ops.eval_acc_layout)."""
+    from .. import ops
+    return {k: v.numpy().copy() for k, v in ops.eval_acc_views(acc_host, n_classes, n_channels).items()}
+
+
+def _ed_side(conf, ce, p, counts):
+    n = int(counts.sum())
+    conf = np.asarray(conf, dtype=np.int64)
+    per = {}
+    for k, name in enumerate(EMOTIONS):
+        nk = int(counts[k])
+        per[name] = ({"n": 0, "accuracy": None, "ce": None, "mean_p_target": None} if nk == 0 else
+                     {"n": nk, "accuracy": float(conf[k, k]) / nk, "ce": float(ce[k]) / nk, "mean_p_target": float(p[k]) / nk})
+    live = counts > 0
+    return {"ce": float(ce[live].sum()) / n if n else None, "accuracy": float(np.trace(conf)) / n if n else None,
+            "mean_p_target": float(p[live].sum()) / n if n else None, "confusion": conf.tolist(), "per_emotion": per}
+
+
+def build_report(raw: dict, T: int, seed: int, batch: int, has_critic: bool, has_ed_fake: bool, has_ed_real: bool) -> dict:
+    """The evaluation report from the raw accumulator (RAW_KEYS; ops.eval_acc_layout): plain Python values only."""
+    missing = [k for k in RAW_KEYS if k not in raw]
+    if missing:
+        raise ValueError(f"build_report: the raw accumulator lacks {missing}")
+    counts = np.asarray(raw["n"], dtype=np.int64)
+    K = len(EMOTIONS)
+    if counts.shape != (K,):
+        raise ValueError(f"build_report: n has shape {counts.shape}, expected ({K},)")
+    n = int(counts.sum())
+    critic = None
+    if has_critic and n:
+        mr, mf = float(raw["d_sum"][0]) / n, float(raw["d_sum"][1]) / n
+        critic = {"mean_real": mr, "mean_fake": mf, "w_dist": mr - mf}
+    cls = np.asarray(raw["cls"], dtype=np.float64)
+    notes = {}
+    for s, side in enumerate(SIDES):
+        notes[side] = {}
+        for k, name in enumerate(EMOTIONS):
+            nk = int(counts[k])
+            cnt = float(nk) * T
+            ch = []
+            for c in range(np.asarray(raw["nsum"]).shape[2]):
+                if nk == 0:
+                    ch.append({"mean": None, "std": None, "min": None, "max": None})
+                    continue
+                sm, sq = float(raw["nsum"][s][k][c]), float(raw["nsq"][s][k][c])
+                var = max((sq - sm * sm / cnt) / cnt, 0.0)       # population variance from the fp64 sums
+                ch.append({"mean": sm / cnt, "std": math.sqrt(var), "min": float(raw["nmin"][s][k][c]),
+                           "max": float(raw["nmax"][s][k][c])})
+            notes[side][name] = {"n_rows": nk, "channels": ch}
+    return {"n": n, "seed": int(seed), "batch": int(batch), "critic": critic,
+            "ed_fake": _ed_side(raw["conf_fake"], cls[0][0], cls[0][1], counts) if has_ed_fake else None,
+            "ed_real": _ed_side(raw["conf_real"], cls[1][0], cls[1][1], counts) if has_ed_real else None,
+            "notes": notes}
+
+
+def format_table(rep: dict) -> str:
+    f = lambda v, spec: "-" if v is None else format(v, spec)  # noqa: E731
+    lines = [f"rows {rep['n']}  seed {rep['seed']}  batch {rep['batch']}"]
+    c = rep["critic"]
+    lines.append("critic: " + ("-" if c is None else f"mean_real {c['mean_real']:.5f}  mean_fake {c['mean_fake']:.5f}  "
+                                                        f"w_dist {c['w_dist']:.5f}"))
+    for side in ("ed_fake", "ed_real"):
+        e = rep[side]
+        if e is None:
+            lines.append(f"{side}: -")
+            continue
+        lines.append(f"{side}: ce {f(e['ce'], '.4f')}  accuracy {f(e['accuracy'], '.3f')}  mean_p_target {f(e['mean_p_target'], '.4f')}")
+        lines.append(f"  {'emotion':<8} {'n':>6} {'accuracy':>9} {'ce':>9} {'p_target':>9}")
+        for name, s in e["per_emotion"].items():
+            lines.append(f"  {name:<8} {s['n']:>6} {f(s['accuracy'], '.3f'):>9} {f(s['ce'], '.4f'):>9} {f(s['mean_p_target'], '.4f'):>9}")
+    lines.append("notes, channel 0 (mean / std / min / max):")
+    for name in EMOTIONS:
+        cells = []
+        for side in SIDES:
+            ch = rep["notes"][side][name]["channels"][0]
+            cells.append(f"{side} " + " / ".join(f(ch[k], '.4f') for k in ("mean", "std", "min", "max")))
+        lines.append(f"  {name:<8} " + "   ".join(cells))
+    return "\n".join(lines)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the engine
+# ---------------------------------------------------------------------------------------------------------------------
+class Evaluator:
+    """One GanEngine of `batch` rows in eval mode: encoder dropout off, generator BatchNorm on running statistics, no
+    optimiser, no update of any buffer."""
+
+    def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH):
+        from .. import ops
+        from .engine import GanEngine
+        if int(batch) < 1:
+            raise EvaluateError(f"batch = {batch}: must be >= 1")
+        cfg = {"LR_G": 0.0, "LR_D": 0.0, **C.with_gan_defaults(cfg, require=False)}      # the rates are never used here
+        self.has_ed = ed_cfg is not None
+        if self.has_ed:
+            check_ed_config(ed_cfg, cfg)
+        else:       # the engine always holds a classifier: the smallest one (latent mode), never run
+            ed_cfg = dict(input_mode="latent", latent_dim=int(cfg["LATENT_DIM"]), mlp_hidden=[256, 128], n_classes=len(EMOTIONS))
+        self.cfg, self.B = cfg, int(batch)
+        self.eng = eng = GanEngine(cfg, ed_cfg, device, self.B)
+        eng.init_weights(int(cfg.get("SEED", 42)))          # defines every parameter
+        self.has_d = False                                  # load_critic / copy_from: the critic's weights mean something
+        self.ed_real = self.has_ed and eng.ed_mode == "notes"
+        d = eng.dev
+        self.K = len(EMOTIONS)
+        self.ctr = torch.zeros(1, dtype=torch.int64, device=d)       # batch cursor, advanced by mg_eval_acc
+        self.base = torch.zeros(1, dtype=torch.int64, device=d)
+        self.acc = ops.eval_acc_new(self.K, eng.C, d)
+        self.logits_real = torch.zeros(self.B, self.K, device=d)
+        self._graph, self._graph_key, self._hold = None, None, None
+
+    # ---- weights ----
+    def load_generator(self, ck):
+        """G (with its BatchNorm running statistics) and E_num from a checkpoint dict or path."""
+        from .train_gan import load_generator_state
+        ck, path = self._read(ck)
+        try:
+            G.check_generator_checkpoint(ck, self.cfg, path)
+        except GenerateError as e:
+            raise EvaluateError(str(e)) from e
+        load_generator_state(self.eng, ck)
+        self.eng.params_changed()
+
+    def load_critic(self, ck) -> bool:
+        """The critic from a full gan_epochNNNN.pth (key 'D').  gan_final.pth holds none: returns False and the critic metrics
+        of the report are null."""
+        ck, path = self._read(ck)
+        if not check_checkpoint(ck, self.cfg, path):
+            self.has_d = False
+            return False
+        self.eng.D.load(ck["D"])
+        self.eng.params_changed()
+        self.has_d = True
+        return True
+
+    def load_ed(self, path: str):
+        """The frozen classifier (train_ed's ed_best.pth or a bare state_dict; spectral-norm keys folded)."""
+        from .train_gan import load_ed_checkpoint
+        if not self.has_ed:
+            raise EvaluateError("this Evaluator was built without an ED config")
+        if not os.path.isfile(path):
+            raise EvaluateError(f"ED checkpoint {path} does not exist")
+        load_ed_checkpoint(self.eng, path)
+
+    def copy_from(self, src):
+        """The current weights of a training engine (same configs), device to device: generator + encoder, critic, frozen
+        classifier and the BatchNorm buffers.  Reads `src` only; the copies are ordered behind the caller's current stream."""
+        e = self.eng
+        for a, b in ((e.GE, src.GE), (e.D, src.D), (e.ED, src.ED)):
+            if a.data.shape != b.data.shape or list(a.spec.items()) != list(b.spec.items()):
+                raise EvaluateError("copy_from: the engines were built from different configs")
+        e.stream.wait_stream(torch.cuda.current_stream(e.dev))
+        with torch.cuda.stream(e.stream):
+            for a, b in ((e.GE, src.GE), (e.D, src.D), (e.ED, src.ED)):
+                a.data.copy_(b.data)
+            for k in e.Gbuf:
+                e.Gbuf[k].copy_(src.Gbuf[k])
+            for k in e.EDbuf:
+                e.EDbuf[k].copy_(src.EDbuf[k])
+            e.params_changed()
+        self.has_d = True
+
+    @staticmethod
+    def _read(ck):
+        if isinstance(ck, (str, os.PathLike)):
+            path = str(ck)
+            try:
+                return G.load_checkpoint(path), path
+            except GenerateError as e:
+                raise EvaluateError(str(e)) from e
+        return ck, "checkpoint"
+
+    # ---- the pass ----
+    def _launches(self, jobs, order, order_len, n, seed, draw, metrics=True):
+        """One batch.  metrics=False leaves the accumulation out (tools/eval_bench.py times the batch with and without it)."""
+        from .. import ops
+        eng, B = self.eng, self.B
+        ops.stage_rows_cursor(jobs, B, order, order_len, self.ctr, self.base)
+        if draw:
+            ops.eval_noise(eng.noise, self.ctr, self.base, n, seed)
+        eng._e_fwd(False, "g", gin=True)
+        eng._g_fwd(eng.fake_d, False, "g")                  # rows [2B, 3B) of X0: [real | fake] is one 2B-row critic batch
+        if self.has_d:
+            eng._d_fwd(eng.X0[B:3 * B], 2 * B, eng.emb)
+        lf = lr = None
+        if self.has_ed:
+            if self.ed_real:
+                eng._ed_fwd(eng.real)
+                ops.axpby(eng.logits, self.logits_real, 1.0, 0.0)
+                lr = self.logits_real
+            eng._ed_fwd(eng.fake_d)                         # latent mode: reads the generator's internal latent instead
+            lf = eng.logits
+        if not metrics:
+            return
+        ops.eval_acc(eng.real, eng.fake_d, eng.emot_idx, eng.s[:B] if self.has_d else None,
+                     eng.s[B:2 * B] if self.has_d else None, lf, lr, self.acc, tick=self.ctr, n_classes=self.K)
+
+    def evaluate(self, dataset, seed: int, noise: Optional[torch.Tensor] = None) -> dict:
+        """One pass over a resident GANDataset in row order; returns the report.  noise: an (n, NOISE_DIM) resident fp32
+        array staged instead of drawn (tests, externally paired runs)."""
+        from .. import ops
+        eng, B = self.eng, self.B
+        if not getattr(dataset, "resident", False):
+            raise EvaluateError("evaluate: the split must be resident on the device (GANDataset(resident=True))")
+        n = len(dataset)
+        if n < 1 or tuple(dataset.notes.shape[1:]) != (eng.T, eng.C):
+            raise EvaluateError(f"evaluate: the split's notes have shape {tuple(dataset.notes.shape)}, the engine reads "
+                                f"(n, {eng.T}, {eng.C})")
+        if tuple(dataset.numeric.shape) != (n, eng.num_in) or tuple(dataset.latent.shape) != (n, eng.latent_dim):
+            raise EvaluateError("evaluate: the split's numeric features / latents do not match the config")
+        if noise is not None and (not isinstance(noise, torch.Tensor) or not noise.is_cuda or noise.dtype != torch.float32 or
+                                  not noise.is_contiguous() or tuple(noise.shape) != (n, eng.noise_dim)):
+            raise EvaluateError(f"evaluate: noise must be a contiguous fp32 device array of shape ({n}, {eng.noise_dim})")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        nb = (n + B - 1) // B
+        key = (dataset.notes.data_ptr(), dataset.emot_idx.data_ptr(), n, seed, None if noise is None else noise.data_ptr(),
+               self.has_d)
+        with torch.cuda.stream(eng.stream):
+            if self._graph_key != key:
+                # the labels padded to whole batches with -1: the staging clamps the other arrays' padding rows into the split
+                labels = torch.full((nb * B,), -1, dtype=torch.int64, device=eng.dev)
+                labels[:n] = dataset.emot_idx
+                order = torch.arange(nb * B, dtype=torch.int64, device=eng.dev)
+                jobs = [(dataset.notes, eng.real), (dataset.numeric, eng.numeric), (labels, eng.emot_idx)]
+                if eng.latent_dim > 0:
+                    jobs.append((dataset.latent, eng.latent))
+                if noise is not None:
+                    jobs.append((noise, eng.noise))
+                args = (jobs, order, nb * B, n, seed, noise is None)
+                self._launches(*args)          # one eager run allocates every workspace this set of launches needs
+                torch.cuda.synchronize()
+                g = ops.Graph()
+                g.begin()
+                try:
+                    self._launches(*args)
+                finally:
+                    g.end()
+                self._graph, self._graph_key, self._hold = g, key, (dataset, labels, order, noise)
+            ops.eval_acc_reset(self.acc, self.K, eng.C)
+            self.ctr.zero_()
+            for _ in range(nb):
+                self._graph.launch()
+            acc = self.acc.cpu()                # the pass's only device -> host read
+        raw = raw_from_acc(acc, self.K, eng.C)
+        return build_report(raw, eng.T, seed, B, self.has_d, self.has_ed, self.ed_real)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CLI
+# ---------------------------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m melo_gan_amd.gan.evaluate",
+                                 description="Held-out evaluation of a trained GAN on the validation split.")
+    ap.add_argument("--config", type=str, default="config/gan_config.yaml", help="Path to the main GAN config")
+    ap.add_argument("--ckpt", type=str, default=None, help="gan_final.pth (default, under CHECKPOINT_DIR) or a full gan_epochNNNN.pth")
+    ap.add_argument("--split", type=str, default=None, help="split to evaluate (default VAL_SPLIT)")
+    ap.add_argument("--feats", type=str, default=None, help="encoder features of the split (default ENCODER_FEATS_VAL)")
+    ap.add_argument("--ed_config", type=str, default=None, help="ED config of the classifier")
+    ap.add_argument("--ed_ckpt", type=str, default=None, help="ED checkpoint (ed_best.pth)")
+    ap.add_argument("--seed", type=int, default=None, help="noise seed (default SEED)")
+    ap.add_argument("--batch", type=int, default=DEFAULT_BATCH, help="rows per replayed batch")
+    ap.add_argument("--out", type=str, default=None, help="report file (default <LOG_DIR>/eval.json)")
+    ap.add_argument("--synthetic", type=int, default=0, help="evaluate on N synthetic rolls (drawn with SEED + 1) instead of a split")
+    return ap.parse_args(argv)
+
+
+@dataclass
+class Plan:
+    cfg: dict
+    ed_cfg: Optional[dict]
+    ckpt_path: str
+    ckpt: dict
+    has_critic: bool
+    ed_ckpt: Optional[str]
+    arrays: Optional[tuple]
+    synthetic: int
+    seed: int
+    batch: int
+    out: str
+
+
+def _read_config(path: str, what: str) -> dict:
+    try:
+        return G._read_config(path, what)
+    except GenerateError as e:
+        raise EvaluateError(str(e)) from e
+
+
+def plan(args) -> Plan:
+    """Every check of what comes from outside, on the host (no GPU needed); raises EvaluateError."""
+    if args.batch < 1:
+        raise EvaluateError(f"--batch {args.batch}: must be >= 1")
+    if args.synthetic < 0:
+        raise EvaluateError(f"--synthetic {args.synthetic}: must be >= 0")
+    cfg = C.with_gan_defaults(_read_config(args.config, "config"), require=False)
+    missing = [k for k in ("NOISE_DIM", "LATENT_DIM", "MAX_NOTES", "NOTE_DIM") if k not in cfg]
+    if missing:
+        raise EvaluateError(f"config {args.config} lacks {', '.join(missing)}")
+    if int(cfg["NOTE_DIM"]) % 4 or not 4 <= int(cfg["NOTE_DIM"]) <= 1024:
+        raise EvaluateError(f"config {args.config}: NOTE_DIM = {cfg['NOTE_DIM']}: the metrics kernel reads 4 channels per lane "
+                            "(a multiple of 4 in 4..1024)")
+    if args.ed_ckpt is not None and args.ed_config is None:
+        raise EvaluateError("--ed_ckpt needs --ed_config (the classifier's architecture)")
+    if args.ed_config is not None and args.ed_ckpt is None:
+        raise EvaluateError("--ed_config needs --ed_ckpt (an untrained classifier's verdict means nothing)")
+    ckpt_path = args.ckpt or os.path.join(cfg.get("CHECKPOINT_DIR", "experiments/gan/checkpoints"), "gan_final.pth")
+    try:
+        ckpt = G.load_checkpoint(ckpt_path)
+    except GenerateError as e:
+        raise EvaluateError(str(e)) from e
+    has_critic = check_checkpoint(ckpt, cfg, ckpt_path)
+    ed_cfg = None
+    if args.ed_config is not None:
+        ed_cfg = _read_config(args.ed_config, "ED config")
+        check_ed_config(ed_cfg, cfg, f"ED config {args.ed_config}")
+        if not os.path.isfile(args.ed_ckpt):
+            raise EvaluateError(f"ED checkpoint {args.ed_ckpt} does not exist")
+    arrays = None
+    if not args.synthetic:
+        split = args.split or cfg.get("VAL_SPLIT")
+        if not split:
+            raise EvaluateError(f"config {args.config} lacks VAL_SPLIT and no --split was given")
+        arrays = load_split_arrays(cfg, split, args.feats or cfg.get("ENCODER_FEATS_VAL"), feats_required=args.feats is not None)
+    out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/gan/logs"), "eval.json")
+    seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
+    return Plan(cfg, ed_cfg, ckpt_path, ckpt, has_critic, args.ed_ckpt, arrays, int(args.synthetic), seed, args.batch, out)
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    try:
+        p = plan(args)
+    except GenerateError as e:
+        print(f"evaluate: error: {e}", file=sys.stderr)
+        return 2
+    if not torch.cuda.is_available():
+        raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+    from .dataset import GANDataset
+    cfg = p.cfg
+    if p.synthetic:
+        ds = GANDataset.synthetic(p.synthetic, int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg["LATENT_DIM"]),
+                                  int(cfg.get("SEED", 42)) + 1, "cuda")
+    else:
+        ds = GANDataset(*p.arrays, int(cfg["LATENT_DIM"]), "cuda", resident=True)
+    ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch)
+    ev.load_generator(p.ckpt)
+    if p.has_critic:
+        ev.load_critic(p.ckpt)
+    if p.ed_cfg is not None:
+        ev.load_ed(p.ed_ckpt)
+    rep = ev.evaluate(ds, p.seed)
+    rep["checkpoint"], rep["ed_checkpoint"] = p.ckpt_path, p.ed_ckpt
+    os.makedirs(os.path.dirname(os.path.abspath(p.out)), exist_ok=True)
+    with open(p.out, "w") as f:
+        json.dump(rep, f, indent=1)
+    print(format_table(rep))
+    print(f"wrote {p.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -10,7 +10,9 @@ Differences that do not change results: the epoch's batches come from an HBM-res
 (no DataLoader workers), every D-step / G-step is a replayed hipGraph over libmelogan_hip, and the three
 per-epoch scalars are accumulated on the device and read back once per epoch (the reference calls .item()
 three times per batch, train_gan.py:205,250-251).  Extra flags (--synthetic, --epochs, --no-graph) exist
-for smoke runs without the (git-ignored) dataset.
+for smoke runs without the (git-ignored) dataset.  --eval-every N (not in the reference, which never looks at held-out data
+while it trains) evaluates the current weights on VAL_SPLIT every N epochs (gan/evaluate.py) and logs Val/W_dist,
+Val/ED_Acc_Fake, Val/ED_CE_Fake and Val/ED_Acc_Real; it changes nothing the training step reads.
 
 Data parallel (not in the reference, which is single-GPU): launched under torch.distributed.run
 (`--nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`) every rank holds a replica, takes every N-th batch of the
@@ -182,7 +184,11 @@ def resume_checkpoint(eng: GanEngine, path: str) -> int:
     return int(ck.get("epoch") or 0)
 
 
-def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: bool = True, resume: str = None):
+def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: bool = True, resume: str = None,
+          eval_every: int = 0):
+    """eval_every = N > 0: after every N-th epoch rank 0 evaluates the current weights on VAL_SPLIT (with `synthetic`: on a
+    second synthetic split drawn with SEED + 1) in an Evaluator of its own (gan/evaluate.py) and writes the Val/* scalars.
+    The pass reads the training engine's weights and nothing else: a run with it ends in the same checkpoints, bit for bit."""
     cfg = C.with_gan_defaults(cfg, require=not synthetic)
     seed_everything(cfg.get("SEED", 42))
     if not torch.cuda.is_available():
@@ -224,6 +230,16 @@ def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: 
     critic_iters = cfg.get("CRITIC_ITERS", 5)
     sums = torch.zeros(3, device=device)        # sum loss_d, sum g_adv, sum g_emo (device-side accumulation)
     shuffle_gen = torch.Generator().manual_seed(cfg.get("SEED", 42))
+    evaluator = val_ds = None
+    if eval_every > 0 and rank == 0:
+        from .evaluate import Evaluator
+        if synthetic:
+            val_ds = GANDataset.synthetic(synthetic, cfg["MAX_NOTES"], cfg["NOTE_DIM"], cfg["LATENT_DIM"], cfg.get("SEED", 42) + 1,
+                                          device)
+        else:
+            val_ds = GANDataset.from_split(cfg, cfg["VAL_SPLIT"], cfg.get("ENCODER_FEATS_VAL"), device, resident=True)
+        log(f"Validation set size: {len(val_ds)} (evaluated every {eval_every} epoch(s))")
+        evaluator = Evaluator(cfg, ed_cfg, device, B)
     log("Starting WGAN-GP Training with Emotion Guidance...")
 
     def epoch_batches():
@@ -268,6 +284,17 @@ def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: 
             writer.add_scalar("Loss/Critic", s[0] / steps, epoch)
             writer.add_scalar("Loss/Generator_Adv", s[1] / g_steps, epoch)
             writer.add_scalar("Loss/Generator_Emo", s[2] / g_steps, epoch)
+            if evaluator is not None and epoch % eval_every == 0:
+                evaluator.copy_from(eng)        # device-to-device, behind this stream's work; the engine is only read
+                rep = evaluator.evaluate(val_ds, cfg.get("SEED", 42))
+                val = {"Val/W_dist": rep["critic"]["w_dist"], "Val/ED_Acc_Fake": rep["ed_fake"]["accuracy"],
+                       "Val/ED_CE_Fake": rep["ed_fake"]["ce"],
+                       "Val/ED_Acc_Real": rep["ed_real"]["accuracy"] if rep["ed_real"] else None}
+                for tag, v in val.items():
+                    if v is not None:
+                        writer.add_scalar(tag, v, epoch)
+                log(f"Epoch {epoch}/{cfg['EPOCHS']} | validation ({rep['n']} rows) | " +
+                    " | ".join(f"{t[4:]}: {v:.4f}" for t, v in val.items() if v is not None))
             if epoch % cfg.get("SAVE_FREQ", 5) == 0:
                 save_checkpoint(eng, os.path.join(cfg["CHECKPOINT_DIR"], f"gan_epoch{epoch:04d}.pth"), epoch, full=True)
     if rank == 0:
@@ -289,12 +316,14 @@ def main(argv=None):
     parser.add_argument("--epochs", type=int, default=None, help="override EPOCHS")
     parser.add_argument("--no-graph", action="store_true")
     parser.add_argument("--resume", type=str, default=None, help="gan_epochNNNN.pth to continue from (G, D, E_num, opt_G, opt_D)")
+    parser.add_argument("--eval-every", type=int, default=0,
+                        help="evaluate on VAL_SPLIT every N epochs (gan/evaluate.py; 0 = off)")
     args = parser.parse_args(argv)
     cfg = C.load_config(args.config)
     ed_cfg = C.load_config(args.ed_config)
     if args.epochs is not None:
         cfg["EPOCHS"] = args.epochs
-    train(cfg, ed_cfg, args.ed_ckpt, args.synthetic, not args.no_graph, args.resume)
+    train(cfg, ed_cfg, args.ed_ckpt, args.synthetic, not args.no_graph, args.resume, args.eval_every)
 
 
 if __name__ == "__main__":

@@ -8,6 +8,7 @@ state_dict layouts.  Nothing here falls back to PyTorch math.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -1692,6 +1693,117 @@ def emotion_score(logits, target, p_target, pred, acc):
     _chk(acc, "acc", (nc, 3), torch.float64)
     L.check(L.load().mg_emotion_score(_p(logits), rows, nc, _p(target), _p(p_target), _p(pred), _p(acc), _stream()),
             "mg_emotion_score")
+
+
+def eval_acc_layout(n_classes: int, C: int) -> dict:
+    """The accumulator of eval_acc (include/melo_gan_hip.h, mg_eval_acc): name -> (offset in 8-byte words, shape), plus
+    'words'.  The int64 and fp64 sections count in words; 'nmin' / 'nmax' are fp32, two to a word."""
+    K = int(n_classes)
+    if not (1 <= K <= 32 and 4 <= C <= 1024 and C % 4 == 0):
+        raise ValueError("eval_acc: 1..32 classes and C a multiple of 4 in 4..1024")
+    lay, off = {}, 0
+    for name, shape in (("n", (K,)), ("conf_fake", (K, K)), ("conf_real", (K, K)), ("d_sum", (2,)), ("cls", (2, 2, K)),
+                        ("nsum", (2, K, C)), ("nsq", (2, K, C))):
+        lay[name] = (off, shape)
+        n = 1
+        for s in shape:
+            n *= s
+        off += n
+    lay["nmin"], lay["nmax"] = (off, (2, K, C)), (off + K * C, (2, K, C))
+    lay["words"] = off + 2 * K * C
+    if lay["words"] != L.load().mg_eval_acc_words(K, C):
+        raise RuntimeError("eval_acc_layout disagrees with mg_eval_acc_words")
+    return lay
+
+
+def eval_acc_views(acc: Tensor, n_classes: int, C: int) -> dict:
+    """Typed views of an accumulator (device or host int64 tensor of eval_acc_layout(...)['words'] words), by name."""
+    lay = eval_acc_layout(n_classes, C)
+    if acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] or not acc.is_contiguous():
+        raise ValueError(f"eval_acc: the accumulator is a contiguous int64 vector of {lay['words']} words")
+    out = {}
+    for name in ("n", "conf_fake", "conf_real"):
+        off, shape = lay[name]
+        out[name] = acc[off:off + math.prod(shape)].view(shape)
+    for name in ("d_sum", "cls", "nsum", "nsq"):
+        off, shape = lay[name]
+        out[name] = acc[off:off + math.prod(shape)].view(torch.float64).view(shape)
+    for name in ("nmin", "nmax"):
+        off, shape = lay[name]
+        out[name] = acc[off:off + math.prod(shape) // 2].view(torch.float32).view(shape)
+    return out
+
+
+def eval_acc_new(n_classes: int, C: int, device) -> Tensor:
+    """A fresh (reset) accumulator for eval_acc."""
+    acc = torch.zeros(eval_acc_layout(n_classes, C)["words"], dtype=torch.int64, device=device)
+    return eval_acc_reset(acc, n_classes, C)
+
+
+def eval_acc_reset(acc: Tensor, n_classes: int, C: int) -> Tensor:
+    _chk(acc, "acc", (eval_acc_layout(n_classes, C)["words"],), torch.int64)
+    L.check(L.load().mg_eval_acc_reset(_p(acc), int(n_classes), int(C), _stream()), "mg_eval_acc_reset")
+    return acc
+
+
+def eval_acc(real, fake, emot_idx, d_real, d_fake, logits_fake, logits_real, acc, tick=None, n_classes=None):
+    """One evaluated batch added to the pass's accumulator (mg_eval_acc): real / fake (B, T, C), emot_idx (B,) int64 (-1 = a
+    padding row), critic scores d_real / d_fake (B,) or both None, classifier logits of the fake / real side (B, K) or None.
+    n_classes: the class count K; may be left out when logits are given (their width).  tick: an int64 (1,) batch counter to
+    advance."""
+    _chk(real, "real")
+    if real.dim() != 3:
+        raise ValueError("eval_acc: real (B, T, C) expected")
+    B, T, C = real.shape
+    _chk(fake, "fake", (B, T, C))
+    _chk(emot_idx, "emot_idx", (B,), torch.int64)
+    if (d_real is None) != (d_fake is None):
+        raise ValueError("eval_acc: d_real and d_fake go together")
+    if d_real is not None:
+        _chk(d_real, "d_real", (B,))
+        _chk(d_fake, "d_fake", (B,))
+    K = None if n_classes is None else int(n_classes)
+    for name, lg in (("logits_fake", logits_fake), ("logits_real", logits_real)):
+        if lg is None:
+            continue
+        _chk(lg, name)
+        if lg.dim() != 2 or lg.shape[0] != B or (K is not None and lg.shape[1] != K):
+            raise ValueError(f"eval_acc: {name} (B, K) expected, K = n_classes on both sides")
+        K = lg.shape[1]
+    if not (C % 4 == 0 and 4 <= C <= 1024):
+        raise ValueError("eval_acc: C must be a multiple of 4 in 4..1024")
+    if not 1 <= B <= 65534:
+        raise ValueError("eval_acc: B must be in 1..65534")
+    if real.data_ptr() % 16 or fake.data_ptr() % 16:
+        raise ValueError("eval_acc: real and fake must be 16-byte aligned")
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1:
+        raise ValueError("eval_acc: acc is an int64 vector (eval_acc_new)")
+    if K is None:
+        raise ValueError("eval_acc: without logits, n_classes must be given")
+    _chk(acc, "acc", (eval_acc_layout(K, C)["words"],), torch.int64)
+    if tick is not None:
+        _chk(tick, "tick", (1,), torch.int64)
+    lib = L.load()
+    nbytes = lib.mg_eval_acc_workspace_bytes(B, T, C)
+    work = workspace(nbytes, real.device, "eval_acc")
+    L.check(lib.mg_eval_acc(_p(real), _p(fake), B, T, C, _p(emot_idx), _p(d_real), _p(d_fake), _p(logits_fake), _p(logits_real), K,
+                            _p(acc), _p(work), work.numel(), _p(tick), _stream()), "mg_eval_acc")
+    return acc
+
+
+def eval_noise(noise, counter, base, n: int, seed: int):
+    """The noise of evaluation batch (counter - base) (mg_eval_noise): row r ~ N(0,1) keyed by (seed, split row (counter - base) *
+    rows + r); zeros for split rows >= n.  counter / base: int64 device scalars (1,)."""
+    _chk(noise, "noise")
+    if noise.dim() != 2 or not 0 < noise.shape[0] <= 65535:
+        raise ValueError("eval_noise: noise (rows, noise_dim) with 1..65535 rows expected")
+    _chk(counter, "counter", (1,), torch.int64)
+    _chk(base, "base", (1,), torch.int64)
+    if int(n) < 1:
+        raise ValueError("eval_noise: the split length must be positive")
+    L.check(L.load().mg_eval_noise(_p(noise), noise.shape[0], noise.shape[1], _p(counter), _p(base), int(n),
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "mg_eval_noise")
+    return noise
 
 
 def wq_table(entries):
