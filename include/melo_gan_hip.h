@@ -105,35 +105,31 @@ int mg_conv1d_scatter2(const float* x, const float* w, float* y,
  * Tout = 2*Tin or 2*Tin-1] in 64x32 / 32x32 output tiles with the whole channel reduction inside each workgroup: no
  * split-K workspace, no second launch, bitwise run-to-run reproducible.  Weights in the WQ layout
  *     wq[((c/4)*5 + k)*N + n][c%4] = W(n, c, k)        (N output columns, c reduction channel, Cin % 16 == 0, N % 32 == 0)
- * which mg_wq_relayout derives from a reference-layout tensor (W(n,c,k) = w[n*w_sn + c*w_sc + k]) and mg_adam_flat_wq
+ * which mg_wq_relayout derives from a reference-layout tensor (W(n,c,k) = w[n*w_sn + c*w_sc + k]) and mg_adam_flat's table
  * keeps current after every optimiser step.  mg_conv16_supported tells whether a shape is covered (else use the calls above). */
 int mg_wq_relayout(const float* w, float* wq, int N, int Cc, int K, int w_sn, int w_sc, mg_stream_t stream);
 int mg_conv16_supported(int B, int Tin, int Cin, int N, int transposed, int Tout);
-int mg_conv16(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-              long xbs, long ybs, const mg_epilogue* epi, mg_stream_t stream);
-/* The same launch that ALSO leaves per-column partial statistics of the values v it stores, so that the train-mode
- * BatchNorm that follows needs no reduction pass of its own: for every (tile, wave row) p and column n
- *   part[p][0][n] = sum_rows v[row, n],   [1][n] = sum_rows (v - mean_p)^2 about that wave's OWN mean,   [2][n] = rows summed
- * (combined by the parallel-variance rule in fp64: nothing is formed as E[x^2] - mean^2).
- * part: 3 * part_rows * N floats; part_rows and the batch rows a tile spans from mg_conv16_plan (a caller that stacks
- * several BatchNorm groups along the batch needs the group size to be a multiple of batch_rows_per_tile).
- * mg_bn_train_fwd_parts finishes the statistics (fixed order, fp64), moves the running ones and applies, all in ONE launch:
- * the semantics of mg_bn_train_fwd_groups (nn.BatchNorm1d training forward, src/gan/models.py:57-61). */
 int mg_conv16_plan(int B, int Tin, int N, int transposed, int* batch_rows_per_tile, int* part_rows, int* tile_rows);
-int mg_conv16_stats(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-                    long xbs, long ybs, const mg_epilogue* epi, float* part, mg_stream_t stream);
-/* The same launch also writing the temporal mean of what it stores -- AdaptiveAvgPool1d(1) behind the critic's last
- * convolution (src/gan/models.py:148): pool[b][n] = pool_scale * sum_t y[b][t][n].  Gather form only; mg_conv16_poolable says
- * whether a shape qualifies (every sample's time axis is one wave's rows of a tile: Tout = 32, or 16 with 32-row tiles). */
 int mg_conv16_poolable(int B, int Tin, int Cin, int N);
-int mg_conv16_pool(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, long xbs, long ybs,
-                   const mg_epilogue* epi, float* pool, float pool_scale, mg_stream_t stream);
-/* One launch with any of the riders: statistics (part), temporal mean (pool), the permuted output order
- *   y_perm: y[b*ybs + n*Tout + tout] -- the (B, N*Tout) order behind the reference's `view(B, 256, L)` (src/gan/models.py:70),
- *           so the data-gradient of the first deconvolution lands in decoder.pre.2's output order with no transpose launch
- *           (zout / gref / emul keep the dense (b, tout, n) index);
- * and the gradient penalty's interpolate (src/gan/utils.py:76-79): for batch rows b < mix_rows ALSO
- *   mix_out[i] = mix_alpha[b] * mix_real[i] + (1 - mix_alpha[b]) * y[i]   at the element's y index i. */
+/* ONE launch, with any of these riders (extra = NULL, or a zeroed field: none):
+ *   part:   per-column partial statistics of the values v the launch stores, so that the train-mode BatchNorm that follows
+ *           needs no reduction pass of its own: for every (tile, wave row) p and column n
+ *             part[p][0][n] = sum_rows v[row, n],   [1][n] = sum_rows (v - mean_p)^2 about that wave's OWN mean,   [2][n] = rows summed
+ *           (combined by the parallel-variance rule in fp64: nothing is formed as E[x^2] - mean^2).
+ *           part: 3 * part_rows * N floats; part_rows and the batch rows a tile spans from mg_conv16_plan (a caller that stacks
+ *           several BatchNorm groups along the batch needs the group size to be a multiple of batch_rows_per_tile).
+ *           mg_bn_train_fwd_parts finishes the statistics (fixed order, fp64), moves the running ones and applies, all in ONE
+ *           launch: the semantics of mg_bn_train_fwd (nn.BatchNorm1d training forward, src/gan/models.py:57-61).  The
+ *           statistics of an accumulating launch (epi->accumulate) are not defined: refused.
+ *   pool:   the temporal mean of what the launch stores -- AdaptiveAvgPool1d(1) behind the critic's last convolution
+ *           (src/gan/models.py:148): pool[b][n] = pool_scale * sum_t y[b][t][n].  Gather form only; mg_conv16_poolable says
+ *           whether a shape qualifies (every sample's time axis is one wave's rows of a tile: Tout = 32, or 16 with 32-row
+ *           tiles).  The mean of an accumulating launch is not defined: refused.
+ *   y_perm: the permuted output order y[b*ybs + n*Tout + tout] -- the (B, N*Tout) order behind the reference's
+ *           `view(B, 256, L)` (src/gan/models.py:70), so the data-gradient of the first deconvolution lands in decoder.pre.2's
+ *           output order with no transpose launch (zout / gref / emul keep the dense (b, tout, n) index);
+ *   mix_*:  the gradient penalty's interpolate (src/gan/utils.py:76-79): for batch rows b < mix_rows ALSO
+ *             mix_out[i] = mix_alpha[b] * mix_real[i] + (1 - mix_alpha[b]) * y[i]   at the element's y index i. */
 typedef struct mg_conv16_extra {
     float* part;
     float* pool;
@@ -155,8 +151,8 @@ typedef struct mg_conv16_extra {
     double* bnb_part;
     int bnb_act;
 } mg_conv16_extra;
-int mg_conv16_ex(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-                 long xbs, long ybs, const mg_epilogue* epi, const mg_conv16_extra* extra, mg_stream_t stream);
+int mg_conv16(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
+              long xbs, long ybs, const mg_epilogue* epi, const mg_conv16_extra* extra /* may be NULL */, mg_stream_t stream);
 /* mg_bn_train_bwd behind a conv16 launch that left the two column sums (bnb_part, part_rows rows of 2 x C doubles): the sums
  * are added in row order and the gradient applied -- one launch. */
 int mg_bn_train_bwd_parts(const double* part, int part_rows, const float* da, const float* a, const float* z, float* dz, long R,
@@ -218,15 +214,13 @@ int mg_stamp(unsigned long long* dst, mg_stream_t stream);
  *       w (out,in): w_sn = in, w_sc = 1;   data-gradient dx = dy @ w: w_sn = 1, w_sc = in(=N).
  *   Deep K is split over workgroups into partial slabs in `work` (mg_linear_workspace_bytes, may be 0). */
 size_t mg_linear_workspace_bytes(int M, int N, int K);
-int mg_linear(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, int w_sc,
-              const mg_epilogue* epi, void* work, size_t work_bytes, mg_stream_t stream);
-/* The same with the OUTPUT COLUMNS PERMUTED: column n' of y is weight row (n' % C) * perm_L + n' / C, C = N / perm_L (bias,
+/* perm_L > 1: the OUTPUT COLUMNS PERMUTED: column n' of y is weight row (n' % C) * perm_L + n' / C, C = N / perm_L (bias,
  * scale, gscale follow the weight row; zout / gref / emul the stored order): y comes out as the channels-last (M, perm_L, C)
  * tensor the reference reaches by `view(B, 256, L)` + permute(0, 2, 1) on the way into the first ConvTranspose1d
- * (src/gan/models.py:70-73) -- no transpose launch.  perm_L = 0: mg_linear. */
-int mg_linear_perm(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, int w_sc,
-                   const mg_epilogue* epi, int perm_L, void* work, size_t work_bytes, mg_stream_t stream);
-/* Host only: what mg_linear_perm launches for these arguments (the same decision function).  Returns 0: the 64x64-tile window
+ * (src/gan/models.py:70-73) -- no transpose launch.  perm_L = 0: the reference's column order. */
+int mg_linear(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, int w_sc,
+              const mg_epilogue* epi, int perm_L, void* work, size_t work_bytes, mg_stream_t stream);
+/* Host only: what mg_linear launches for these arguments (the same decision function).  Returns 0: the 64x64-tile window
  * GEMM conv_wgemm_kernel<1,1,false,true,TM,TN> (the permuted forward with many rows and columns; MG_LINEAR_SKINNY_ONLY=1
  * disables that route), 1: linear_skinny_kernel<*kcontig, *vec>, followed by linear_finish_kernel when *ksplit > 1;
  * negative: an argument error.  x_aligned / w_aligned: whether the pointer is 16-byte aligned. */
@@ -355,24 +349,19 @@ int mg_colsum(const float* x, long R, int C, float* sum, float* sumsq,
 /* ---- BatchNorm1d, training mode, fused with ReLU (src/gan/models.py:57-61, src/ae/model.py:12-21) ----
  * z: (R, C) pre-BN (R = B*T).  Computes batch mean / biased var, a = relu((z-mean)*invstd*gamma+beta),
  * saves mean/invstd, updates running_mean/var (momentum 0.1, unbiased var) -- also under no_grad.
- * act: any MG_ACT_* (the generator uses RELU, the emotion discriminator's pre-training GELU). */
-size_t mg_bn_workspace_bytes(int C);
-int mg_bn_train_fwd(const float* z, float* a, long R, int C,
-                    const float* gamma, const float* beta,
+ * act: any MG_ACT_* (the generator uses RELU, the emotion discriminator's pre-training GELU).
+ * `groups` independent batches of R rows each, stacked along the rows of z / a (the generator forward of the critic step and
+ * of the generator step run as one 2B-row pass: src/gan/train_gan.py:186-189 and :216-219 use the same generator weights):
+ * batch statistics per group (save_mean / save_invstd: (groups, C)), running statistics updated group after group -- what
+ * consecutive forward calls do.  groups = 1: one plain forward.  `work`: mg_bn_workspace_bytes(C, groups). */
+size_t mg_bn_workspace_bytes(int C, int groups);
+int mg_bn_train_fwd(const float* z, float* a, long R, int C, int groups, const float* gamma, const float* beta,
                     float* running_mean, float* running_var, float momentum, float eps,
                     float* save_mean, float* save_invstd, int act,
                     void* work, size_t work_bytes, mg_stream_t stream);
-/* The same over `groups` independent batches of R rows each, stacked along the rows of z / a (the generator forward of
- * the critic step and of the generator step run as one 2B-row pass: src/gan/train_gan.py:186-189 and :216-219 use the
- * same generator weights): batch statistics per group (save_mean / save_invstd: (groups, C)), running statistics
- * updated group after group -- what consecutive forward calls do.  `work`: mg_bn_groups_workspace_bytes(C, groups). */
-size_t mg_bn_groups_workspace_bytes(int C, int groups);
-int mg_bn_train_fwd_groups(const float* z, float* a, long R, int C, int groups, const float* gamma, const float* beta,
-                           float* running_mean, float* running_var, float momentum, float eps,
-                           float* save_mean, float* save_invstd, int act,
-                           void* work, size_t work_bytes, mg_stream_t stream);
 /* backward: da (grad wrt a), a (forward output: the ReLU / LeakyReLU mask, tanh'), z.  Produces dz, dgamma, dbeta.
- * beta: only read for act = MG_ACT_GELU, whose derivative is taken at the BN output (recomputed from z); else may be NULL. */
+ * beta: only read for act = MG_ACT_GELU, whose derivative is taken at the BN output (recomputed from z); else may be NULL.
+ * `work`: mg_bn_workspace_bytes(C, 1). */
 int mg_bn_train_bwd(const float* da, const float* a, const float* z, float* dz, long R, int C,
                     const float* gamma, const float* beta, const float* save_mean, const float* save_invstd,
                     float* dgamma, float* dbeta, int act,
@@ -387,9 +376,11 @@ int mg_bn_fold(const float* gamma, const float* beta, const float* running_mean,
 
 /* ---- mean over time (AdaptiveAvgPool1d(1); src/gan/models.py:148, ed_model.py:60) ---- */
 int mg_meanT_fwd(const float* a, float* h, int B, int T, int C, mg_stream_t stream);
-/* dz[b,t,c] = dh[b,c]/T * act'(gref[b,t,c]) * gscale[c]   (gref/gscale may be NULL) */
-int mg_meanT_bwd(const float* dh, float* dz, int B, int T, int C,
-                 const float* gref, int gact, const float* gscale, mg_stream_t stream);
+/* dz[b,t,c] = dh[b,c]/T * act'(gref[b,t,c]) * gscale[c]   (gref/gscale may be NULL).
+ * mean_out != NULL: a scalar mean rides in the same launch (one extra block): mean_out[0] = mean_scale * mean(mean_src[0..mean_n))
+ * -- the generator's adversarial loss -mean(D(fake)), src/gan/train_gan.py:224. */
+int mg_meanT_bwd(const float* dh, float* dz, int B, int T, int C, const float* gref, int gact, const float* gscale,
+                 const float* mean_src, float* mean_out, int mean_n, float mean_scale, mg_stream_t stream);
 
 /* ---- LayerNorm over the last dim (src/gan/feature_encoder.py:19), D <= 64 ---- */
 int mg_layernorm_fwd(const float* x, float* y, float* xhat, int B, int D,
@@ -407,42 +398,29 @@ int mg_dhead_bwd(const float* ds, const float* f, const float* w, float* dU, flo
 int mg_dhead_fwd_bwd(const float* ds, const float* f, const float* emb, const float* w, const float* bias, float* s,
                      float* dU, float* demb, int B, int Be, int F, int E, int nb_emb, mg_stream_t stream);
 /* dw[j<F] = sum_{b<nb} ds[b] f[b,j] + sum_{b<ng} gf[b,j];  dw[F+j] = sum_{b<nb} ds[b] emb[b%Be,j];
- * dbias = sum_{b<nb} ds[b] */
-int mg_dhead_wgrad(const float* ds, const float* f, const float* emb, const float* gf,
-                   float* dw, float* dbias, int nb, int ng, int Be, int F, int E, mg_stream_t stream);
+ * dbias = sum_{b<nb} ds[b].
+ * loss_out != NULL: the critic's loss scalars (src/gan/train_gan.py:196-199, logging only) ride in the same launch (one extra
+ * block), from the scores s (2 * nb_loss: real rows, then fake) and the per-sample gradient norms of mg_gp_penalty:
+ *   gp_out[0] = mean((norms-1)^2) ;  loss_out = {mean fake - mean real + lambda_gp * gp_out[0], mean real, mean fake} */
+int mg_dhead_wgrad(const float* ds, const float* f, const float* emb, const float* gf, float* dw, float* dbias,
+                   int nb, int ng, int Be, int F, int E, const float* s, const float* norms, float lambda_gp,
+                   float* loss_out, float* gp_out, int nb_loss, mg_stream_t stream);
 
 /* ---- WGAN-GP pieces (src/gan/utils.py:75-90) ---- */
 /* xhat[b,:] = alpha[b]*real[b,:] + (1-alpha[b])*fake[b,:]   (n = T*C elements per sample) */
 int mg_gp_interp(const float* real, const float* fake, const float* alpha, float* xhat,
                  int B, long n, mg_stream_t stream);
 /* norms[b] = ||g[b,:]||_2 ; gp = mean((norm-1)^2) ; gbar[b,:] = coef*(2/B)*(norm-1)/norm * g[b,:]
- * gp may be NULL: the mean is then left to mg_wgan_d_loss_gp (one launch fewer) */
+ * gp may be NULL: the mean is then left to mg_dhead_wgrad's loss rider (one launch fewer) */
 int mg_gp_penalty(const float* g, float* gbar, float* norms, float* gp, float coef,
                   int B, long n, mg_stream_t stream);
 
 /* ---- losses ---- */
-/* loss_d = mean(s[nb:2nb]) - mean(s[0:nb]) + lambda_gp*gp ; out[0]=loss_d out[1]=mean_real out[2]=mean_fake */
-int mg_wgan_d_loss(const float* s, const float* gp, float lambda_gp, float* out, int nb, mg_stream_t stream);
-/* the same with the penalty computed from the per-sample gradient norms: gp_out[0] = mean((norms-1)^2) */
-int mg_wgan_d_loss_gp(const float* s, const float* norms, float lambda_gp, float* out, float* gp_out, int nb,
-                      mg_stream_t stream);
 /* cross entropy over C<=32 classes: loss = mean_b(-log softmax[b,y_b]); dlogits = coef*(softmax-onehot)/B */
 int mg_softmax_ce(const float* logits, const int64_t* target, float* loss, float* dlogits,
                   float coef, int B, int C, mg_stream_t stream);
-/* out[0] = -mean(s[0:B]) */
-/* mg_dhead_wgrad with the critic's loss scalars riding in the same launch (one extra block): mg_wgan_d_loss_gp's outputs
- * (loss_out = {loss_d, mean real, mean fake}, gp_out = mean((norm-1)^2)); loss_out = NULL: mg_dhead_wgrad. */
-int mg_dhead_wgrad_loss(const float* ds, const float* f, const float* emb, const float* gf, float* dw, float* dbias,
-                        int nb, int ng, int Be, int F, int E, const float* s, const float* norms, float lambda_gp,
-                        float* loss_out, float* gp_out, int nb_loss, mg_stream_t stream);
-/* mg_meanT_bwd with a scalar mean riding in the same launch (one extra block): mean_out[0] = mean_scale * mean(mean_src[0..n))
- * -- the generator's adversarial loss -mean(D(fake)), src/gan/train_gan.py:224.  mean_out = NULL: mg_meanT_bwd. */
-int mg_meanT_bwd_mean(const float* dh, float* dz, int B, int T, int C, const float* gref, int gact, const float* gscale,
-                      const float* mean_src, float* mean_out, int mean_n, float mean_scale, mg_stream_t stream);
-int mg_neg_mean(const float* s, float* out, int B, mg_stream_t stream);
 
 /* ---- elementwise helpers ---- */
-int mg_fill(float* x, float v, long n, mg_stream_t stream);
 int mg_axpby(const float* x, float* y, float a, float b, long n, mg_stream_t stream); /* y = a*x + b*y */
 /* dst[r, doff + j] = src[r, soff + j] for j < ncols (row-major 2-D copy; accumulate adds) */
 int mg_copy_cols(const float* src, int sld, int soff, float* dst, int dld, int doff,
@@ -553,27 +531,23 @@ int mg_ed_metrics_acc(const float* logits, const int64_t* labels, const float* l
  *      src/gan/train_gan.py:188,218; src/gan/utils.py:76; src/gan/feature_encoder.py:34) in ONE launch:
  *      normal[n_normal] ~ N(0,1), uniform[n_uniform] ~ U(0,1), mask{0,1} = keep-mask * 1/(1-p_drop).
  *      Philox4x32-10 keyed by `seed`; *step_counter (device, uint64) is read and then advanced on device,
- *      so a captured hipGraph draws fresh numbers at every replay.  Any pointer may be NULL. */
+ *      so a captured hipGraph draws fresh numbers at every replay.  Any tensor pointer may be NULL.
+ *      Riders (each NULL: absent):
+ *        adam_state:  *step_counter is NOT advanced here; instead the Adam state of the optimiser whose update will consume the
+ *                     draws is advanced (it is not read by this launch).  Pair it with mg_adam_flat(state_ticked = 1), which
+ *                     applies the update without advancing its state and advances *rng_step instead: two launches per sub-step
+ *                     instead of four.  Without adam_state a second launch of this call advances *step_counter.
+ *        adam_state2: one draw serving TWO updates (critic and generator step fused into one graph): both states are advanced.
+ *                     Needs adam_state, and must differ from it.
+ *        jobs:        mg_stage_rows_cursor (counter = step_counter; n_jobs, n_rows, order, order_len, base and the per-job rules
+ *                     as there) in the SAME launch: the staging rides as extra block planes.  Both only read the step counter
+ *                     and a fused step needs both first -- one launch and one dependent-launch gap fewer.  Needs both states
+ *                     and at least one tensor to draw. */
 int mg_rng_fill(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0,
-                float* mask1, long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter, mg_stream_t stream);
-
-/* The same draw WITHOUT advancing *step_counter; instead the Adam state of the optimiser whose update will consume
- * the draws is advanced here (it is not read by this launch).  Pair it with mg_adam_flat_ticked, which applies the
- * update without advancing its state and advances *rng_step instead: two launches per sub-step instead of four. */
-int mg_rng_fill_tick(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0,
-                     float* mask1, long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter,
-                     double* adam_state, float beta1, float beta2, mg_stream_t stream);
-/* One draw serving TWO updates (critic and generator step fused into one graph): both Adam states are advanced. */
-int mg_rng_fill_tick2(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0,
-                      float* mask1, long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter,
-                      double* adam_state, double* adam_state2, float beta1, float beta2, mg_stream_t stream);
-/* mg_rng_fill_tick2 and mg_stage_rows_cursor (counter = step_counter) as ONE launch: the staging rides as extra block planes.
- * Both only read the step counter and a fused step needs both first -- one launch and one dependent-launch gap fewer. */
-int mg_rng_fill_tick2_stage(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0,
-                            float* mask1, long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter,
-                            double* adam_state, double* adam_state2, float beta1, float beta2, const mg_stage_job* jobs,
-                            int n_jobs, int n_rows, const int64_t* order, long order_len, const uint64_t* base,
-                            mg_stream_t stream);
+                float* mask1, long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter,
+                double* adam_state, double* adam_state2, float beta1, float beta2, const mg_stage_job* jobs,
+                int n_jobs, int n_rows, const int64_t* order, long order_len, const uint64_t* base,
+                mg_stream_t stream);
 
 /* ---- sampling from a trained generator (melo_gan_amd.gan.generate; the reference's generation route, app.py:53-65,97-110) ----
  * mg_gen_inputs: the generator's three inputs for `rows` samples in ONE launch (replaces app.py's torch.randn noise, its
@@ -640,31 +614,24 @@ int mg_eval_noise(float* noise, int rows, int noise_dim, const uint64_t* counter
 /* ---- fused flat Adam / AdamW (torch.optim.Adam defaults; src/gan/train_gan.py:136-145,
  *      src/ae/train_ae.py:79).  state: double[4] = {step, beta1^step, beta2^step, unused},
  *      advanced on device so the launch is hipGraph-replayable.  grad_scale multiplies g first
- *      (used for 1/world_size and for clip_grad_norm_ via a device scalar if gs_dev != NULL). */
-int mg_adam_flat(float* p, const float* g, float* m, float* v, long n,
-                 float lr, float beta1, float beta2, float eps, float weight_decay,
-                 double* state, float grad_scale, const float* gs_dev, mg_stream_t stream);
-/* The update alone, for a state that mg_rng_fill_tick has already advanced; advances *rng_step (see there) unless
- * rng_step is NULL (the second of the two updates behind one mg_rng_fill_tick2 draw). */
-int mg_adam_flat_ticked(float* p, const float* g, float* m, float* v, long n,
-                        float lr, float beta1, float beta2, float eps, float weight_decay,
-                        const double* state, float grad_scale, const float* gs_dev, uint64_t* rng_step,
-                        mg_stream_t stream);
-/* The update that ALSO keeps WQ-layout copies (mg_conv16) of some weight tensors current: entry = a dense tensor
- * W(n,c,k) = w[n*w_sn + c*w_sc + k] at [start, start + N*Cc*K) of the flat buffer, in (N,Cc,K) order (w_sn = Cc*K,
- * w_sc = K) or (Cc,N,K) order (w_sn = K, w_sc = N*K); dst (N*Cc*K floats) receives the updated values in WQ order.
- * state_ticked: the Adam state was advanced by mg_rng_fill_tick(2) (rng_step, if not NULL, is advanced here); otherwise
- * it is advanced by this call. */
+ *      (used for 1/world_size and for clip_grad_norm_ via a device scalar if gs_dev != NULL).
+ *      state_ticked: the Adam state was already advanced by mg_rng_fill's adam_state rider and is only read here; rng_step,
+ *      if not NULL, is then advanced here (NULL for the second of the two updates behind one two-state draw).
+ *      Otherwise the state is advanced by this call (a launch of its own in front of the update).
+ *      table / n_table (NULL / 0: none): the update ALSO keeps WQ-layout copies (mg_conv16) of some weight tensors current:
+ *      entry = a dense tensor W(n,c,k) = w[n*w_sn + c*w_sc + k] at [start, start + N*Cc*K) of the flat buffer, in (N,Cc,K) order
+ *      (w_sn = Cc*K, w_sc = K) or (Cc,N,K) order (w_sn = K, w_sc = N*K); dst (N*Cc*K floats) receives the updated values in WQ
+ *      order. */
 #define MG_MAX_WQ_ENTRIES 8
 typedef struct mg_wq_entry {
     long start;
     int N, Cc, K, w_sn, w_sc;
     float* dst;
 } mg_wq_entry;
-int mg_adam_flat_wq(float* p, const float* g, float* m, float* v, long n,
-                    float lr, float beta1, float beta2, float eps, float weight_decay,
-                    double* state, float grad_scale, const float* gs_dev, int state_ticked, uint64_t* rng_step,
-                    const mg_wq_entry* table, int n_table, mg_stream_t stream);
+int mg_adam_flat(float* p, const float* g, float* m, float* v, long n,
+                 float lr, float beta1, float beta2, float eps, float weight_decay,
+                 double* state, float grad_scale, const float* gs_dev, int state_ticked, uint64_t* rng_step,
+                 const mg_wq_entry* table, int n_table, mg_stream_t stream);
 /* out[0] = sqrt(sum g^2) ; out[1] = min(1, max_norm/(norm+1e-6))  (clip_grad_norm_, train_ae.py:121) */
 int mg_grad_norm_clip(const float* g, long n, float max_norm, float* out, void* work, size_t work_bytes,
                       mg_stream_t stream);
@@ -696,9 +663,9 @@ typedef struct mg_mlp_cls {
  *   train = 0 (eval): no masks, no backward: logits and loss_rows only (z / a are written where not NULL).
  *   draw = 0: mask[l] is read.  draw = 1: mask[l] is drawn and written: Philox4x32-10 keyed by seed, counter = (e / 4,
  *     (e / 4 >> 32) ^ (stream << 28), step lo, step hi), word e % 4, e = the element's index in (rows, width[l]), stream =
- *     l for l < 2 -- element for element what mg_rng_fill(NULL, 0, NULL, 0, mask0, ., mask1, ., p_drop, seed, step_counter)
+ *     l for l < 2 -- element for element what mg_rng_fill(NULL, 0, NULL, 0, mask0, ., mask1, ., p_drop, seed, step_counter, ...)
  *     writes -- and l + 2 for l = 2, 3.  *step_counter is read, never written.
- *   tick_state != NULL: the Adam state {step, beta1^step, beta2^step} is advanced as by mg_rng_fill_tick (not read here). */
+ *   tick_state != NULL: the Adam state {step, beta1^step, beta2^step} is advanced as by mg_rng_fill's adam_state rider (not read here). */
 int mg_mlp_cls_fwd_bwd(const mg_mlp_cls* net, int rows, float* x, int64_t* y, const float* split_x, const int64_t* split_y,
                        long src_rows, const int64_t* order, long order_len, const uint64_t* base, int rule, int train, int draw,
                        float p_drop, uint64_t seed, const uint64_t* step_counter, double* tick_state, float beta1, float beta2,
@@ -707,7 +674,7 @@ int mg_mlp_cls_fwd_bwd(const mg_mlp_cls* net, int rows, float* x, int64_t* y, co
  * 16 x 16 tile over the rows in row order.  g[w_off[l] + o * in + i] = sum_r dz[l][r, o] * a[l-1][r, i] (a[-1] = x, dz[n_hidden]
  * = dlogits) and g[b_off[l] + o] = sum_r dz[l][r, o], always; w_off / b_off: n_hidden + 1 element offsets into the flat
  * buffers of n_flat floats (host arrays).  apply != 0: the same threads then apply AdamW to their elements of p / m / v from
- * the gradient in registers -- mg_adam_flat_ticked's formula and `state` semantics (state is read, never written; weight
+ * the gradient in registers -- mg_adam_flat(state_ticked = 1)'s formula and `state` semantics (state is read, never written; weight
  * decay decoupled).  One workgroup also writes loss[0] = (sum of loss_rows in row order) / rows, adds the batch to `metrics`
  * (if not NULL) exactly as mg_ed_metrics_acc does, and advances *rng_step (if not NULL; apply mode only). */
 int mg_mlp_cls_wgrad_update(const mg_mlp_cls* net, int rows, const float* x, const float* dlogits, const long* w_off,
@@ -731,9 +698,8 @@ int mg_vae_loss(const float* recon, const float* x, long n_x, const float* mu, c
 
 /* ---- hipGraph capture of a launch sequence issued through this library (or anything else on the stream) ---- */
 int mg_graph_begin(mg_stream_t stream);
-int mg_graph_end(mg_stream_t stream, void** graph_exec_out);
-/* mg_graph_end with the capture instantiated n (1..8) times (launches may then alternate between the executables). */
-int mg_graph_end_n(mg_stream_t stream, void** graph_execs_out, int n);
+/* Ends the capture and instantiates it n (1..8) times into execs_out[0..n) (launches may then alternate between the executables). */
+int mg_graph_end(mg_stream_t stream, void** execs_out, int n);
 /* kernel nodes of the graph the calling thread captured last (-1: unknown): the launches one replay stands for */
 int mg_graph_last_kernel_nodes(void);
 int mg_graph_launch(void* graph_exec, mg_stream_t stream);

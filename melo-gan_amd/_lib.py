@@ -101,16 +101,12 @@ SIGNATURES = {
     "mg_conv1d_scatter2": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), vp, sz, vp]),
     "mg_wq_relayout": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "mg_conv16_supported": (i32, [i32, i32, i32, i32, i32, i32]),
-    "mg_conv16": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), vp]),
     "mg_conv16_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
-    "mg_conv16_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), vp, vp]),
-    "mg_conv16_ex": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), C.POINTER(Conv16Extra), vp]),
+    "mg_conv16": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), C.POINTER(Conv16Extra), vp]),
     "mg_conv16_poolable": (i32, [i32, i32, i32, i32]),
-    "mg_conv16_pool": (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, C.POINTER(Epilogue), vp, f32, vp]),
     "mg_bn_train_fwd_parts": (i32, [vp, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, vp]),
     "mg_linear_workspace_bytes": (sz, [i32, i32, i32]),
-    "mg_linear": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(Epilogue), vp, sz, vp]),
-    "mg_linear_perm": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(Epilogue), i32, vp, sz, vp]),
+    "mg_linear": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(Epilogue), i32, vp, sz, vp]),
     "mg_conv_tile_config": (i32, [i64, i32, i32]),
     "mg_conv_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, sz, C.POINTER(i32), C.POINTER(i32)]),
     "mg_conv_finish_vec": (i32, [i32, i64, i32]),
@@ -126,24 +122,20 @@ SIGNATURES = {
     "mg_wgrad_multi": (i32, [vp, i32, i32, i32, vp, sz, vp]),
     "mg_colsum_workspace_bytes": (sz, [i32]),
     "mg_colsum": (i32, [vp, i64, i32, vp, vp, vp, sz, vp]),
-    "mg_bn_workspace_bytes": (sz, [i32]),
-    "mg_bn_train_fwd": (i32, [vp, vp, i64, i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, vp, sz, vp]),
-    "mg_bn_groups_workspace_bytes": (sz, [i32, i32]),
-    "mg_bn_train_fwd_groups": (i32, [vp, vp, i64, i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, vp, sz, vp]),
+    "mg_bn_workspace_bytes": (sz, [i32, i32]),
+    "mg_bn_train_fwd": (i32, [vp, vp, i64, i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, i32, vp, sz, vp]),
     "mg_bn_train_bwd": (i32, [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, i32, vp, sz, vp]),
     "mg_bn_train_bwd_parts": (i32, [vp, i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
     "mg_bn_eval_fwd": (i32, [vp, vp, i64, i32, vp, vp, vp, vp, f32, i32, vp]),
     "mg_bn_fold": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, i32, vp]),
     "mg_meanT_fwd": (i32, [vp, vp, i32, i32, i32, vp]),
-    "mg_meanT_bwd": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp]),
     "mg_layernorm_fwd": (i32, [vp, vp, vp, i32, i32, vp, vp, f32, vp]),
     "mg_layernorm_bwd_params": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "mg_dhead_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mg_dhead_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mg_dhead_fwd_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mg_dhead_wgrad": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "mg_dhead_wgrad_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, i32, vp]),
-    "mg_meanT_bwd_mean": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, f32, vp]),
+    "mg_dhead_wgrad": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, i32, vp]),
+    "mg_meanT_bwd": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, f32, vp]),
     "mg_row_chain": (i32, [vp, i32, i32, vp]),
     "mg_mean_scaled": (i32, [vp, vp, i32, f32, vp]),
     "mg_stamp": (i32, [vp, vp]),
@@ -155,11 +147,7 @@ SIGNATURES = {
     "mg_wino3_weights_multi": (i32, [vp, i32, vp]),
     "mg_gp_interp": (i32, [vp, vp, vp, vp, i32, i64, vp]),
     "mg_gp_penalty": (i32, [vp, vp, vp, vp, f32, i32, i64, vp]),
-    "mg_wgan_d_loss": (i32, [vp, vp, f32, vp, i32, vp]),
-    "mg_wgan_d_loss_gp": (i32, [vp, vp, f32, vp, vp, i32, vp]),
     "mg_softmax_ce": (i32, [vp, vp, vp, vp, f32, i32, i32, vp]),
-    "mg_neg_mean": (i32, [vp, vp, i32, vp]),
-    "mg_fill": (i32, [vp, f32, i64, vp]),
     "mg_axpby": (i32, [vp, vp, f32, f32, i64, vp]),
     "mg_copy_cols": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, vp]),
     "mg_transpose_bcl_blc": (i32, [vp, vp, i32, i32, i32, vp, i32, vp]),
@@ -169,10 +157,7 @@ SIGNATURES = {
     "mg_weighted_order": (i32, [vp, i64, vp, i64, C.c_uint64, C.c_uint64, vp]),
     "mg_ed_metrics_acc": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "mg_act_bwd": (i32, [vp, vp, i32, vp, vp, i64, vp]),
-    "mg_rng_fill": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp]),
-    "mg_rng_fill_tick": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp, f32, f32, vp]),
-    "mg_rng_fill_tick2": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp, vp, f32, f32, vp]),
-    "mg_rng_fill_tick2_stage": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp, vp, f32, f32, vp, i32, i32, vp, i64, vp, vp]),
+    "mg_rng_fill": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp, vp, f32, f32, vp, i32, i32, vp, i64, vp, vp]),
     "mg_gen_inputs": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, f32, vp, i32, C.c_uint64, vp]),
     "mg_emotion_score": (i32, [vp, i32, i32, vp, vp, vp, vp, vp]),
     "mg_eval_acc_words": (i64, [i32, i32]),
@@ -180,9 +165,7 @@ SIGNATURES = {
     "mg_eval_acc_reset": (i32, [vp, i32, i32, vp]),
     "mg_eval_acc": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, vp, vp]),
     "mg_eval_noise": (i32, [vp, i32, i32, vp, vp, i64, C.c_uint64, vp]),
-    "mg_adam_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp]),
-    "mg_adam_flat_ticked": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, vp, vp]),
-    "mg_adam_flat_wq": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, i32, vp, vp, i32, vp]),
+    "mg_adam_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, i32, vp, vp, i32, vp]),
     "mg_mlp_cls_fwd_bwd": (i32, [C.POINTER(MlpCls), i32, vp, vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, f32, C.c_uint64, vp, vp, f32, f32,
                                  vp, vp, vp, vp]),
     "mg_mlp_cls_wgrad_update": (i32, [C.POINTER(MlpCls), i32, vp, vp, C.POINTER(i64), C.POINTER(i64), i64, vp, vp, vp, vp, i32, f32, f32,
@@ -194,8 +177,7 @@ SIGNATURES = {
     "mg_vae_loss_workspace_bytes": (sz, []),
     "mg_vae_loss": (i32, [vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp, vp, sz, vp]),
     "mg_graph_begin": (i32, [vp]),
-    "mg_graph_end": (i32, [vp, C.POINTER(vp)]),
-    "mg_graph_end_n": (i32, [vp, C.POINTER(vp), i32]),
+    "mg_graph_end": (i32, [vp, C.POINTER(vp), i32]),
     "mg_graph_last_kernel_nodes": (i32, []),
     "mg_graph_launch": (i32, [vp, vp]),
     "mg_graph_destroy": (i32, [vp]),

@@ -264,7 +264,7 @@ int mg_conv_thin_dispatch(const float* x, const float* w, float* y, int B, int T
                           int flip, int transposed, int w_sn, int w_sc, long xbs, long ybs, const mg_epilogue* epi,
                           hipStream_t stream);
 
-// conv_mfma.hip: nn.Linear forward on the 64x64-tile window-GEMM kernel (K = 1), output columns in mg_linear_perm's order
+// conv_mfma.hip: nn.Linear forward on the 64x64-tile window-GEMM kernel (K = 1), output columns in mg_linear's perm_L order
 int mg_conv_linear_perm(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, const mg_epilogue* epi,
                         int perm_L, hipStream_t stream);
 

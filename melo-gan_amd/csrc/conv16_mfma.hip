@@ -12,7 +12,7 @@
 //
 // Weights come in the "WQ" layout, wq[((c/4)*5 + k)*N + n][c%4]: the four channels of a quad contiguous per (tap,
 // output column), which IS the LDS image (20 planes of 32 columns x 16 B per 16-channel chunk), so staging a chunk's
-// weights is 640 plain 16-byte copies.  The optimiser writes this layout next to the reference's (mg_adam_flat_wq), once
+// weights is 640 plain 16-byte copies.  The optimiser writes this layout next to the reference's (mg_adam_flat's table), once
 // per update and per direction a convolution is used in; mg_wq_relayout fills it from a state_dict tensor.
 //
 // MFMA operand maps (cdna_hip_programming.md section 3): A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15],
@@ -517,9 +517,6 @@ extern "C" int mg_conv16_plan(int B, int Tin, int N, int transposed, int* batch_
     return MG_OK;
 }
 
-static int conv16_launch(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-                         long xbs, long ybs, const mg_epilogue* epi, const mg_conv16_extra& ex, mg_stream_t stream);
-
 // 1 if a launch of this shape can also write the temporal mean of its output: gather form, every sample's time axis is
 // exactly one wave's rows of a tile (Tout = 32 with 64-row tiles, 16 with 32-row tiles)
 extern "C" int mg_conv16_poolable(int B, int Tin, int Cin, int N) {
@@ -528,41 +525,15 @@ extern "C" int mg_conv16_poolable(int B, int Tin, int Cin, int N) {
     return Tm == 16 * pick_rt((long)B * Tm, N);
 }
 
-extern "C" int mg_conv16_pool(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, long xbs, long ybs,
-                              const mg_epilogue* epi, float* pool, float pool_scale, mg_stream_t stream) {
-    MG_CHECK_ARG(pool != nullptr, "mg_conv16_pool: null pool tensor");
-    MG_CHECK_ARG(mg_conv16_poolable(B, Tin, Cin, N), "mg_conv16_pool: shape B=%d Tin=%d Cin=%d N=%d is not poolable", B, Tin, Cin, N);
-    MG_CHECK_ARG(!(epi && epi->accumulate), "mg_conv16_pool: the mean of an accumulating launch is not defined");
-    mg_conv16_extra ex{};
-    ex.pool = pool;
-    ex.pool_scale = pool_scale;
-    return conv16_launch(x, wq, y, B, Tin, Cin, N, 0, 0, xbs, ybs, epi, ex, stream);
-}
-
 extern "C" int mg_conv16(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-                         long xbs, long ybs, const mg_epilogue* epi, mg_stream_t stream) {
-    return conv16_launch(x, wq, y, B, Tin, Cin, N, transposed, Tout, xbs, ybs, epi, mg_conv16_extra{}, stream);
-}
-
-extern "C" int mg_conv16_stats(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-                               long xbs, long ybs, const mg_epilogue* epi, float* part, mg_stream_t stream) {
-    mg_conv16_extra ex{};
-    ex.part = part;
-    return conv16_launch(x, wq, y, B, Tin, Cin, N, transposed, Tout, xbs, ybs, epi, ex, stream);
-}
-
-extern "C" int mg_conv16_ex(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-                            long xbs, long ybs, const mg_epilogue* epi, const mg_conv16_extra* extra, mg_stream_t stream) {
-    return conv16_launch(x, wq, y, B, Tin, Cin, N, transposed, Tout, xbs, ybs, epi, extra ? *extra : mg_conv16_extra{}, stream);
-}
-
-static int conv16_launch(const float* x, const float* wq, float* y, int B, int Tin, int Cin, int N, int transposed, int Tout,
-                         long xbs, long ybs, const mg_epilogue* epi, const mg_conv16_extra& ex, mg_stream_t stream) {
+                         long xbs, long ybs, const mg_epilogue* epi, const mg_conv16_extra* extra, mg_stream_t stream) {
+    const mg_conv16_extra ex = extra ? *extra : mg_conv16_extra{};
     float* const part = ex.part;
     float* const pool = ex.pool;
     const float pool_scale = ex.pool_scale;
     MG_CHECK_ARG(x && wq && y, "mg_conv16: null tensor");
     MG_CHECK_ARG(!(part && epi && epi->accumulate), "mg_conv16: statistics of an accumulating launch are not defined");
+    MG_CHECK_ARG(!(pool && epi && epi->accumulate), "mg_conv16: the mean of an accumulating launch is not defined");
     MG_CHECK_ARG(!pool || (!transposed && mg_conv16_poolable(B, Tin, Cin, N)), "mg_conv16: shape is not poolable");
     MG_CHECK_ARG(!ex.mix_out || (ex.mix_real && ex.mix_alpha && ex.mix_rows > 0 && ex.mix_rows <= B && !ex.y_perm),
                  "mg_conv16: mix needs real, alpha, 0 < rows <= B and the plain output order");

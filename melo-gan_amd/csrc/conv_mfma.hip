@@ -57,7 +57,7 @@ struct ConvP {
     float* part;      // [ksplit][B*Tout*N] raw partial sums when ksplit > 1
     void* work;       // caller workspace (may be null)
     size_t work_bytes;
-    int perm_L, perm_C;   // perm_L > 0 (K = 1, Linear forward): output column n is weight row conv_wrow(n) -- mg_linear_perm's order
+    int perm_L, perm_C;   // perm_L > 0 (K = 1, Linear forward): output column n is weight row conv_wrow(n) -- mg_linear's perm_L order
     mg_epilogue e;
 };
 
@@ -797,7 +797,7 @@ extern "C" int mg_conv1d_gather(const float* x, const float* w, float* y, int B,
     return MG_EUNSUP;
 }
 
-// nn.Linear forward with mg_linear_perm's output order on the 64x64-tile kernel (K = 1): decoder.pre.2 (512 -> 8192) at the
+// nn.Linear forward with mg_linear's perm_L output order on the 64x64-tile kernel (K = 1): decoder.pre.2 (512 -> 8192) at the
 // 2B = 128 rows of the fused step, where the skinny kernel's 32x32 tiles re-read the weights four times (linear_skinny.hip
 // routes here; alone 13.2 us against 20.3).  No split-K.
 int mg_conv_linear_perm(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, const mg_epilogue* epi,

@@ -181,7 +181,7 @@ int plan_ksplit(int M, int N, int K) {
     return ks;
 }
 
-// Which kernel a Linear call runs and how its K range is cut: mg_linear_perm and the mg_linear_route query both decide here.
+// Which kernel a Linear call runs and how its K range is cut: mg_linear and the mg_linear_route query both decide here.
 struct LinRoute {
     bool window_gemm;     // the permuted forward on the 64x64-tile window GEMM (mg_conv_linear_perm); nothing below applies
     bool kcontig, vec;    // linear_skinny_kernel<W_KCONTIG, VEC>
@@ -226,17 +226,10 @@ extern "C" size_t mg_linear_workspace_bytes(int M, int N, int K) {
     return ks > 1 ? (size_t)ks * M * N * sizeof(float) : 0;
 }
 
-extern "C" int mg_linear_perm(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, int w_sc,
-                              const mg_epilogue* epi, int perm_L, void* work, size_t work_bytes, mg_stream_t stream);
 extern "C" int mg_linear(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, int w_sc,
-                         const mg_epilogue* epi, void* work, size_t work_bytes, mg_stream_t stream) {
-    return mg_linear_perm(x, w, y, M, K, N, w_sn, w_sc, epi, 0, work, work_bytes, stream);
-}
-
-extern "C" int mg_linear_perm(const float* x, const float* w, float* y, int M, int K, int N, int w_sn, int w_sc,
-                              const mg_epilogue* epi, int perm_L, void* work, size_t work_bytes, mg_stream_t stream) {
+                         const mg_epilogue* epi, int perm_L, void* work, size_t work_bytes, mg_stream_t stream) {
     MG_CHECK_ARG(x && w && y, "mg_linear: null tensor");
-    MG_CHECK_ARG(perm_L >= 0 && (perm_L == 0 || N % perm_L == 0), "mg_linear_perm: perm_L must divide N");
+    MG_CHECK_ARG(perm_L >= 0 && (perm_L == 0 || N % perm_L == 0), "mg_linear: perm_L must divide N");
     MG_CHECK_ARG(M > 0 && K > 0 && N > 0 && w_sn > 0 && w_sc > 0, "mg_linear: bad shape");
     MG_CHECK_ARG(w_sn == 1 || w_sc == 1, "mg_linear: one weight stride must be 1");
     const LinRoute r = linear_route(M, K, N, w_sn, w_sc, perm_L, al16(x), al16(w));

@@ -14,29 +14,13 @@ void mg_set_error(const char* fmt, ...) {
 
 extern "C" {
 
-int mg_version(void) { return 103; }
+int mg_version(void) { return 104; }
 const char* mg_last_error(void) { return g_err; }
 
 int mg_graph_begin(mg_stream_t stream) {
     MG_HIP(hipStreamBeginCapture((hipStream_t)stream, hipStreamCaptureModeRelaxed));
     return MG_OK;
 }
-int mg_graph_end(mg_stream_t stream, void** graph_exec_out) {
-    MG_CHECK_ARG(graph_exec_out != nullptr, "mg_graph_end: null out pointer");
-    hipGraph_t graph = nullptr;
-    MG_HIP(hipStreamEndCapture((hipStream_t)stream, &graph));
-    hipGraphExec_t exec = nullptr;
-    hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (e != hipSuccess) {
-        mg_set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e));
-        return MG_EHIP;
-    }
-    *graph_exec_out = (void*)exec;
-    return MG_OK;
-}
-// The same capture instantiated `n` times (an experiment knob: alternating executables of the step graph measured slower
-// than replaying one, melo-gan_amd/ops.py::Graph).
 static thread_local int g_last_kernel_nodes = -1;
 int mg_graph_last_kernel_nodes(void) { return g_last_kernel_nodes; }
 
@@ -57,8 +41,10 @@ static void count_kernel_nodes(hipGraph_t graph) {
     free(nodes);
 }
 
-int mg_graph_end_n(mg_stream_t stream, void** graph_execs_out, int n) {
-    MG_CHECK_ARG(graph_execs_out != nullptr && n >= 1 && n <= 8, "mg_graph_end_n: 1..8 executables");
+// The capture instantiated `n` times (more than one is an experiment knob: alternating executables of the step graph measured
+// slower than replaying one, melo-gan_amd/ops.py::Graph).
+int mg_graph_end(mg_stream_t stream, void** execs_out, int n) {
+    MG_CHECK_ARG(execs_out != nullptr && n >= 1 && n <= 8, "mg_graph_end: 1..8 executables");
     hipGraph_t graph = nullptr;
     MG_HIP(hipStreamEndCapture((hipStream_t)stream, &graph));
     count_kernel_nodes(graph);
@@ -66,12 +52,12 @@ int mg_graph_end_n(mg_stream_t stream, void** graph_execs_out, int n) {
         hipGraphExec_t exec = nullptr;
         hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
         if (e != hipSuccess) {
-            for (int j = 0; j < i; ++j) hipGraphExecDestroy((hipGraphExec_t)graph_execs_out[j]);
+            for (int j = 0; j < i; ++j) hipGraphExecDestroy((hipGraphExec_t)execs_out[j]);
             hipGraphDestroy(graph);
             mg_set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e));
             return MG_EHIP;
         }
-        graph_execs_out[i] = (void*)exec;
+        execs_out[i] = (void*)exec;
     }
     hipGraphDestroy(graph);
     return MG_OK;

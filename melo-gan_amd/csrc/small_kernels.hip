@@ -181,7 +181,7 @@ __global__ void bn_fold_kernel(const float* gamma, const float* beta, const floa
 }
 
 // ---------------- BatchNorm from the producing convolution's partial statistics: ONE launch ----------------
-// part[g*np + p][3][C] (float): per-(workgroup, wave) column partials written by mg_conv16_stats -- the sum, the sum of
+// part[g*np + p][3][C] (float): per-(workgroup, wave) column partials written by mg_conv16's `part` rider -- the sum, the sum of
 // squares about that wave's OWN mean, and the number of rows.  A block owns 64 channels x one row slice of one group: it
 // first combines ITS channels' partials (fixed order, fp64, parallel-variance rule: n = sum n_p, mean = sum S_p / n,
 // M2 = sum M2_p + sum S_p^2 / n_p - (sum S_p)^2 / n -- the between-wave term in fp64 from fp32 inputs, never E[x^2] - mean^2
@@ -657,7 +657,7 @@ __device__ __forceinline__ void wgan_d_loss_block(const DLoss& L) {
 }
 
 // one wave per output element j: lanes stride over the batch rows, shuffle-reduce.  Optional rider (loss.out != nullptr):
-// one extra block at the end of the grid computes the critic's loss scalars (mg_wgan_d_loss_gp) -- logging only, nothing
+// one extra block at the end of the grid computes the critic's loss scalars (mg_dhead_wgrad's loss rider) -- logging only, nothing
 // in the step depends on them, so they need no launch of their own.
 __global__ void dhead_wgrad_kernel(const float* __restrict__ ds, const float* __restrict__ f,
                                    const float* __restrict__ emb, const float* __restrict__ gf, float* dw,
@@ -748,31 +748,6 @@ __global__ void gp_final_kernel(const float* norms, float* gp, int B) {
 }
 
 // ---------------- losses ----------------
-__global__ void wgan_d_loss_kernel(const float* s, const float* gp, const float* norms, float lambda_gp, float* out,
-                                   float* gp_out, int nb) {
-    __shared__ float sh[16];
-    float r = 0.f, f = 0.f, q = 0.f;
-    for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-        r += s[b];
-        f += s[nb + b];
-        if (norms) {
-            const float d = norms[b] - 1.f;
-            q += d * d;
-        }
-    }
-    r = block_sum(r, sh);
-    f = block_sum(f, sh);
-    if (norms) q = block_sum(q, sh);
-    if (threadIdx.x == 0) {
-        const float mr = r / (float)nb, mf = f / (float)nb;
-        const float pen = norms ? q / (float)nb : gp[0];
-        if (norms) gp_out[0] = pen;
-        out[0] = mf - mr + lambda_gp * pen;
-        out[1] = mr;
-        out[2] = mf;
-    }
-}
-
 __global__ void neg_mean_kernel(const float* s, float* out, int B, float scale) {
     __shared__ float sh[16];
     float r = 0.f;
@@ -806,10 +781,6 @@ __global__ void softmax_ce_kernel(const float* __restrict__ logits, const int64_
 }
 
 // ---------------- elementwise ----------------
-__global__ void fill_kernel(float* x, float v, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] = v;
-}
 __global__ void axpby_kernel(const float* __restrict__ x, float* __restrict__ y, float a, float b, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = a * x[i] + (b != 0.f ? b * y[i] : 0.f);
@@ -1499,7 +1470,6 @@ inline unsigned nblk(long n, int bs = 256) { return (unsigned)mg_cdiv(n, bs); }
 extern "C" {
 
 size_t mg_colsum_workspace_bytes(int C) { return ((size_t)RED_SPLITS + 1) * 2 * (size_t)C * sizeof(double); }
-size_t mg_bn_workspace_bytes(int C) { return mg_colsum_workspace_bytes(C); }
 
 int mg_colsum(const float* x, long R, int C, float* sum, float* sumsq, void* work, size_t work_bytes,
               mg_stream_t stream) {
@@ -1514,38 +1484,38 @@ int mg_colsum(const float* x, long R, int C, float* sum, float* sumsq, void* wor
     return MG_OK;
 }
 
-size_t mg_bn_groups_workspace_bytes(int C, int groups) { return (size_t)(groups < 1 ? 1 : groups) * mg_colsum_workspace_bytes(C); }
+size_t mg_bn_workspace_bytes(int C, int groups) { return (size_t)(groups < 1 ? 1 : groups) * mg_colsum_workspace_bytes(C); }
 
-int mg_bn_train_fwd_groups(const float* z, float* a, long R, int C, int groups, const float* gamma, const float* beta,
-                           float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
-                           float* save_invstd, int act, void* work, size_t work_bytes, mg_stream_t stream) {
+// The row slices of a BatchNorm apply pass (bn_parts_apply_kernel / bn_bwd_parts_apply_kernel, grid.y): ~256 blocks of
+// BNA_THREADS threads in all, at least 64 rows (one per row lane) each.  Returns the rows per slice.
+static long bn_row_slices(long R, int C, int groups, long* slices) {
+    long n = 256 / (mg_cdiv(C, 64) * groups);
+    if (n < 1) n = 1;
+    if (n > mg_cdiv(R, 64)) n = mg_cdiv(R, 64);
+    const long rows_per = mg_cdiv(R, n);
+    *slices = mg_cdiv(R, rows_per);
+    return rows_per;
+}
+
+int mg_bn_train_fwd(const float* z, float* a, long R, int C, int groups, const float* gamma, const float* beta,
+                    float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
+                    float* save_invstd, int act, void* work, size_t work_bytes, mg_stream_t stream) {
     MG_CHECK_ARG(z && a && gamma && beta && save_mean && save_invstd && R > 0 && C > 0 && groups >= 1 && groups <= 64,
                  "mg_bn_train_fwd: bad args");
     MG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "mg_bn_train_fwd: running stats must come in pairs");
-    if (!work || work_bytes < mg_bn_groups_workspace_bytes(C, groups)) { mg_set_error("mg_bn_train_fwd: workspace too small"); return MG_EWORK; }
+    if (!work || work_bytes < mg_bn_workspace_bytes(C, groups)) { mg_set_error("mg_bn_train_fwd: workspace too small"); return MG_EWORK; }
     const RedPlan pl = red_plan(R);
     dim3 grid((unsigned)mg_cdiv(C, 64), (unsigned)pl.nsplit, (unsigned)groups);
     hipLaunchKernelGGL(colsum_partial_kernel<0>, grid, dim3(256), 0, ST, z, nullptr, nullptr, nullptr, nullptr, 0, R, C,
                        pl.rows_per, (double*)work, 1);
-    // row slices: ~256 blocks of 1024 threads in all, at least 64 rows (one per row lane) each
     const long cb = mg_cdiv(C, 64);
-    long slices = 256 / (cb * groups);
-    if (slices < 1) slices = 1;
-    if (slices > mg_cdiv(R, 64)) slices = mg_cdiv(R, 64);
-    const long rows_per = mg_cdiv(R, slices);
-    slices = mg_cdiv(R, rows_per);
+    long slices;
+    const long rows_per = bn_row_slices(R, C, groups, &slices);
     hipLaunchKernelGGL(bn_parts_apply_kernel<double>, dim3((unsigned)cb, (unsigned)slices, (unsigned)groups), dim3(BNA_THREADS), 0, ST,
                        (const double*)work, pl.nsplit, groups, R, C, momentum, eps, running_mean, running_var, save_mean,
                        save_invstd, z, a, gamma, beta, act, rows_per);
     MG_CHECK_LAUNCH("bn_train_fwd");
     return MG_OK;
-}
-
-int mg_bn_train_fwd(const float* z, float* a, long R, int C, const float* gamma, const float* beta,
-                    float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
-                    float* save_invstd, int act, void* work, size_t work_bytes, mg_stream_t stream) {
-    return mg_bn_train_fwd_groups(z, a, R, C, 1, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
-                                  save_invstd, act, work, work_bytes, stream);
 }
 
 int mg_bn_train_fwd_parts(const float* part, int part_rows_per_group, int groups, const float* z, float* a, long R, int C,
@@ -1554,14 +1524,9 @@ int mg_bn_train_fwd_parts(const float* part, int part_rows_per_group, int groups
     MG_CHECK_ARG(part && z && a && gamma && beta && save_mean && save_invstd && R > 0 && C > 0 && groups >= 1 &&
                  part_rows_per_group > 0, "mg_bn_train_fwd_parts: bad args");
     MG_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "mg_bn_train_fwd_parts: running stats must come in pairs");
-    // row slices: ~512 blocks in all (2 per CU), at least 64 rows each
-    // row slices: ~256 blocks of 1024 threads in all, at least 64 rows (one per row lane) each
     const long cb = mg_cdiv(C, 64);
-    long slices = 256 / (cb * groups);
-    if (slices < 1) slices = 1;
-    if (slices > mg_cdiv(R, 64)) slices = mg_cdiv(R, 64);
-    const long rows_per = mg_cdiv(R, slices);
-    slices = mg_cdiv(R, rows_per);
+    long slices;
+    const long rows_per = bn_row_slices(R, C, groups, &slices);
     hipLaunchKernelGGL(bn_parts_apply_kernel<float>, dim3((unsigned)cb, (unsigned)slices, (unsigned)groups), dim3(BNA_THREADS), 0, ST, part,
                        part_rows_per_group, groups, R, C, momentum, eps, running_mean, running_var, save_mean, save_invstd, z, a,
                        gamma, beta, act, rows_per);
@@ -1574,18 +1539,15 @@ int mg_bn_train_bwd(const float* da, const float* a, const float* z, float* dz, 
                     int act, void* work, size_t work_bytes, mg_stream_t stream) {
     MG_CHECK_ARG(da && a && z && dz && gamma && save_mean && save_invstd && dgamma && dbeta, "mg_bn_train_bwd: bad args");
     MG_CHECK_ARG(act != MG_ACT_GELU || beta, "mg_bn_train_bwd: GELU needs beta (its derivative is taken at the BN output)");
-    if (!work || work_bytes < mg_bn_workspace_bytes(C)) { mg_set_error("mg_bn_train_bwd: workspace too small"); return MG_EWORK; }
+    if (!work || work_bytes < mg_bn_workspace_bytes(C, 1)) { mg_set_error("mg_bn_train_bwd: workspace too small"); return MG_EWORK; }
     const RedPlan pl = red_plan(R);
     double* part = (double*)work;
     dim3 grid((unsigned)mg_cdiv(C, 64), (unsigned)pl.nsplit);
     hipLaunchKernelGGL(colsum_partial_kernel<1>, grid, dim3(256), 0, ST, da, a, z, save_mean, save_invstd, act, R, C,
                        pl.rows_per, part, 1, gamma, beta);
     const long cb = mg_cdiv(C, 64);
-    long slices = 256 / cb;
-    if (slices < 1) slices = 1;
-    if (slices > mg_cdiv(R, 64)) slices = mg_cdiv(R, 64);
-    const long rows_per = mg_cdiv(R, slices);
-    slices = mg_cdiv(R, rows_per);
+    long slices;
+    const long rows_per = bn_row_slices(R, C, 1, &slices);
     hipLaunchKernelGGL(bn_bwd_parts_apply_kernel<double>, dim3((unsigned)cb, (unsigned)slices), dim3(BNA_THREADS), 0, ST, (const double*)part,
                        pl.nsplit, C, R, da, a, z, dz, gamma, beta, save_mean, save_invstd, dgamma, dbeta, act, rows_per);
     MG_CHECK_LAUNCH("bn_train_bwd");
@@ -1599,11 +1561,8 @@ int mg_bn_train_bwd_parts(const double* part, int part_rows, const float* da, co
                  "mg_bn_train_bwd_parts: bad args");
     MG_CHECK_ARG(act == MG_ACT_RELU || act == MG_ACT_LRELU, "mg_bn_train_bwd_parts: ReLU / LeakyReLU layers only");
     const long cb = mg_cdiv(C, 64);
-    long slices = 256 / cb;
-    if (slices < 1) slices = 1;
-    if (slices > mg_cdiv(R, 64)) slices = mg_cdiv(R, 64);
-    const long rows_per = mg_cdiv(R, slices);
-    slices = mg_cdiv(R, rows_per);
+    long slices;
+    const long rows_per = bn_row_slices(R, C, 1, &slices);
     hipLaunchKernelGGL(bn_bwd_parts_apply_kernel<double>, dim3((unsigned)cb, (unsigned)slices), dim3(BNA_THREADS), 0, ST, part, part_rows,
                        C, R, da, a, z, dz, gamma, beta, save_mean, save_invstd, dgamma, dbeta, act, rows_per);
     MG_CHECK_LAUNCH("bn_train_bwd_parts");
@@ -1635,10 +1594,10 @@ int mg_meanT_fwd(const float* a, float* h, int B, int T, int C, mg_stream_t stre
     return MG_OK;
 }
 
-int mg_meanT_bwd_mean(const float* dh, float* dz, int B, int T, int C, const float* gref, int gact, const float* gscale,
-                      const float* mean_src, float* mean_out, int mean_n, float mean_scale, mg_stream_t stream) {
+int mg_meanT_bwd(const float* dh, float* dz, int B, int T, int C, const float* gref, int gact, const float* gscale,
+                 const float* mean_src, float* mean_out, int mean_n, float mean_scale, mg_stream_t stream) {
     MG_CHECK_ARG(dh && dz && B > 0 && T > 0 && C > 0, "mg_meanT_bwd: bad args");
-    MG_CHECK_ARG(!mean_out || (mean_src && mean_n > 0), "mg_meanT_bwd_mean: the mean rider needs a source and a length");
+    MG_CHECK_ARG(!mean_out || (mean_src && mean_n > 0), "mg_meanT_bwd: the mean rider needs a source and a length");
     const long n = (long)B * T * C;
     const unsigned extra = mean_out ? 1u : 0u;
     auto al16 = [](const void* q) { return q == nullptr || ((((uintptr_t)q) & 15) == 0); };
@@ -1650,11 +1609,6 @@ int mg_meanT_bwd_mean(const float* dh, float* dz, int B, int T, int C, const flo
                            mean_src, mean_out, mean_n, mean_scale);
     MG_CHECK_LAUNCH("meanT_bwd");
     return MG_OK;
-}
-
-int mg_meanT_bwd(const float* dh, float* dz, int B, int T, int C, const float* gref, int gact, const float* gscale,
-                 mg_stream_t stream) {
-    return mg_meanT_bwd_mean(dh, dz, B, T, C, gref, gact, gscale, nullptr, nullptr, 0, 0.f, stream);
 }
 
 int mg_layernorm_fwd(const float* x, float* y, float* xhat, int B, int D, const float* gamma, const float* beta,
@@ -1702,21 +1656,16 @@ int mg_dhead_fwd_bwd(const float* ds, const float* f, const float* emb, const fl
     return MG_OK;
 }
 
-int mg_dhead_wgrad_loss(const float* ds, const float* f, const float* emb, const float* gf, float* dw, float* dbias,
-                        int nb, int ng, int Be, int F, int E, const float* s, const float* norms, float lambda_gp,
-                        float* loss_out, float* gp_out, int nb_loss, mg_stream_t stream) {
+int mg_dhead_wgrad(const float* ds, const float* f, const float* emb, const float* gf, float* dw, float* dbias,
+                   int nb, int ng, int Be, int F, int E, const float* s, const float* norms, float lambda_gp,
+                   float* loss_out, float* gp_out, int nb_loss, mg_stream_t stream) {
     MG_CHECK_ARG(ds && f && dw && dbias, "mg_dhead_wgrad: bad args");
-    MG_CHECK_ARG(!loss_out || (s && norms && gp_out && nb_loss > 0), "mg_dhead_wgrad_loss: the loss rider needs s, norms, gp_out");
+    MG_CHECK_ARG(!loss_out || (s && norms && gp_out && nb_loss > 0), "mg_dhead_wgrad: the loss rider needs s, norms, gp_out");
     const DLoss loss{s, norms, lambda_gp, loss_out, gp_out, nb_loss};
     hipLaunchKernelGGL(dhead_wgrad_kernel, dim3(nblk(F + E + 1, 4) + (loss_out ? 1u : 0u)), dim3(256), 0, ST, ds, f, emb, gf, dw,
                        dbias, nb, ng, Be > 0 ? Be : 1, F, emb ? E : 0, loss);
     MG_CHECK_LAUNCH("dhead_wgrad");
     return MG_OK;
-}
-
-int mg_dhead_wgrad(const float* ds, const float* f, const float* emb, const float* gf, float* dw, float* dbias,
-                   int nb, int ng, int Be, int F, int E, mg_stream_t stream) {
-    return mg_dhead_wgrad_loss(ds, f, emb, gf, dw, dbias, nb, ng, Be, F, E, nullptr, nullptr, 0.f, nullptr, nullptr, 0, stream);
 }
 
 int mg_gp_interp(const float* real, const float* fake, const float* alpha, float* xhat, int B, long n,
@@ -1736,35 +1685,11 @@ int mg_gp_penalty(const float* g, float* gbar, float* norms, float* gp, float co
     return MG_OK;
 }
 
-int mg_wgan_d_loss(const float* s, const float* gp, float lambda_gp, float* out, int nb, mg_stream_t stream) {
-    MG_CHECK_ARG(s && gp && out && nb > 0, "mg_wgan_d_loss: bad args");
-    hipLaunchKernelGGL(wgan_d_loss_kernel, dim3(1), dim3(256), 0, ST, s, gp, (const float*)nullptr, lambda_gp, out,
-                       (float*)nullptr, nb);
-    MG_CHECK_LAUNCH("wgan_d_loss");
-    return MG_OK;
-}
-
-int mg_wgan_d_loss_gp(const float* s, const float* norms, float lambda_gp, float* out, float* gp_out, int nb,
-                      mg_stream_t stream) {
-    MG_CHECK_ARG(s && norms && out && gp_out && nb > 0, "mg_wgan_d_loss_gp: bad args");
-    hipLaunchKernelGGL(wgan_d_loss_kernel, dim3(1), dim3(256), 0, ST, s, (const float*)nullptr, norms, lambda_gp, out,
-                       gp_out, nb);
-    MG_CHECK_LAUNCH("wgan_d_loss_gp");
-    return MG_OK;
-}
-
 int mg_softmax_ce(const float* logits, const int64_t* target, float* loss, float* dlogits, float coef, int B, int C,
                   mg_stream_t stream) {
     MG_CHECK_ARG(logits && target && loss && B > 0 && C > 0 && C <= 32, "mg_softmax_ce: bad args");
     hipLaunchKernelGGL(softmax_ce_kernel, dim3(1), dim3(256), 0, ST, logits, target, loss, dlogits, coef, B, C);
     MG_CHECK_LAUNCH("softmax_ce");
-    return MG_OK;
-}
-
-int mg_neg_mean(const float* s, float* out, int B, mg_stream_t stream) {
-    MG_CHECK_ARG(s && out && B > 0, "mg_neg_mean: bad args");
-    hipLaunchKernelGGL(neg_mean_kernel, dim3(1), dim3(256), 0, ST, s, out, B, -1.f);
-    MG_CHECK_LAUNCH("neg_mean");
     return MG_OK;
 }
 
@@ -1783,14 +1708,6 @@ int mg_stamp(unsigned long long* dst, mg_stream_t stream) {
     MG_CHECK_ARG(dst, "mg_stamp: bad args");
     hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, ST, dst);
     MG_CHECK_LAUNCH("stamp");
-    return MG_OK;
-}
-
-int mg_fill(float* x, float v, long n, mg_stream_t stream) {
-    MG_CHECK_ARG(x && n >= 0, "mg_fill: bad args");
-    if (n == 0) return MG_OK;
-    hipLaunchKernelGGL(fill_kernel, dim3(nblk(n)), dim3(256), 0, ST, x, v, n);
-    MG_CHECK_LAUNCH("fill");
     return MG_OK;
 }
 
@@ -1876,45 +1793,52 @@ int mg_act_bwd(const float* dy, const float* gref, int gact, const float* emul, 
     return MG_OK;
 }
 
-static int rng_fill_impl(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0,
-                         float* mask1, long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter,
-                         double* tick_state, double* tick_state2, float beta1, float beta2, mg_stream_t stream,
-                         const StageRide* ride = nullptr) {
+int mg_rng_fill(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0, float* mask1,
+                long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter, double* adam_state, double* adam_state2,
+                float beta1, float beta2, const mg_stage_job* jobs, int n_jobs, int n_rows, const int64_t* order,
+                long order_len, const uint64_t* base, mg_stream_t stream) {
     MG_CHECK_ARG(step_counter != nullptr, "mg_rng_fill: null step counter");
     MG_CHECK_ARG(p_drop >= 0.f && p_drop < 1.f, "mg_rng_fill: bad dropout probability");
-    RngJobs jobs{};
+    MG_CHECK_ARG(!adam_state2 || (adam_state && adam_state != adam_state2), "mg_rng_fill: adam_state2 needs a distinct adam_state");
+    StageRide sr{};
+    if (jobs) {
+        MG_CHECK_ARG(adam_state && adam_state2, "mg_rng_fill: the staging rider needs both adam states");
+        MG_CHECK_ARG(n_jobs > 0 && n_jobs <= MG_MAX_STAGE_JOBS && n_rows > 0 && order_len > 0 && base,
+                     "mg_rng_fill: the staging rider needs 1..%d jobs, rows, a positive order length and base", MG_MAX_STAGE_JOBS);
+        sr.n_jobs = n_jobs; sr.n_rows = n_rows; sr.order = order; sr.order_len = order_len;
+        sr.base = (const unsigned long long*)base;
+        for (int i = 0; i < n_jobs; ++i) {
+            const mg_stage_job& j = jobs[i];
+            MG_CHECK_ARG(j.src && j.dst && j.row_bytes > 0 && (j.row_bytes & 3) == 0 && j.src_rows > 0 && !j.idx && j.rows == 0 &&
+                             ((((uintptr_t)j.src | (uintptr_t)j.dst)) & 3) == 0 && (order || j.src_rows >= order_len),
+                         "mg_rng_fill: job %d: the rules of mg_stage_rows_cursor", i);
+            MG_CHECK_ARG(j.dst_pitch == 0 || (j.dst_pitch >= j.row_bytes && (j.dst_pitch & 3) == 0),
+                         "mg_rng_fill: job %d: dst_pitch must be 0 or a multiple of 4 that holds a row", i);
+            sr.J.j[i] = j;
+        }
+    }
+    RngJobs draws{};
     int n = 0;
     long mx = 0;
     auto add = [&](float* d, long cnt, int kind) {
-        if (d && cnt > 0) { jobs.j[n++] = RngJob{d, cnt, kind, p_drop}; if (cnt > mx) mx = cnt; }
+        if (d && cnt > 0) { draws.j[n++] = RngJob{d, cnt, kind, p_drop}; if (cnt > mx) mx = cnt; }
     };
     add(normal, n_normal, 0);
     add(uniform, n_uniform, 1);
     add(mask0, n_mask0, 2);
     add(mask1, n_mask1, 2);
-    jobs.njobs = n;
-    if (n == 0 && !ride) return MG_OK;
+    draws.njobs = n;
+    if (n == 0 && !jobs) return MG_OK;
     MG_CHECK_ARG(n > 0, "mg_rng_fill: the staging rider needs at least one tensor to draw");
     unsigned gx = (unsigned)mg_cdiv(mg_cdiv(mx, 4), 256);
     if (gx > 256) gx = 256;
-    StageRide sr{};
-    if (ride) {
-        sr = *ride;
-        if (gx < 256) gx = 256;        // row pieces for the staging planes
-    }
-    hipLaunchKernelGGL(rng_fill_kernel, dim3(gx, n + sr.n_jobs), dim3(256), 0, ST, jobs, (unsigned long long)seed,
-                       (unsigned long long*)step_counter, tick_state, tick_state2, (double)beta1, (double)beta2, sr);
-    if (!tick_state)
+    if (jobs && gx < 256) gx = 256;        // row pieces for the staging planes
+    hipLaunchKernelGGL(rng_fill_kernel, dim3(gx, n + sr.n_jobs), dim3(256), 0, ST, draws, (unsigned long long)seed,
+                       (unsigned long long*)step_counter, adam_state, adam_state2, (double)beta1, (double)beta2, sr);
+    if (!adam_state)
         hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(64), 0, ST, (unsigned long long*)step_counter);
     MG_CHECK_LAUNCH("rng_fill");
     return MG_OK;
-}
-
-int mg_rng_fill(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0,
-                           float* mask1, long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter,
-                           mg_stream_t stream) {
-    return rng_fill_impl(normal, n_normal, uniform, n_uniform, mask0, n_mask0, mask1, n_mask1, p_drop, seed,
-                         step_counter, nullptr, nullptr, 0.f, 0.f, stream);
 }
 
 int mg_gen_inputs(const int32_t* emotion, const int32_t* sample, int rows, float* noise, int noise_dim, float* numeric,
@@ -1996,74 +1920,11 @@ int mg_ed_metrics_acc(const float* logits, const int64_t* labels, const float* l
     return MG_OK;
 }
 
-int mg_rng_fill_tick(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0,
-                                long n_mask0, float* mask1, long n_mask1, float p_drop, uint64_t seed,
-                                uint64_t* step_counter, double* adam_state, float beta1, float beta2,
-                                mg_stream_t stream) {
-    MG_CHECK_ARG(adam_state, "mg_rng_fill_tick: null adam_state");
-    return rng_fill_impl(normal, n_normal, uniform, n_uniform, mask0, n_mask0, mask1, n_mask1, p_drop, seed,
-                         step_counter, adam_state, nullptr, beta1, beta2, stream);
-}
-
-int mg_rng_fill_tick2(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0,
-                      long n_mask0, float* mask1, long n_mask1, float p_drop, uint64_t seed,
-                      uint64_t* step_counter, double* adam_state, double* adam_state2, float beta1, float beta2,
-                      mg_stream_t stream) {
-    MG_CHECK_ARG(adam_state && adam_state2 && adam_state != adam_state2, "mg_rng_fill_tick2: two distinct adam states");
-    return rng_fill_impl(normal, n_normal, uniform, n_uniform, mask0, n_mask0, mask1, n_mask1, p_drop, seed,
-                         step_counter, adam_state, adam_state2, beta1, beta2, stream);
-}
-
-int mg_rng_fill_tick2_stage(float* normal, long n_normal, float* uniform, long n_uniform, float* mask0, long n_mask0, float* mask1,
-                            long n_mask1, float p_drop, uint64_t seed, uint64_t* step_counter, double* adam_state,
-                            double* adam_state2, float beta1, float beta2, const mg_stage_job* jobs, int n_jobs, int n_rows,
-                            const int64_t* order, long order_len, const uint64_t* base, mg_stream_t stream) {
-    MG_CHECK_ARG(adam_state && adam_state2 && adam_state != adam_state2, "mg_rng_fill_tick2_stage: two distinct adam states");
-    MG_CHECK_ARG(jobs && n_jobs > 0 && n_jobs <= MG_MAX_STAGE_JOBS && n_rows > 0 && order_len > 0 && base && step_counter,
-                 "mg_rng_fill_tick2_stage: need 1..%d jobs, rows, a positive order length, counter and base", MG_MAX_STAGE_JOBS);
-    StageRide sr{};
-    sr.n_jobs = n_jobs; sr.n_rows = n_rows; sr.order = order; sr.order_len = order_len;
-    sr.base = (const unsigned long long*)base;
-    for (int i = 0; i < n_jobs; ++i) {
-        const mg_stage_job& j = jobs[i];
-        MG_CHECK_ARG(j.src && j.dst && j.row_bytes > 0 && (j.row_bytes & 3) == 0 && j.src_rows > 0 && !j.idx && j.rows == 0 &&
-                         ((((uintptr_t)j.src | (uintptr_t)j.dst)) & 3) == 0 && (order || j.src_rows >= order_len),
-                     "mg_rng_fill_tick2_stage: job %d: the rules of mg_stage_rows_cursor", i);
-        MG_CHECK_ARG(j.dst_pitch == 0 || (j.dst_pitch >= j.row_bytes && (j.dst_pitch & 3) == 0),
-                     "mg_rng_fill_tick2_stage: job %d: dst_pitch must be 0 or a multiple of 4 that holds a row", i);
-        sr.J.j[i] = j;
-    }
-    return rng_fill_impl(normal, n_normal, uniform, n_uniform, mask0, n_mask0, mask1, n_mask1, p_drop, seed, step_counter,
-                         adam_state, adam_state2, beta1, beta2, stream, &sr);
-}
-
 int mg_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, double* state, float grad_scale, const float* gs_dev,
-                 mg_stream_t stream) {
+                 int state_ticked, uint64_t* rng_step, const mg_wq_entry* table, int n_table, mg_stream_t stream) {
     MG_CHECK_ARG(p && g && m && v && state && n > 0, "mg_adam_flat: bad args");
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, ST, state, (double)beta1, (double)beta2);
-    hipLaunchKernelGGL(adam_apply_kernel, dim3(nblk(n)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps,
-                       weight_decay, (const double*)state, grad_scale, gs_dev, (unsigned long long*)nullptr, WqTable{});
-    MG_CHECK_LAUNCH("adam_flat");
-    return MG_OK;
-}
-
-int mg_adam_flat_ticked(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                        float eps, float weight_decay, const double* state, float grad_scale, const float* gs_dev,
-                        uint64_t* rng_step, mg_stream_t stream) {
-    /* rng_step may be NULL: of the two updates one fused draw serves (mg_rng_fill_tick2) only one advances the counter */
-    MG_CHECK_ARG(p && g && m && v && state && n > 0, "mg_adam_flat_ticked: bad args");
-    hipLaunchKernelGGL(adam_apply_kernel, dim3(nblk(n)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps,
-                       weight_decay, state, grad_scale, gs_dev, (unsigned long long*)rng_step, WqTable{});
-    MG_CHECK_LAUNCH("adam_flat_ticked");
-    return MG_OK;
-}
-
-int mg_adam_flat_wq(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                    float eps, float weight_decay, double* state, float grad_scale, const float* gs_dev,
-                    int state_ticked, uint64_t* rng_step, const mg_wq_entry* table, int n_table, mg_stream_t stream) {
-    MG_CHECK_ARG(p && g && m && v && state && n > 0, "mg_adam_flat_wq: bad args");
-    MG_CHECK_ARG(n_table >= 0 && n_table <= MG_MAX_WQ_ENTRIES && (n_table == 0 || table), "mg_adam_flat_wq: bad table");
+    MG_CHECK_ARG(n_table >= 0 && n_table <= MG_MAX_WQ_ENTRIES && (n_table == 0 || table), "mg_adam_flat: bad table");
     WqTable t{};
     t.n = n_table;
     t.lo = n; t.hi = 0;
@@ -2072,7 +1933,7 @@ int mg_adam_flat_wq(float* p, const float* g, float* m, float* v, long n, float 
         const long cnt = (long)e.N * e.Cc * e.K;
         MG_CHECK_ARG(e.dst && e.N > 0 && e.Cc > 0 && e.Cc % 4 == 0 && e.K > 0 && e.start >= 0 && e.start + cnt <= n &&
                      ((e.w_sc == e.K && e.w_sn == e.Cc * e.K) || (e.w_sn == e.K && e.w_sc == e.N * e.K)),
-                     "mg_adam_flat_wq: table entry %d is not a dense (N,C,K) or (C,N,K) tensor inside the flat buffer", i);
+                     "mg_adam_flat: table entry %d is not a dense (N,C,K) or (C,N,K) tensor inside the flat buffer", i);
         t.e[i] = e;
         if (e.start < t.lo) t.lo = e.start;
         if (e.start + cnt > t.hi) t.hi = e.start + cnt;
@@ -2081,7 +1942,7 @@ int mg_adam_flat_wq(float* p, const float* g, float* m, float* v, long n, float 
         hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, ST, state, (double)beta1, (double)beta2);
     hipLaunchKernelGGL(adam_apply_kernel, dim3(nblk(n)), dim3(256), 0, ST, p, g, m, v, n, lr, beta1, beta2, eps,
                        weight_decay, (const double*)state, grad_scale, gs_dev, (unsigned long long*)rng_step, t);
-    MG_CHECK_LAUNCH("adam_flat_wq");
+    MG_CHECK_LAUNCH("adam_flat");
     return MG_OK;
 }
 

@@ -231,7 +231,7 @@ class EdEngine:
 
     def draw_masks(self):
         """Production path: one Philox launch draws both keep-masks (scaled) and advances the AdamW state; the
-        update advances the Philox counter (mg_rng_fill_tick / mg_adam_flat_ticked)."""
+        update advances the Philox counter (mg_rng_fill's adam_state rider / mg_adam_flat with state_ticked)."""
         ops.rng_fill(None, None, self.dmask[0], self.dmask[1] if len(self.dmask) > 1 else None, self.p_drop,
                      self.rng_seed, self.rng_step, tick_state=self.P.state, betas=self.betas)
         self.P.ticked = True

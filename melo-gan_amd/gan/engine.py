@@ -353,7 +353,7 @@ class GanEngine:
     # -------------------------------------------------------------------------------------
     def _init_wq(self):
         """One WQ copy per (stride-2 convolution, direction it is used in) whose channel counts conv16 covers
-        (reduction channels % 16, output columns % 32): written by the optimiser step itself (mg_adam_flat_wq) and by
+        (reduction channels % 16, output columns % 32): written by the optimiser step itself (mg_adam_flat's table) and by
         params_changed() after parameters were written from outside."""
         self.wq, self._wq_src = {}, []
         ent = {"D": [], "GE": []}
@@ -619,7 +619,7 @@ class GanEngine:
         """Production path: one Philox launch fills noise, alpha and both dropout masks (draw order of the
         reference per sub-step: dropout masks, randn noise, rand alpha -- SURVEY section 3).  The same launch advances
         the Adam state of the optimiser this sub-step ends with (critic when alpha is drawn, generator otherwise), and
-        that update advances the Philox step counter: no tick launches (see mg_rng_fill_tick)."""
+        that update advances the Philox step counter: no tick launches (see mg_rng_fill's adam_state rider)."""
         fp = self.D if with_alpha else self.GE
         if with_alpha:
             self._stage_bound()                   # a bound split: the batch's first sub-step stages it (bind_batches)

@@ -305,7 +305,7 @@ def conv16_poolable(B: int, Tin: int, Cin: int, N: int) -> bool:
 
 
 def conv16_pool(x: Tensor, wq: Tensor, y: Tensor, N: int, pool: Tensor, scale: float, **epi) -> Tensor:
-    """conv16 (gather form) that also writes pool[b][n] = scale * sum_t y[b][t][n] (mg_conv16_pool)."""
+    """conv16 (gather form) that also writes pool[b][n] = scale * sum_t y[b][t][n] (mg_conv16's pool rider)."""
     return conv16(x, wq, y, N, False, pool=(pool, scale), **epi)
 
 
@@ -322,7 +322,7 @@ def _conv16_plan(B, Tin, N, transposed):
 
 def conv16(x: Tensor, wq: Tensor, y: Tensor, N: int, transposed: bool, odd: bool = False, stats=None, pool=None,
            perm: bool = False, mix=None, bnb=None, **epi) -> Tensor:
-    """Stride-2 K=5 window GEMM on 16x16 MFMA tiles with WQ-layout weights (mg_conv16_ex).  transposed=False: the gather
+    """Stride-2 K=5 window GEMM on 16x16 MFMA tiles with WQ-layout weights (mg_conv16).  transposed=False: the gather
     form (Conv1d forward / ConvTranspose1d data-gradient), True: the scatter form (ConvTranspose1d forward / Conv1d
     data-gradient; odd: Tout = 2*Tin - 1).  y: (B, Ty >= Tout, N).  Riders of the same launch:
       stats: a float buffer that receives per-column partial statistics (sum, centred sum of squares, count) of the stored
@@ -394,8 +394,8 @@ def conv16(x: Tensor, wq: Tensor, y: Tensor, N: int, transposed: bool, odd: bool
         ex.mix_real, ex.mix_alpha, ex.mix_out, ex.mix_rows = _p(real), _p(alpha), _p(out), int(rows)
 
     def launch():
-        return lib.mg_conv16_ex(_p(x), _p(wq), _p(y), B, Tin, Cin, N, 1 if transposed else 0, Tout, Tin * Cin, Ty * N, C.byref(e),
-                                C.byref(ex), _stream())
+        return lib.mg_conv16(_p(x), _p(wq), _p(y), B, Tin, Cin, N, 1 if transposed else 0, Tout, Tin * Cin, Ty * N, C.byref(e),
+                             C.byref(ex), _stream())
     rid = "true" if (stats is not None or pool is not None or perm or mix is not None or bnb is not None) else "false"
     sym = lambda: "conv16_kernel<%s,%d,%s>" % ("true" if transposed else "false", _conv16_plan(B, Tin, N, transposed)[2] // 32, rid)  # noqa: E731
     with _observe(sym, 2.0 * B * (Tin if transposed else Tout) * N * Cin * 5, launch):
@@ -408,7 +408,7 @@ SKINNY_MAX_ROWS = 512      # Linear layers with at most this many rows use the s
 
 
 def linear_route(M: int, K: int, N: int, w_sn: int, w_sc: int, perm_L: int = 0, x_aligned: bool = True, w_aligned: bool = True):
-    """(symbol, ksplit) of the launch mg_linear_perm makes (mg_linear_route): the window GEMM a permuted forward with many
+    """(symbol, ksplit) of the launch mg_linear makes (mg_linear_route): the window GEMM a permuted forward with many
     rows is routed to, or linear_skinny_kernel<W_KCONTIG,VEC>; ksplit > 1: linear_finish_kernel follows.  x_aligned /
     w_aligned: the tensor starts on a 16-byte boundary.  Host only; reads MG_LINEAR_SKINNY_ONLY / MG_FORCE_TILE as the launch
     does."""
@@ -430,15 +430,15 @@ def _linear(x, w, y, K, N, w_sn, w_sc, epi, perm_L=0):
     work = workspace(need, x.device, "linear") if need else None
     sym = lambda: linear_route(M, K, N, w_sn, w_sc, perm_L, x.data_ptr() % 16 == 0, w.data_ptr() % 16 == 0)[0]  # noqa: E731
     with _observe(sym, 2.0 * M * N * K):
-        rc = lib.mg_linear_perm(_p(x), _p(w), _p(y), M, K, N, w_sn, w_sc, C.byref(e), perm_L, _p(work),
-                                work.numel() if work is not None else 0, _stream())
+        rc = lib.mg_linear(_p(x), _p(w), _p(y), M, K, N, w_sn, w_sc, C.byref(e), perm_L, _p(work),
+                           work.numel() if work is not None else 0, _stream())
     L.check(rc, "mg_linear")
     return y
 
 
 def linear_fwd(x, w, y, perm_L: int = 0, **epi):
     """nn.Linear forward; x: (B, in), w: (out, in), y: (B, out).  perm_L > 0: y is (B, perm_L, out / perm_L) -- the
-    channels-last tensor behind the reference's view(B, C, L) + permute (mg_linear_perm); elementwise epilogue tensors are
+    channels-last tensor behind the reference's view(B, C, L) + permute (mg_linear's perm_L); elementwise epilogue tensors are
     laid out like y."""
     _chk(x, "x")
     _chk(w, "w")
@@ -964,10 +964,10 @@ def bn_train_fwd(z, a, gamma, beta, running_mean, running_var, save_mean, save_i
         _chk(running_mean, "running_mean", (Cc,))
         _chk(running_var, "running_var", (Cc,))
     lib = L.load()
-    work = workspace(lib.mg_bn_groups_workspace_bytes(Cc, groups), z.device, "bn")
-    L.check(lib.mg_bn_train_fwd_groups(_p(z), _p(a), R // groups, Cc, groups, _p(gamma), _p(beta), _p(running_mean),
-                                       _p(running_var), momentum, eps, _p(save_mean), _p(save_invstd), act, _p(work),
-                                       work.numel(), _stream()), "mg_bn_train_fwd")
+    work = workspace(lib.mg_bn_workspace_bytes(Cc, groups), z.device, "bn")
+    L.check(lib.mg_bn_train_fwd(_p(z), _p(a), R // groups, Cc, groups, _p(gamma), _p(beta), _p(running_mean),
+                                _p(running_var), momentum, eps, _p(save_mean), _p(save_invstd), act, _p(work),
+                                work.numel(), _stream()), "mg_bn_train_fwd")
     return a
 
 
@@ -1007,7 +1007,7 @@ def bn_train_bwd(da, a, z, dz, gamma, save_mean, save_invstd, dgamma, dbeta, act
                   ("dbeta", dbeta)):
         _chk(v, nm, (Cc,))
     lib = L.load()
-    work = workspace(lib.mg_bn_workspace_bytes(Cc), z.device, "bn")
+    work = workspace(lib.mg_bn_workspace_bytes(Cc, 1), z.device, "bn")
     if beta is not None:
         _chk(beta, "beta", (Cc,))
     L.check(lib.mg_bn_train_bwd(_p(da), _p(a), _p(z), _p(dz), R, Cc, _p(gamma), _p(beta), _p(save_mean), _p(save_invstd),
@@ -1064,7 +1064,7 @@ def meanT_fwd(a, h):
 
 
 def meanT_bwd(dh, dz, gref=None, gact=ACT_NONE, gscale=None, mean=None):
-    """mean = (src, out, scale): out[0] = scale * mean(src) rides in the same launch (mg_meanT_bwd_mean)."""
+    """mean = (src, out, scale): out[0] = scale * mean(src) rides in the same launch."""
     _chk(dz, "dz")
     B, T, Cc = dz.shape
     _chk(dh, "dh", (B, Cc))
@@ -1081,8 +1081,8 @@ def meanT_bwd(dh, dz, gref=None, gact=ACT_NONE, gscale=None, mean=None):
         mn = msrc.numel()
         if mn < 1 or mout.numel() < 1:
             raise ValueError("meanT_bwd: empty mean rider")
-    L.check(L.load().mg_meanT_bwd_mean(_p(dh), _p(dz), B, T, Cc, _p(gref), gact, _p(gscale), _p(msrc), _p(mout), mn, float(msc),
-                                       _stream()), "mg_meanT_bwd")
+    L.check(L.load().mg_meanT_bwd(_p(dh), _p(dz), B, T, Cc, _p(gref), gact, _p(gscale), _p(msrc), _p(mout), mn, float(msc),
+                                  _stream()), "mg_meanT_bwd")
     return dz
 
 
@@ -1165,7 +1165,8 @@ def dhead_bwd(ds, f, w, dU, demb=None, nb_emb=0):
 
 
 def dhead_wgrad(ds, f, emb, gf, dw, dbias, nb, ng, loss=None):
-    """loss = (s, norms, lambda_gp, out, gp_out, nb): the critic's loss scalars (wgan_d_loss with norms) ride in the same launch."""
+    """loss = (s, norms, lambda_gp, out, gp_out, nb): the critic's loss scalars out = {loss_d, mean_real, mean_fake} and
+    gp_out = mean((norms - 1)^2) ride in the same launch."""
     _chk(f, "f")
     F = f.shape[1]
     Be, E = (emb.shape if emb is not None else (0, 0))
@@ -1184,8 +1185,8 @@ def dhead_wgrad(ds, f, emb, gf, dw, dbias, nb, ng, loss=None):
         _chk(lg, "gp_out")
         if ls.numel() < 2 * lnb or lo.numel() < 3 or lnb < 1:
             raise ValueError("dhead_wgrad: loss rider sizes")
-    L.check(L.load().mg_dhead_wgrad_loss(_p(ds), _p(f), _p(emb), _p(gf), _p(dw), _p(dbias), nb, ng if gf is not None else 0,
-                                         Be, F, E, _p(ls), _p(ln), float(lam), _p(lo), _p(lg), lnb, _stream()), "mg_dhead_wgrad")
+    L.check(L.load().mg_dhead_wgrad(_p(ds), _p(f), _p(emb), _p(gf), _p(dw), _p(dbias), nb, ng if gf is not None else 0,
+                                    Be, F, E, _p(ls), _p(ln), float(lam), _p(lo), _p(lg), lnb, _stream()), "mg_dhead_wgrad")
 
 
 def gp_interp(real, fake, alpha, xhat):
@@ -1207,23 +1208,10 @@ def gp_penalty(g, gbar, norms, gp, coef):
     if gbar is not None:
         _chk(gbar, "gbar", g.shape)
     _chk(norms, "norms", (B,))
-    if gp is not None:           # None: the mean is left to wgan_d_loss(..., norms=...)
+    if gp is not None:           # None: the mean is left to dhead_wgrad(loss=...)
         _chk(gp, "gp")
     L.check(L.load().mg_gp_penalty(_p(g), _p(gbar), _p(norms), _p(gp), coef, B, g.numel() // B, _stream()),
             "mg_gp_penalty")
-
-
-def wgan_d_loss(s, gp, lambda_gp, out, nb, norms=None):
-    """out = {loss_d, mean_real, mean_fake}.  With `norms` (per-sample gradient norms) the penalty mean((norm-1)^2) is
-    computed here and written to gp; otherwise gp is read."""
-    _chk(s, "s")
-    if s.numel() < 2 * nb or out.numel() < 3:
-        raise ValueError("wgan_d_loss: sizes")
-    if norms is not None:
-        _chk(norms, "norms", (nb,))
-        L.check(L.load().mg_wgan_d_loss_gp(_p(s), _p(norms), lambda_gp, _p(out), _p(gp), nb, _stream()), "mg_wgan_d_loss_gp")
-        return
-    L.check(L.load().mg_wgan_d_loss(_p(s), _p(gp), lambda_gp, _p(out), nb, _stream()), "mg_wgan_d_loss")
 
 
 def softmax_ce(logits, target, loss, dlogits, coef=1.0):
@@ -1236,19 +1224,9 @@ def softmax_ce(logits, target, loss, dlogits, coef=1.0):
             "mg_softmax_ce")
 
 
-def neg_mean(s, out):
-    _chk(s, "s")
-    L.check(L.load().mg_neg_mean(_p(s), _p(out), s.numel(), _stream()), "mg_neg_mean")
-
-
 # ---------------------------------------------------------------------------------------
 # elementwise / optimiser
 # ---------------------------------------------------------------------------------------
-def fill(x, v):
-    _chk(x, "x")
-    L.check(L.load().mg_fill(_p(x), v, x.numel(), _stream()), "mg_fill")
-
-
 def axpby(x, y, a=1.0, b=0.0):
     _chk(x, "x")
     _chk(y, "y")
@@ -1306,17 +1284,22 @@ def stage_rows_cursor(jobs, n_rows, order, order_len, counter, base):
     """stage_rows with the source rows picked on the device (mg_stage_rows_cursor): for every (src, dst) in `jobs`,
     dst[r] = src[order[p]] (order None: src[p]) with p = ((counter - base) * n_rows + r) % order_len.  counter / base: int64
     device scalars (1,)."""
-    if not 0 < len(jobs) <= L.MAX_STAGE_JOBS:
-        raise ValueError(f"stage_rows_cursor: 1..{L.MAX_STAGE_JOBS} jobs")
     _chk(counter, "counter", (1,), torch.int64)
+    _cursor_check("stage_rows_cursor", jobs, order, order_len, base)
+    arr = _cursor_jobs(jobs, n_rows, order, order_len)
+    L.check(L.load().mg_stage_rows_cursor(arr, len(jobs), n_rows, _p(order), int(order_len), _p(counter), _p(base), _stream()),
+            "mg_stage_rows_cursor")
+
+
+def _cursor_check(who, jobs, order, order_len, base):
+    """What stage_rows_cursor and rng_fill(stage=...) ask of a cursor's arguments: the job-count limit, base, order."""
+    if not 0 < len(jobs) <= L.MAX_STAGE_JOBS:
+        raise ValueError(f"{who}: 1..{L.MAX_STAGE_JOBS} jobs")
     _chk(base, "base", (1,), torch.int64)
     if order is not None:
         _chk(order, "order", dtype=torch.int64)
         if order.numel() < order_len:
-            raise ValueError("stage_rows_cursor: order shorter than order_len")
-    arr = _cursor_jobs(jobs, n_rows, order, order_len)
-    L.check(L.load().mg_stage_rows_cursor(arr, len(jobs), n_rows, _p(order), int(order_len), _p(counter), _p(base), _stream()),
-            "mg_stage_rows_cursor")
+            raise ValueError(f"{who}: order shorter than order_len")
 
 
 def _cursor_jobs(jobs, n_rows, order, order_len):
@@ -1616,7 +1599,9 @@ def act_bwd(dy, dx, gref=None, gact=ACT_NONE, emul=None):
 def rng_fill(normal, uniform, mask0, mask1, p_drop, seed, step_counter, tick_state=None, betas=None, tick_state2=None, stage=None):
     """normal ~ N(0,1), uniform ~ U(0,1), mask* = keep-mask/(1-p_drop); any of them may be None.  Plain: draw, then
     advance step_counter (two launches).  With tick_state (an optimiser's Adam state) and betas: ONE launch that
-    draws and advances that Adam state instead; adam_flat(..., ticked_rng_step=step_counter) later advances the counter."""
+    draws and advances that Adam state instead; adam_flat(..., ticked_rng_step=step_counter) later advances the counter.
+    tick_state2: a second Adam state advanced by the same draw (one draw in front of two updates).  stage = (jobs, n_rows,
+    order, order_len, base): stage_rows_cursor with counter = step_counter rides in the same launch (needs both states)."""
     for t in (normal, uniform, mask0, mask1):
         if t is not None:
             _chk(t, "rng tensor")
@@ -1624,37 +1609,19 @@ def rng_fill(normal, uniform, mask0, mask1, p_drop, seed, step_counter, tick_sta
     n = lambda t: 0 if t is None else t.numel()  # noqa: E731
     if stage is not None and tick_state2 is None:
         raise ValueError("rng_fill(stage=...): only with the fused draw (tick_state and tick_state2)")
-    if tick_state2 is not None:          # one draw in front of two updates: both Adam states advance here
+    if tick_state is not None or tick_state2 is not None:
         _chk(tick_state, "tick_state", (4,), torch.float64)
+    if tick_state2 is not None:
         _chk(tick_state2, "tick_state2", (4,), torch.float64)
-        if stage is not None:
-            # stage = (jobs, n_rows, order, order_len, base): stage_rows_cursor with counter = step_counter, riding in this launch
-            jobs, n_rows, order, order_len, base = stage
-            if not 0 < len(jobs) <= L.MAX_STAGE_JOBS:
-                raise ValueError(f"rng_fill(stage=...): 1..{L.MAX_STAGE_JOBS} jobs")
-            _chk(base, "base", (1,), torch.int64)
-            if order is not None:
-                _chk(order, "order", dtype=torch.int64)
-                if order.numel() < order_len:
-                    raise ValueError("rng_fill(stage=...): order shorter than order_len")
-            arr = _cursor_jobs(jobs, n_rows, order, order_len)
-            L.check(L.load().mg_rng_fill_tick2_stage(_p(normal), n(normal), _p(uniform), n(uniform), _p(mask0), n(mask0), _p(mask1),
-                                                     n(mask1), p_drop, seed & 0xFFFFFFFFFFFFFFFF, _p(step_counter), _p(tick_state),
-                                                     _p(tick_state2), betas[0], betas[1], arr, len(jobs), n_rows, _p(order),
-                                                     int(order_len), _p(base), _stream()), "mg_rng_fill_tick2_stage")
-            return
-        L.check(L.load().mg_rng_fill_tick2(_p(normal), n(normal), _p(uniform), n(uniform), _p(mask0), n(mask0), _p(mask1),
-                                           n(mask1), p_drop, seed & 0xFFFFFFFFFFFFFFFF, _p(step_counter), _p(tick_state),
-                                           _p(tick_state2), betas[0], betas[1], _stream()), "mg_rng_fill_tick2")
-        return
-    if tick_state is not None:
-        _chk(tick_state, "tick_state", (4,), torch.float64)
-        L.check(L.load().mg_rng_fill_tick(_p(normal), n(normal), _p(uniform), n(uniform), _p(mask0), n(mask0), _p(mask1),
-                                          n(mask1), p_drop, seed & 0xFFFFFFFFFFFFFFFF, _p(step_counter), _p(tick_state),
-                                          betas[0], betas[1], _stream()), "mg_rng_fill_tick")
-        return
-    L.check(L.load().mg_rng_fill(_p(normal), n(normal), _p(uniform), n(uniform), _p(mask0), n(mask0), _p(mask1),
-                                 n(mask1), p_drop, seed & 0xFFFFFFFFFFFFFFFF, _p(step_counter), _stream()), "mg_rng_fill")
+    arr, n_jobs, n_rows, order, order_len, base = None, 0, 0, None, 0, None
+    if stage is not None:
+        jobs, n_rows, order, order_len, base = stage
+        _cursor_check("rng_fill(stage=...)", jobs, order, order_len, base)
+        arr, n_jobs = _cursor_jobs(jobs, n_rows, order, order_len), len(jobs)
+    b1, b2 = betas if tick_state is not None else (0.0, 0.0)
+    L.check(L.load().mg_rng_fill(_p(normal), n(normal), _p(uniform), n(uniform), _p(mask0), n(mask0), _p(mask1), n(mask1), p_drop,
+                                 seed & 0xFFFFFFFFFFFFFFFF, _p(step_counter), _p(tick_state), _p(tick_state2), b1, b2, arr, n_jobs,
+                                 n_rows, _p(order), int(order_len), _p(base), _stream()), "mg_rng_fill")
 
 
 def gen_inputs(emotion, sample, noise, numeric, table, jitter, latent, seed):
@@ -1830,21 +1797,12 @@ def adam_flat(p, g, m, v, state, lr, beta1, beta2, eps=1e-8, weight_decay=0.0, g
         if t.numel() != n:
             raise ValueError("adam_flat: size mismatch")
     _chk(state, "state", (4,), torch.float64)
-    if wq is not None:             # the update also refreshes WQ-layout weight copies (wq_table)
-        if ticked_rng_step is not None:
-            _chk(ticked_rng_step, "ticked_rng_step", (1,), torch.int64)
-        L.check(L.load().mg_adam_flat_wq(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, _p(state),
-                                         grad_scale, _p(gs_dev), 1 if (ticked or ticked_rng_step is not None) else 0,
-                                         _p(ticked_rng_step), wq[0], wq[1], _stream()), "mg_adam_flat_wq")
-        return
-    if ticked_rng_step is not None or ticked:
-        if ticked_rng_step is not None:
-            _chk(ticked_rng_step, "ticked_rng_step", (1,), torch.int64)
-        L.check(L.load().mg_adam_flat_ticked(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, _p(state),
-                                             grad_scale, _p(gs_dev), _p(ticked_rng_step), _stream()), "mg_adam_flat_ticked")
-        return
-    L.check(L.load().mg_adam_flat(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, _p(state),
-                                  grad_scale, _p(gs_dev), _stream()), "mg_adam_flat")
+    if ticked_rng_step is not None:
+        _chk(ticked_rng_step, "ticked_rng_step", (1,), torch.int64)
+    table, n_table = (wq[0], wq[1]) if wq is not None else (None, 0)     # wq_table: WQ-layout weight copies the update refreshes
+    L.check(L.load().mg_adam_flat(_p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, weight_decay, _p(state), grad_scale,
+                                  _p(gs_dev), 1 if (ticked or ticked_rng_step is not None) else 0, _p(ticked_rng_step), table,
+                                  n_table, _stream()), "mg_adam_flat")
 
 
 def grad_norm_clip(g, max_norm, out):
@@ -1920,7 +1878,7 @@ class Graph:
         L.check(L.load().mg_graph_begin(_stream()), "mg_graph_begin")
 
     def end(self):
-        L.check(L.load().mg_graph_end_n(_stream(), self.handles, self.n), "mg_graph_end_n")
+        L.check(L.load().mg_graph_end(_stream(), self.handles, self.n), "mg_graph_end")
         self.kernel_nodes = L.load().mg_graph_last_kernel_nodes()      # launches one replay stands for
 
     def launch(self):

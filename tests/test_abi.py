@@ -68,6 +68,42 @@ def test_lds_pad_outside_its_range_is_rejected_on_the_host():
         assert lib.mg_conv1d_wino3(x, w, y, 4, 256, 64, 128, None, pad, None) == -1 and b"lds_pad" in lib.mg_last_error(), pad
 
 
+def test_riders_are_checked_by_their_family_entry_point():
+    """Every kernel family has ONE entry point whose riders are nullable arguments; the rules between riders are checked
+    there, before any launch (non-null dummy addresses; nothing here launches)."""
+    import ctypes as C
+    import melo_gan_amd  # noqa: F401
+    from melo_gan_amd import _lib
+    lib = _lib.load()
+    x, w, y, q, r = 256, 512, 1024, 2048, 4096
+    # mg_conv16: no extra and null tensors; the temporal mean of an accumulating launch
+    assert lib.mg_conv16(None, None, None, 4, 64, 64, 128, 0, 0, 0, 0, None, None, None) == -1 and b"null" in lib.mg_last_error()
+    epi, ex = _lib.Epilogue(), _lib.Conv16Extra()
+    epi.accumulate, ex.pool, ex.pool_scale = 1, q, 1.0
+    assert lib.mg_conv16_poolable(4, 64, 64, 128)
+    rc = lib.mg_conv16(x, w, y, 4, 64, 64, 128, 0, 0, 0, 0, C.byref(epi), C.byref(ex), None)
+    assert rc == -1 and b"mean of an accumulating" in lib.mg_last_error()
+    # mg_rng_fill: a second Adam state without / equal to the first; staging jobs without both states
+    draw = (x, 16, None, 0, None, 0, None, 0, 0.0, 1, w)
+    tail = (None, 0, 0, None, 0, None, None)
+    assert lib.mg_rng_fill(*draw, None, q, 0.9, 0.99, *tail) == -1 and b"adam_state" in lib.mg_last_error()
+    assert lib.mg_rng_fill(*draw, q, q, 0.9, 0.99, *tail) == -1 and b"adam_state" in lib.mg_last_error()
+    st = (_lib.StageJob * 1)()
+    st[0].src, st[0].dst, st[0].row_bytes, st[0].src_rows = 256, 512, 16, 16
+    for states in ((None, None), (q, None)):
+        assert lib.mg_rng_fill(*draw, *states, 0.9, 0.99, st, 1, 8, None, 16, r, None) == -1, states
+        assert b"both adam states" in lib.mg_last_error(), states
+    # mg_adam_flat: a WQ table that is missing or too long
+    adam = (x, w, y, q, 64, 1e-3, 0.9, 0.99, 1e-8, 0.0, r, 1.0, None, 0, None)
+    assert lib.mg_adam_flat(*adam, None, 1, None) == -1 and b"table" in lib.mg_last_error()
+    tab = (_lib.WqEntry * (_lib.MAX_WQ_ENTRIES + 1))()
+    assert lib.mg_adam_flat(*adam, tab, _lib.MAX_WQ_ENTRIES + 1, None) == -1 and b"table" in lib.mg_last_error()
+    # mg_graph_end: 1..8 executables
+    out = (C.c_void_p * 9)()
+    for n in (0, 9):
+        assert lib.mg_graph_end(None, out, n) == -1 and b"1..8" in lib.mg_last_error(), n
+
+
 def test_ops_refuse_cpu_tensors():
     import pytest
     import torch

@@ -132,7 +132,7 @@ def test_batchnorm_from_the_convolutions_partial_statistics(ops, B, L, Cin, Cout
 
 @pytest.mark.parametrize("B,Tin,Cin,N", [(192, 64, 128, 256), (64, 64, 128, 256), (3, 64, 32, 64), (5, 63, 64, 96)])
 def test_conv16_pool_is_the_temporal_mean_of_the_output(B, Tin, Cin, N):
-    """mg_conv16_pool: AdaptiveAvgPool1d(1) of the activated output from the convolution's own launch (critic conv.4 ->
+    """mg_conv16's pool rider: AdaptiveAvgPool1d(1) of the activated output from the convolution's own launch (critic conv.4 ->
     pooling, src/gan/models.py:141-148) equals the mean over time of what the launch stored, for full and ragged batch
     tiles, with the bias + LeakyReLU and the tangent-pass epilogues; shapes that do not qualify are refused."""
     import melo_gan_amd  # noqa: F401
@@ -231,7 +231,7 @@ def test_gradient_penalty_interpolate_rides_in_the_producing_launch(ops):
 
 @pytest.mark.parametrize("M,K,Cc,Lp", [(128, 512, 256, 32), (64, 512, 256, 32), (3, 40, 8, 4)])
 def test_linear_with_permuted_output_columns(ops, M, K, Cc, Lp):
-    """mg_linear_perm: the Linear output lands as (M, L, C) = view(M, C, L).permute(0, 2, 1) of the reference order
+    """mg_linear with perm_L: the Linear output lands as (M, L, C) = view(M, C, L).permute(0, 2, 1) of the reference order
     (src/gan/models.py:70-73), bias and activation included, elementwise operands in the stored order."""
     g = torch.Generator().manual_seed(M)
     N = Cc * Lp

@@ -18,7 +18,7 @@ from oracle import melo_oracle as O  # noqa: E402
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["ed_latent_d64_b8", "ed_latent_d8_b5", "ed_latent_d32_h3_b7"]
 OPT = dict(name="AdamW", lr=2e-4, betas=[0.5, 0.999], weight_decay=0.01)
-TICKED_ONCE = [1.0, 0.5, float(np.float32(0.999))]      # the betas are float arguments of the launch, as mg_rng_fill_tick's
+TICKED_ONCE = [1.0, 0.5, float(np.float32(0.999))]      # the betas are float arguments of the launch, as mg_rng_fill's
 
 
 def rel_err(a, b):

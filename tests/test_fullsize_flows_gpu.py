@@ -1,7 +1,7 @@
 """The flows that bench.py and the trainers actually replay, at the sizes that are benchmarked, against the oracle.
 
  * cfg2 (B=64, T=256, C=128): the production sequence of `dg_step_rng` -- ONE 2B-row generator pass
-   (`mg_bn_train_fwd_groups` / conv16 statistics epilogue at 128 rows, conv.4 with the fused temporal mean, the 3B-row
+   (`mg_bn_train_fwd` with groups / conv16 statistics epilogue at 128 rows, conv.4 with the fused temporal mean, the 3B-row
    tile plans) + critic step + generator step -- with injected randoms: teacher-forced at the critic update (every
    quantity judged from identical inputs), and the forked side-stream flow free-running (the engine's own critic update
    feeds its generator step) against the oracle's two consecutive sub-steps.

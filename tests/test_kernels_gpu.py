@@ -336,34 +336,60 @@ def test_rng_fill(ops):
 
 def test_tick_free_draw_and_update_match_the_plain_pair(ops):
     """rng_fill(tick_state=...) + adam_flat(ticked_rng_step=...) (one launch each) == rng_fill + adam_flat (two each):
-    same draws for the same (seed, step), same Adam state and parameters after the update, counter advanced once."""
+    same draws for the same (seed, step), same Adam state and parameters after the update, counter advanced once.  The
+    same holds for every other rider of the two entry points: the two-state draw (both Adam states advance once per step),
+    the two-state draw that also stages a batch (the rows equal stage_rows_cursor's), and an update with an empty WQ
+    table (bit-equal to the plain update)."""
     n = 4096 + 3
     torch.manual_seed(0)
     p0, g = torch.randn(n, device="cuda"), torch.randn(n, device="cuda")
     betas = (0.5, 0.9)
+    src = torch.arange(16 * 4, dtype=torch.float32, device="cuda").reshape(16, 4)      # the staged split: 16 rows of 4 floats
+    base = torch.zeros(1, dtype=torch.int64, device="cuda")
 
-    def run(ticked, steps=3):
+    def run(mode, steps=3):
         p, m, v = p0.clone(), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
         state = torch.zeros(4, dtype=torch.float64, device="cuda")
+        state2 = torch.zeros(4, dtype=torch.float64, device="cuda")
         ctr = torch.zeros(1, dtype=torch.int64, device="cuda")
-        draws = []
+        draws, staged = [], []
         for _ in range(steps):
             x = torch.empty(1001, device="cuda")
-            if ticked:
-                ops.rng_fill(x, None, None, None, 0.2, 99, ctr, tick_state=state, betas=betas)
-                ops.adam_flat(p, g, m, v, state, 1e-3, *betas, ticked_rng_step=ctr)
-            else:
+            if mode == "plain":
                 ops.rng_fill(x, None, None, None, 0.2, 99, ctr)
                 ops.adam_flat(p, g, m, v, state, 1e-3, *betas)
+            elif mode == "empty_wq":
+                ops.rng_fill(x, None, None, None, 0.2, 99, ctr)
+                ops.adam_flat(p, g, m, v, state, 1e-3, *betas, wq=ops.wq_table([]))
+            else:
+                stage = None
+                if mode == "two_states_staged":
+                    want, got = torch.full((8, 4), -1.0, device="cuda"), torch.full((8, 4), -2.0, device="cuda")
+                    ops.stage_rows_cursor([(src, want)], 8, None, 16, ctr, base)
+                    stage = ([(src, got)], 8, None, 16, base)
+                    staged.append((want, got))
+                ops.rng_fill(x, None, None, None, 0.2, 99, ctr, tick_state=state, betas=betas,
+                             tick_state2=None if mode == "ticked" else state2, stage=stage)
+                ops.adam_flat(p, g, m, v, state, 1e-3, *betas, ticked_rng_step=ctr)
             draws.append(x)
-        return p, m, v, state, ctr, draws
+        return p, m, v, state, ctr, draws, state2, staged
 
-    a, b = run(False), run(True)
-    for x, y in zip(a[:5], b[:5]):
-        assert torch.equal(x, y)
-    for x, y in zip(a[5], b[5]):
-        assert torch.equal(x, y)
-    assert int(b[4].item()) == 3 and float(b[3][0].item()) == 3.0
+    a = run("plain")
+    for mode in ("ticked", "two_states", "two_states_staged", "empty_wq"):
+        b = run(mode)
+        for x, y in zip(a[:5], b[:5]):
+            assert torch.equal(x, y), mode
+        for x, y in zip(a[5], b[5]):
+            assert torch.equal(x, y), mode
+        assert int(b[4].item()) == 3 and float(b[3][0].item()) == 3.0, mode
+        if mode.startswith("two_states"):
+            assert torch.equal(b[6], b[3]), mode                       # the second state advanced once per step, like the first
+        else:
+            assert not b[6].any(), mode
+        assert len(b[7]) == (3 if mode == "two_states_staged" else 0)
+        for step, (want, got) in enumerate(b[7]):
+            assert torch.equal(got, want), (mode, step)
+            assert torch.equal(got, src[[(step * 8 + r) % 16 for r in range(8)]]), (mode, step)
 
 
 def test_wgrad_multi_equals_separate_launches():

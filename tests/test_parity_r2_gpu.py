@@ -3,8 +3,8 @@
   * FREE-RUNNING trajectories: the engine runs the fixtures' 2-3 (critic + generator) steps on its own state -- no
     re-synchronisation with the oracle between sub-steps -- and is compared with what the REFERENCE recorded for the same
     injected randoms (tests/golden/make_golden.py::gan_case): per-step losses and the end-of-run state checksums;
-  * the production optimiser path (flat buffers, Adam state advanced by the Philox draw = mg_rng_fill_tick +
-    mg_adam_flat_ticked, grad_scale = 1/world) against torch.optim.Adam / AdamW element by element;
+  * the production optimiser path (flat buffers, Adam state advanced by the Philox draw = mg_rng_fill's adam_state
+    rider + mg_adam_flat with state_ticked, grad_scale = 1/world) against torch.optim.Adam / AdamW element by element;
   * batch-1 eval generation (BASELINE config 5, app.py:92-119) against reference fixtures, through the MIDI contract.
 """
 import os
@@ -141,7 +141,7 @@ def test_free_running_trajectory_matches_reference(name):
 @pytest.mark.parametrize("world", [1, 8])
 @pytest.mark.parametrize("decoupled_wd", [0.0, 0.01])
 def test_production_optimiser_path_elementwise(world, decoupled_wd):
-    """The flat, ticked update (mg_rng_fill_tick advances the Adam state, mg_adam_flat_ticked applies it) with the
+    """The flat, ticked update (mg_rng_fill's adam_state rider advances the Adam state, mg_adam_flat with state_ticked applies it) with the
     data-parallel 1/world factor against torch.optim.Adam / AdamW on the averaged gradient, element by element."""
     import melo_gan_amd  # noqa: F401
     from melo_gan_amd import ops

@@ -55,7 +55,7 @@ def gather_s1(x, w, K, flip=False):
 
 
 def perm_index(N, perm_L, device="cpu"):
-    """Weight row behind output column n' of mg_linear_perm: (n' % C) * L + n' // C, C = N / L (identity for perm_L <= 1)."""
+    """Weight row behind output column n' of mg_linear with perm_L: (n' % C) * L + n' // C, C = N / L (identity for perm_L <= 1)."""
     n = torch.arange(N, device=device)
     if perm_L <= 1:
         return n
@@ -64,7 +64,7 @@ def perm_index(N, perm_L, device="cpu"):
 
 
 def linear(x, w, perm_L=0):
-    """nn.Linear forward without bias: x (M, K) @ w (N, K)^T, columns in mg_linear_perm's order when perm_L > 1 (a bias /
+    """nn.Linear forward without bias: x (M, K) @ w (N, K)^T, columns in mg_linear's perm_L order when perm_L > 1 (a bias /
     scale / gscale vector follows the weight row: index it with perm_index).  Returns (ref, M), (M, N); n = K."""
     idx = perm_index(w.shape[0], perm_L, w.device)
     return _both(lambda a, b: (a @ b.t())[:, idx], x, w)
