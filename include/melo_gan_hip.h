@@ -611,6 +611,40 @@ int mg_eval_acc(const float* real, const float* fake, int B, int T, int C, const
 int mg_eval_noise(float* noise, int rows, int noise_dim, const uint64_t* counter, const uint64_t* base, long n, uint64_t seed,
                   mg_stream_t stream);
 
+/* ---- pairwise metrics between two feature sets (melo_gan_amd.gan.evaluate --feature-metrics; csrc/pair_metrics.hip) ----
+ * The reference suspects mode collapse and memorisation (src/gan/diagnose.py: "latent vectors are very collapsed";
+ * src/gan/tsne.py plots clusters) and measures neither.  KID, k-NN precision / recall and the nearest-training-neighbour check
+ * all reduce to the dot products between two sets, reduced in the GEMM's epilogue: the nA x nB matrix is never stored.
+ *   A (nA, D), B (nB, D)   contiguous fp32, row-major, 16-byte aligned; D a multiple of 4 in 4..1024; 1 <= nA, nB <= 2^20
+ *   g_ij  = a_i . b_j      exact fp32 on v_mfma_f32_32x32x2_f32, accumulated in fp32
+ *   d2_ij = max(|a_i|^2 + |b_j|^2 - 2 g_ij, 0)      the row norms are computed once per call into the workspace, by the same
+ *                          multiply-add chain as g: the d2 between a row and an identical row is exactly 0
+ * mg_pair_ksum:   out[0] (fp64) = sum_ij (g_ij / D + 1)^3, every g widened to fp64 before the cube and the sum (the cubic
+ *                 kernel of the Kernel Inception Distance).  exclude_diag (needs A == B, nA == nB) leaves i == j out.
+ * mg_pair_knn:    out (nA, k) fp32 = the k smallest d2_ij over j, ascending, 1 <= k <= 8.  exclude_self (needs A == B,
+ *                 nA == nB) skips j == i.  k > nB - exclude_self is an argument error.  Ties and duplicate rows are legal: the
+ *                 output is a multiset of values.
+ * mg_pair_margin: out[i] (fp32) = min_j (d2_ij - r2B[j]); row i lies in B's k-NN manifold (r2B[j] = b_j's k-th neighbour
+ *                 distance within B) iff out[i] <= 0.
+ * Launch shape: a workgroup of 256 lanes owns 64 rows of A and a run of 64-row tiles of B; D streams through LDS in chunks of
+ * 32 with rows past the end zero-filled; columns j >= nB and the excluded column enter the epilogue as +inf.  Per-workgroup
+ * partials (an fp64 sum; per row a sorted candidate list, +inf where a run holds fewer than k columns) go to `work`
+ * (mg_pair_workspace_bytes(nA, nB, D, k); k = 1 for mg_pair_ksum and mg_pair_margin), and a second launch of the same call
+ * folds them in a fixed order.  No floating-point atomics: two runs, and an eager run and a graph replay, leave identical bits.
+ * Capturable. */
+size_t mg_pair_workspace_bytes(long nA, long nB, int D, int k);
+int mg_pair_ksum(const float* A, long nA, const float* B, long nB, int D, int exclude_diag, double* out, void* work,
+                 size_t work_bytes, mg_stream_t stream);
+int mg_pair_knn(const float* A, long nA, const float* B, long nB, int D, int exclude_self, int k, float* out, void* work,
+                size_t work_bytes, mg_stream_t stream);
+int mg_pair_margin(const float* A, long nA, const float* B, long nB, int D, const float* r2B, float* out, void* work,
+                   size_t work_bytes, mg_stream_t stream);
+/* The inverse of mg_stage_rows_cursor for one fp32 array: row r of src (rows, width) goes to row
+ *   p = (counter[0] - base[0]) * rows + r   of dst (dst_rows, width); rows with p >= dst_rows are dropped (the padded tail of
+ * a pass's last batch).  Capturable: a replayed evaluation batch leaves its features at their split position. */
+int mg_scatter_rows_cursor(const float* src, int rows, int width, float* dst, long dst_rows, const uint64_t* counter,
+                           const uint64_t* base, mg_stream_t stream);
+
 /* ---- fused flat Adam / AdamW (torch.optim.Adam defaults; src/gan/train_gan.py:136-145,
  *      src/ae/train_ae.py:79).  state: double[4] = {step, beta1^step, beta2^step, unused},
  *      advanced on device so the launch is hipGraph-replayable.  grad_scale multiplies g first

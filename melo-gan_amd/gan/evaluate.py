@@ -8,7 +8,7 @@ ed_model.py):
     python -m melo_gan_amd.gan.evaluate --config config/gan_config.yaml \
         [--ckpt <CHECKPOINT_DIR>/gan_final.pth | gan_epochNNNN.pth] [--split <VAL_SPLIT>] [--feats <ENCODER_FEATS_VAL>] \
         [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--seed <SEED>] [--batch 64] \
-        [--out <LOG_DIR>/eval.json] [--synthetic N]
+        [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3]] [--memorisation]
 
 One pass over the split in row order.  Per batch ONE replayed hipGraph: stage the batch by a device-side cursor -> noise
 (mg_eval_noise: Philox keyed by (seed, split row), so the report does not depend on the batch size) -> E_num -> G (eval:
@@ -16,6 +16,11 @@ dropout off, BatchNorm on running statistics) -> critic on [real | fake] -> clas
 (latent mode: on the generator's internal latent, fake side only, as train_gan.py:232-237) -> mg_eval_acc, which adds the
 batch to a device-resident accumulator and advances the cursor.  The host reads the accumulator once, when the pass ends.
 A full checkpoint (gan_epochNNNN.pth) carries the critic; gan_final.pth does not and the critic metrics are then null.
+--feature-metrics adds what means over rows cannot see -- mode collapse and memorisation -- in the classifier's feature space
+(encoder.project's output): each batch's features are scattered to their split position inside the same graph, and after the
+pass the pair kernels (mg_pair_ksum / mg_pair_knn / mg_pair_margin) give KID, k-NN precision / recall, both per emotion, and
+the real-emotion x generated-emotion KID table (gan/feature_metrics.py).  --memorisation runs the real side over TRAIN_SPLIT
+as well and reports every generated and validation row's distance to its nearest training row.
 Every input from outside is checked on the host before any GPU use.
 """
 from __future__ import annotations
@@ -33,11 +38,13 @@ import numpy as np
 import torch
 
 from . import config as C
+from . import feature_metrics as FM
 from . import generate as G
 from .generate import EMOTIONS, GenerateError
 from .utils import check_labels, emotion_to_index
 
 DEFAULT_BATCH = 64
+DEFAULT_KNN_K, MAX_KNN_K = 3, 8
 SIDES = ("real", "fake")            # order of the accumulator's note statistics
 RAW_KEYS = ("n", "conf_fake", "conf_real", "d_sum", "cls", "nsum", "nsq", "nmin", "nmax")
 
@@ -54,6 +61,19 @@ def check_ed_config(ed_cfg: dict, cfg: dict, path: str = "ED config"):
         G.check_ed_config(ed_cfg, cfg)
     except GenerateError as e:
         raise EvaluateError(f"{path}: {e}") from e
+
+
+def check_feature_options(features: bool, knn_k: int, ed_cfg: Optional[dict]):
+    """What the feature-space metrics need: a neighbour count the kernel serves and a classifier that sees the real rolls."""
+    if not features:
+        return
+    if not 1 <= int(knn_k) <= MAX_KNN_K:
+        raise EvaluateError(f"--knn-k {knn_k}: must be in 1..{MAX_KNN_K}")
+    if ed_cfg is None:
+        raise EvaluateError("--feature-metrics needs the classifier (--ed_config / --ed_ckpt): its encoder is the feature space")
+    if ed_cfg.get("input_mode", "notes") != "notes":
+        raise EvaluateError("--feature-metrics needs a notes-mode classifier: a latent-mode one never sees the real rolls, so "
+                            "the real side of every metric is missing")
 
 
 def check_checkpoint(ck, cfg: dict, path: str = "checkpoint") -> bool:
@@ -203,6 +223,8 @@ def format_table(rep: dict) -> str:
             ch = rep["notes"][side][name]["channels"][0]
             cells.append(f"{side} " + " / ".join(f(ch[k], '.4f') for k in ("mean", "std", "min", "max")))
         lines.append(f"  {name:<8} " + "   ".join(cells))
+    if "feature_space" in rep:
+        lines.append(FM.format_block(rep["feature_space"], rep["feature_space"].get("nn_train")))
     return "\n".join(lines)
 
 
@@ -211,13 +233,16 @@ def format_table(rep: dict) -> str:
 # ---------------------------------------------------------------------------------------------------------------------
 class Evaluator:
     """One GanEngine of `batch` rows in eval mode: encoder dropout off, generator BatchNorm on running statistics, no
-    optimiser, no update of any buffer."""
+    optimiser, no update of any buffer.  features: also keep every row's encoder features of the real and the generated roll
+    and report the feature-space metrics over them (notes-mode classifier only); knn_k: the manifolds' neighbour count."""
 
-    def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH):
+    def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH, features: bool = False,
+                 knn_k: int = DEFAULT_KNN_K):
         from .. import ops
         from .engine import GanEngine
         if int(batch) < 1:
             raise EvaluateError(f"batch = {batch}: must be >= 1")
+        check_feature_options(features, knn_k, ed_cfg)
         cfg = {"LR_G": 0.0, "LR_D": 0.0, **C.with_gan_defaults(cfg, require=False)}      # the rates are never used here
         self.has_ed = ed_cfg is not None
         if self.has_ed:
@@ -235,7 +260,9 @@ class Evaluator:
         self.base = torch.zeros(1, dtype=torch.int64, device=d)
         self.acc = ops.eval_acc_new(self.K, eng.C, d)
         self.logits_real = torch.zeros(self.B, self.K, device=d)
-        self._graph, self._graph_key, self._hold = None, None, None
+        self.features, self.knn_k = bool(features), int(knn_k)
+        self.feat_real = self.feat_fake = self.feat_train = None      # (whole batches, notes_hidden) stashes in split row order
+        self._graph, self._graph_key, self._hold, self._labels_host = None, None, None, None
 
     # ---- weights ----
     def load_generator(self, ck):
@@ -316,24 +343,115 @@ class Evaluator:
                 eng._ed_fwd(eng.real)
                 ops.axpby(eng.logits, self.logits_real, 1.0, 0.0)
                 lr = self.logits_real
+                if self.features:                           # in front of eval_acc, which advances the cursor
+                    ops.scatter_rows_cursor(eng.ed_proj, self.feat_real, self.ctr, self.base)
             eng._ed_fwd(eng.fake_d)                         # latent mode: reads the generator's internal latent instead
             lf = eng.logits
+            if self.features:
+                ops.scatter_rows_cursor(eng.ed_proj, self.feat_fake, self.ctr, self.base)
         if not metrics:
             return
         ops.eval_acc(eng.real, eng.fake_d, eng.emot_idx, eng.s[:B] if self.has_d else None,
                      eng.s[B:2 * B] if self.has_d else None, lf, lr, self.acc, tick=self.ctr, n_classes=self.K)
 
-    def evaluate(self, dataset, seed: int, noise: Optional[torch.Tensor] = None) -> dict:
-        """One pass over a resident GANDataset in row order; returns the report.  noise: an (n, NOISE_DIM) resident fp32
-        array staged instead of drawn (tests, externally paired runs)."""
+    def _check_split(self, dataset, who):
+        eng = self.eng
+        if not getattr(dataset, "resident", False):
+            raise EvaluateError(f"evaluate: the {who} must be resident on the device (GANDataset(resident=True))")
+        if len(dataset) < 1 or tuple(dataset.notes.shape[1:]) != (eng.T, eng.C):
+            raise EvaluateError(f"evaluate: the {who}'s notes have shape {tuple(dataset.notes.shape)}, the engine reads "
+                                f"(n, {eng.T}, {eng.C})")
+
+    def _train_features(self, train_dataset):
+        """The real-side-only pass over the training split: stage -> classifier -> scatter, batch b under cursor value b."""
         from .. import ops
         eng, B = self.eng, self.B
-        if not getattr(dataset, "resident", False):
-            raise EvaluateError("evaluate: the split must be resident on the device (GANDataset(resident=True))")
+        n = len(train_dataset)
+        nb = (n + B - 1) // B
+        self.feat_train = torch.zeros(nb * B, eng.ed_feat_dim, device=eng.dev)
+        order = torch.arange(nb * B, dtype=torch.int64, device=eng.dev)
+        cursors = torch.arange(nb, dtype=torch.int64, device=eng.dev)
+        for b in range(nb):
+            ops.stage_rows_cursor([(train_dataset.notes, eng.real)], B, order, nb * B, cursors[b:b + 1], self.base)
+            eng._ed_fwd(eng.real)
+            ops.scatter_rows_cursor(eng.ed_proj, self.feat_train, cursors[b:b + 1], self.base)
+        return self.feat_train[:n]
+
+    def feature_space(self, labels_host, n, train=None):
+        """The report's feature_space block from the stashes: the pair kernels over the whole sets and the per-emotion slices,
+        every result in one device buffer that the host reads once.  labels_host: the split's class indices on the host (read
+        from the device once, when the pass's graph is built); the per-emotion row indices go up to the device on every call."""
+        from .. import ops
+        dev, k, K = self.eng.dev, self.knn_k, self.K
+        R, F = self.feat_real[:n], self.feat_fake[:n]
+        idx = [torch.nonzero(labels_host == e).flatten().to(dev) for e in range(K)]
+        counts = [int(i.numel()) for i in idx]
+        Re = [R.index_select(0, i) if c else None for i, c in zip(idx, counts)]
+        Fe = [F.index_select(0, i) if c else None for i, c in zip(idx, counts)]
+        # the layout of the result buffer: fp64 kernel sums first, then fp32 margins / distances
+        n_sums = 3 + 2 * K + K * K
+        n_f32 = 2 * sum(c for c in [n] + counts if c > k) + (2 * n if train is not None else 0)
+        buf = torch.zeros(8 * n_sums + 4 * n_f32, dtype=torch.uint8, device=dev)
+        ks, fl = buf[:8 * n_sums].view(torch.float64), buf[8 * n_sums:].view(torch.float32)
+        slot = iter(range(n_sums))
+        cut = [0]
+
+        def take(m):
+            cut[0] += m
+            return fl[cut[0] - m:cut[0]]
+
+        def ksum(A, Bm, same):
+            i = next(slot)
+            if A is not None and Bm is not None and A.shape[0] >= 2 and Bm.shape[0] >= 2:
+                ops.pair_ksum(A, Bm, ks[i:i + 1], exclude_diag=same)
+            return i
+
+        def margins(A, Bm):
+            """(A's rows in Bm's manifold, Bm's rows in A's), or None when the sets hold at most k rows."""
+            m = A.shape[0] if A is not None else 0
+            if m <= k:
+                return None, None
+            out = []
+            for X, Y in ((A, Bm), (Bm, A)):          # Y's radii, then X against Y's manifold
+                nn = torch.empty(m, k, device=dev)
+                ops.pair_knn(Y, Y, nn, exclude_self=True)
+                out.append(ops.pair_margin(X, Y, nn[:, k - 1].contiguous(), take(m)))
+            return out
+
+        s_xx, s_yy, s_xy = ksum(R, R, True), ksum(F, F, True), ksum(R, F, False)
+        s_xx_e = [ksum(Re[e], Re[e], True) for e in range(K)]
+        s_yy_e = [ksum(Fe[e], Fe[e], True) for e in range(K)]
+        s_xy_ef = [[ksum(Re[e], Fe[f], False) for f in range(K)] for e in range(K)]
+        m_fr, m_rf = margins(F, R)
+        m_e = [margins(Fe[e], Re[e]) for e in range(K)]
+        nn_fake = nn_real = None
+        if train is not None:
+            nn_fake = ops.pair_knn(F, train, take(n).view(n, 1))
+            nn_real = ops.pair_knn(R, train, take(n).view(n, 1))
+        host = buf.cpu()                                   # every result of the pair kernels in one device -> host read
+        hk, hf = host[:8 * n_sums].view(torch.float64).numpy(), host[8 * n_sums:].view(torch.float32).numpy()
+        at = lambda v: None if v is None else hf[v.storage_offset() - fl.storage_offset():][:v.numel()]  # noqa: E731
+        sums = {"xx": hk[s_xx], "yy": hk[s_yy], "xy": hk[s_xy], "xx_e": [hk[i] for i in s_xx_e], "yy_e": [hk[i] for i in s_yy_e],
+                "xy_ef": [[hk[i] for i in row] for row in s_xy_ef]}
+        marg = {"fake_in_real": at(m_fr), "real_in_fake": at(m_rf), "fake_in_real_e": [at(m[0]) for m in m_e],
+                "real_in_fake_e": [at(m[1]) for m in m_e]}
+        block = FM.feature_block(R.shape[1], k, EMOTIONS, counts, sums, marg)
+        if train is not None:
+            block["nn_train"] = FM.nn_summary(at(nn_fake), at(nn_real))
+        return block
+
+    def evaluate(self, dataset, seed: int, noise: Optional[torch.Tensor] = None, train_dataset=None) -> dict:
+        """One pass over a resident GANDataset in row order; returns the report.  noise: an (n, NOISE_DIM) resident fp32
+        array staged instead of drawn (tests, externally paired runs).  train_dataset (features=True only): the resident
+        training split of the nearest-training-row check."""
+        from .. import ops
+        eng, B = self.eng, self.B
+        self._check_split(dataset, "split")
         n = len(dataset)
-        if n < 1 or tuple(dataset.notes.shape[1:]) != (eng.T, eng.C):
-            raise EvaluateError(f"evaluate: the split's notes have shape {tuple(dataset.notes.shape)}, the engine reads "
-                                f"(n, {eng.T}, {eng.C})")
+        if train_dataset is not None:
+            if not self.features:
+                raise EvaluateError("evaluate: the nearest-training-row check needs an Evaluator built with features=True")
+            self._check_split(train_dataset, "training split")
         if tuple(dataset.numeric.shape) != (n, eng.num_in) or tuple(dataset.latent.shape) != (n, eng.latent_dim):
             raise EvaluateError("evaluate: the split's numeric features / latents do not match the config")
         if noise is not None and (not isinstance(noise, torch.Tensor) or not noise.is_cuda or noise.dtype != torch.float32 or
@@ -343,8 +461,14 @@ class Evaluator:
         nb = (n + B - 1) // B
         key = (dataset.notes.data_ptr(), dataset.emot_idx.data_ptr(), n, seed, None if noise is None else noise.data_ptr(),
                self.has_d)
+        train = None
         with torch.cuda.stream(eng.stream):
+            if train_dataset is not None:
+                train = self._train_features(train_dataset)
             if self._graph_key != key:
+                if self.features:
+                    self.feat_real = torch.zeros(nb * B, eng.ed_feat_dim, device=eng.dev)
+                    self.feat_fake = torch.zeros(nb * B, eng.ed_feat_dim, device=eng.dev)
                 # the labels padded to whole batches with -1: the staging clamps the other arrays' padding rows into the split
                 labels = torch.full((nb * B,), -1, dtype=torch.int64, device=eng.dev)
                 labels[:n] = dataset.emot_idx
@@ -364,13 +488,18 @@ class Evaluator:
                 finally:
                     g.end()
                 self._graph, self._graph_key, self._hold = g, key, (dataset, labels, order, noise)
+                self._labels_host = dataset.emot_idx.cpu() if self.features else None      # the grouping of the feature metrics
             ops.eval_acc_reset(self.acc, self.K, eng.C)
             self.ctr.zero_()
             for _ in range(nb):
                 self._graph.launch()
             acc = self.acc.cpu()                # the pass's only device -> host read
+            block = self.feature_space(self._labels_host, n, train) if self.features else None
         raw = raw_from_acc(acc, self.K, eng.C)
-        return build_report(raw, eng.T, seed, B, self.has_d, self.has_ed, self.ed_real)
+        rep = build_report(raw, eng.T, seed, B, self.has_d, self.has_ed, self.ed_real)
+        if block is not None:
+            rep["feature_space"] = block
+        return rep
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -389,6 +518,12 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=DEFAULT_BATCH, help="rows per replayed batch")
     ap.add_argument("--out", type=str, default=None, help="report file (default <LOG_DIR>/eval.json)")
     ap.add_argument("--synthetic", type=int, default=0, help="evaluate on N synthetic rolls (drawn with SEED + 1) instead of a split")
+    ap.add_argument("--feature-metrics", action="store_true",
+                    help="add KID and k-NN precision / recall in the classifier's feature space (needs a notes-mode classifier)")
+    ap.add_argument("--knn-k", type=int, default=DEFAULT_KNN_K, help=f"neighbours of the precision / recall manifolds (1..{MAX_KNN_K})")
+    ap.add_argument("--memorisation", action="store_true",
+                    help="also report every generated / validation row's distance to its nearest TRAIN_SPLIT row (implies "
+                         "--feature-metrics)")
     return ap.parse_args(argv)
 
 
@@ -405,6 +540,10 @@ class Plan:
     seed: int
     batch: int
     out: str
+    features: bool = False
+    knn_k: int = DEFAULT_KNN_K
+    memorisation: bool = False
+    train_arrays: Optional[tuple] = None
 
 
 def _read_config(path: str, what: str) -> dict:
@@ -420,6 +559,13 @@ def plan(args) -> Plan:
         raise EvaluateError(f"--batch {args.batch}: must be >= 1")
     if args.synthetic < 0:
         raise EvaluateError(f"--synthetic {args.synthetic}: must be >= 0")
+    memorisation = bool(getattr(args, "memorisation", False))
+    features = bool(getattr(args, "feature_metrics", False)) or memorisation
+    knn_k = int(getattr(args, "knn_k", DEFAULT_KNN_K))
+    if not 1 <= knn_k <= MAX_KNN_K:
+        raise EvaluateError(f"--knn-k {knn_k}: must be in 1..{MAX_KNN_K}")
+    if features and args.ed_config is None:
+        check_feature_options(True, knn_k, None)
     cfg = C.with_gan_defaults(_read_config(args.config, "config"), require=False)
     missing = [k for k in ("NOISE_DIM", "LATENT_DIM", "MAX_NOTES", "NOTE_DIM") if k not in cfg]
     if missing:
@@ -441,6 +587,7 @@ def plan(args) -> Plan:
     if args.ed_config is not None:
         ed_cfg = _read_config(args.ed_config, "ED config")
         check_ed_config(ed_cfg, cfg, f"ED config {args.ed_config}")
+        check_feature_options(features, knn_k, ed_cfg)
         if not os.path.isfile(args.ed_ckpt):
             raise EvaluateError(f"ED checkpoint {args.ed_ckpt} does not exist")
     arrays = None
@@ -449,9 +596,15 @@ def plan(args) -> Plan:
         if not split:
             raise EvaluateError(f"config {args.config} lacks VAL_SPLIT and no --split was given")
         arrays = load_split_arrays(cfg, split, args.feats or cfg.get("ENCODER_FEATS_VAL"), feats_required=args.feats is not None)
+    train_arrays = None
+    if memorisation and not args.synthetic:     # with --synthetic the training side is the trainer's synthetic split (SEED)
+        if not cfg.get("TRAIN_SPLIT"):
+            raise EvaluateError(f"--memorisation: config {args.config} lacks TRAIN_SPLIT")
+        train_arrays = load_split_arrays(cfg, cfg["TRAIN_SPLIT"], None)
     out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/gan/logs"), "eval.json")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
-    return Plan(cfg, ed_cfg, ckpt_path, ckpt, has_critic, args.ed_ckpt, arrays, int(args.synthetic), seed, args.batch, out)
+    return Plan(cfg, ed_cfg, ckpt_path, ckpt, has_critic, args.ed_ckpt, arrays, int(args.synthetic), seed, args.batch, out,
+                features, knn_k, memorisation, train_arrays)
 
 
 def main(argv=None) -> int:
@@ -470,13 +623,18 @@ def main(argv=None) -> int:
                                   int(cfg.get("SEED", 42)) + 1, "cuda")
     else:
         ds = GANDataset(*p.arrays, int(cfg["LATENT_DIM"]), "cuda", resident=True)
-    ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch)
+    train_ds = None
+    if p.memorisation:
+        train_ds = (GANDataset.synthetic(p.synthetic, int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg["LATENT_DIM"]),
+                                         int(cfg.get("SEED", 42)), "cuda") if p.synthetic else
+                    GANDataset(*p.train_arrays, int(cfg["LATENT_DIM"]), "cuda", resident=True))
+    ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch, features=p.features, knn_k=p.knn_k)
     ev.load_generator(p.ckpt)
     if p.has_critic:
         ev.load_critic(p.ckpt)
     if p.ed_cfg is not None:
         ev.load_ed(p.ed_ckpt)
-    rep = ev.evaluate(ds, p.seed)
+    rep = ev.evaluate(ds, p.seed, train_dataset=train_ds)
     rep["checkpoint"], rep["ed_checkpoint"] = p.ckpt_path, p.ed_ckpt
     os.makedirs(os.path.dirname(os.path.abspath(p.out)), exist_ok=True)
     with open(p.out, "w") as f:

@@ -1773,6 +1773,92 @@ def eval_noise(noise, counter, base, n: int, seed: int):
     return noise
 
 
+PAIR_MAX_K, PAIR_MAX_ROWS = 8, 1 << 20
+
+
+def _pair_sets(who, A, B):
+    """The two feature sets of a pair kernel: (nA, D) and (nB, D) fp32, contiguous, 16-byte aligned."""
+    _chk(A, f"{who}: A")
+    _chk(B, f"{who}: B")
+    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[1]:
+        raise ValueError(f"{who}: A (nA, D) and B (nB, D) expected, got {tuple(A.shape)} and {tuple(B.shape)}")
+    nA, D = A.shape
+    nB = B.shape[0]
+    if not (D % 4 == 0 and 4 <= D <= 1024):
+        raise ValueError(f"{who}: D must be a multiple of 4 in 4..1024")
+    if not (1 <= nA <= PAIR_MAX_ROWS and 1 <= nB <= PAIR_MAX_ROWS):
+        raise ValueError(f"{who}: 1..2^20 rows on each side")
+    if A.data_ptr() % 16 or B.data_ptr() % 16:
+        raise ValueError(f"{who}: A and B must be 16-byte aligned")
+    return nA, nB, D
+
+
+def _pair_self(who, A, B, flag):
+    if flag and (A.data_ptr() != B.data_ptr() or A.shape[0] != B.shape[0]):
+        raise ValueError(f"{who}: leaving a row's own column out needs A and B to be the same array")
+    return 1 if flag else 0
+
+
+def _pair_work(lib, nA, nB, D, k, device):
+    return workspace(lib.mg_pair_workspace_bytes(nA, nB, D, k), device, "pair")
+
+
+def pair_ksum(A, B, out, exclude_diag=False):
+    """out[0] (fp64) = sum_ij (a_i . b_j / D + 1)^3 (mg_pair_ksum), the cubic-kernel sum of KID; exclude_diag (A is B) leaves
+    i == j out."""
+    nA, nB, D = _pair_sets("pair_ksum", A, B)
+    ex = _pair_self("pair_ksum", A, B, exclude_diag)
+    _chk(out, "pair_ksum: out", (1,), torch.float64)
+    lib = L.load()
+    work = _pair_work(lib, nA, nB, D, 1, A.device)
+    L.check(lib.mg_pair_ksum(_p(A), nA, _p(B), nB, D, ex, _p(out), _p(work), work.numel(), _stream()), "mg_pair_ksum")
+    return out
+
+
+def pair_knn(A, B, out, exclude_self=False):
+    """out (nA, k) = the k smallest squared distances from every row of A to the rows of B, ascending (mg_pair_knn);
+    exclude_self (A is B) skips a row's own column."""
+    nA, nB, D = _pair_sets("pair_knn", A, B)
+    ex = _pair_self("pair_knn", A, B, exclude_self)
+    _chk(out, "pair_knn: out")
+    if out.dim() != 2 or out.shape[0] != nA or not 1 <= out.shape[1] <= PAIR_MAX_K:
+        raise ValueError(f"pair_knn: out ({nA}, k) with k in 1..{PAIR_MAX_K} expected, got {tuple(out.shape)}")
+    k = out.shape[1]
+    if k > nB - ex:
+        raise ValueError(f"pair_knn: k = {k} neighbours asked of {nB - ex} candidates")
+    lib = L.load()
+    work = _pair_work(lib, nA, nB, D, k, A.device)
+    L.check(lib.mg_pair_knn(_p(A), nA, _p(B), nB, D, ex, k, _p(out), _p(work), work.numel(), _stream()), "mg_pair_knn")
+    return out
+
+
+def pair_margin(A, B, r2B, out):
+    """out[i] = min_j (|a_i - b_j|^2 - r2B[j]) (mg_pair_margin): row i lies in B's k-NN manifold iff out[i] <= 0."""
+    nA, nB, D = _pair_sets("pair_margin", A, B)
+    _chk(r2B, "pair_margin: r2B", (nB,))
+    _chk(out, "pair_margin: out", (nA,))
+    lib = L.load()
+    work = _pair_work(lib, nA, nB, D, 1, A.device)
+    L.check(lib.mg_pair_margin(_p(A), nA, _p(B), nB, D, _p(r2B), _p(out), _p(work), work.numel(), _stream()), "mg_pair_margin")
+    return out
+
+
+def scatter_rows_cursor(src, dst, counter, base):
+    """stage_rows_cursor's inverse (mg_scatter_rows_cursor): row r of src (rows, width) goes to row (counter - base) * rows + r
+    of dst (dst_rows, width); rows past dst's end are dropped.  counter / base: int64 device scalars (1,)."""
+    _chk(src, "scatter_rows_cursor: src")
+    _chk(dst, "scatter_rows_cursor: dst")
+    if src.dim() != 2 or dst.dim() != 2 or src.shape[1] != dst.shape[1] or not 1 <= src.shape[0] <= 65535 or dst.shape[0] < 1 \
+            or src.shape[1] < 1:
+        raise ValueError(f"scatter_rows_cursor: src (1..65535 rows, width) and dst (dst_rows, width) expected, got "
+                         f"{tuple(src.shape)} and {tuple(dst.shape)}")
+    _chk(counter, "counter", (1,), torch.int64)
+    _chk(base, "base", (1,), torch.int64)
+    L.check(L.load().mg_scatter_rows_cursor(_p(src), src.shape[0], src.shape[1], _p(dst), dst.shape[0], _p(counter), _p(base),
+                                            _stream()), "mg_scatter_rows_cursor")
+    return dst
+
+
 def wq_table(entries):
     """ctypes table for adam_flat(wq=...): entries = [(start, N, Cc, K, w_sn, w_sc, dst tensor), ...] (mg_wq_entry)."""
     if len(entries) > L.MAX_WQ_ENTRIES:
