@@ -645,6 +645,54 @@ int mg_pair_margin(const float* A, long nA, const float* B, long nB, int D, cons
 int mg_scatter_rows_cursor(const float* src, int rows, int width, float* dst, long dst_rows, const uint64_t* counter,
                            const uint64_t* base, mg_stream_t stream);
 
+/* ---- note-level musical statistics of real and generated rolls (melo_gan_amd.gan.evaluate --music-metrics;
+ *      csrc/note_metrics.hip) ----
+ * The reference's instrument for "is the GAN learning different emotions" is src/gan/analyze_midi.py:28-54: note count, mean
+ * pitch, pitch range, unique pitches, mean velocity and density of .mid files written one by one.  mg_note_stats computes the
+ * same quantities, and the histograms the music-generation literature compares (pitch, pitch class, pitch-class transitions,
+ * interval, duration, inter-onset step), from the rolls of ONE evaluated batch where they lie on the device.  Capturable.
+ * The launch sits in front of mg_eval_acc, which advances the cursor.
+ *   real, fake      (B, T, 4) fp32, 16-byte aligned; C != 4 is an argument error: only the note-row format decodes into notes
+ *   emot_idx        (B) int64, the true class; rows with a label outside [0, n_classes) are padding, count nowhere and write
+ *                   nothing
+ *   B in 1..32767, T in 1..2^20, n_classes in 1..32; anything else returns -1 before a launch
+ * The decode of a time position x = (x0, x1, x2, x3) is the output contract src/gan/utils.py:102-156 (notes_from_roll with the
+ * chromatic scale, for which snapping is the identity), every fp32 operation rounded on its own, no fused multiply-add, an
+ * IEEE divide:
+ *   invalid = any of the four not finite       counted as such and otherwise absent (the host function would raise)
+ *   rest    = x1 < -0.2f
+ *   pitch   = clip(trunc((x0 + 1f) * 63.5f), 36, 96)
+ *   vel     = clip(trunc(60f + ((x1 - -0.2f) / 1.2f) * 67f), 0, 127)
+ *   dur     = d > 0.25f ? double(d) : 0.25,   d = ((x2 + 1f) / 2f) * 4f       beats
+ *   step    = s > 0.1f ? double(s) : 0.1,     s = ((x3 + 1f) / 2f) * 4f       beats (0.1 enters as the Python double)
+ * Accumulator: mg_note_acc_words(K = n_classes) = 2 K 504 int64 words, one block per [side: real, fake][true class]:
+ *   counters[8]        rows, valid events, notes, rests, invalid events, overlaps, transitions, 0
+ *   pitch[128]         notes by MIDI pitch
+ *   velocity[128]      notes by MIDI velocity
+ *   dur16[16]          notes by min(15, floor(dur * 4))
+ *   step16[16]         valid events, rests included, by min(15, floor(step * 4))
+ *   interval[64]       per transition, min(63, |pitch - previous pitch|)
+ *   pctm[12][12]       per transition, [previous pitch % 12][pitch % 12]
+ * A transition is a pair of consecutive sounding notes of one row (rests and invalid positions between them are skipped); an
+ * overlap is a note at position t < T - 1 with dur > step (it still sounds when the next position begins).
+ * mg_note_acc_reset writes zeros.
+ * Per-row outputs at the split position p = (counter[0] - base[0]) * B + row (mg_scatter_rows_cursor's rule; rows with
+ * p >= dst_rows are dropped; the caller zeroes both arrays):
+ *   row_i      [side][dst_rows][8] int32: notes, rests, invalid, unique pitches, lowest pitch, highest pitch (0 and 0 without
+ *              a note), overlaps, transitions
+ *   row_beats  [side][dst_rows][2] double: sum of step over valid events, sum of dur over notes; every term is fp64 before it is
+ *              added, a lane adds its positions in order and the 256 lanes are reduced by a fixed tree
+ * Launch shape: one workgroup of 256 lanes per (side, row), 2 B workgroups; a lane loads one time position as one 16-byte
+ * load and the workgroup walks the row in chunks of 256 positions.  The previous sounding pitch comes from the wave's ballot
+ * of sounding lanes, across waves and chunks through LDS.  Histograms are integer LDS atomics, the unique pitches a 61-bit
+ * mask OR-ed over the workgroup; at the end only the non-zero bins go to the accumulator, as integer atomics.  No
+ * floating-point atomics: two runs, and an eager run and a graph replay, leave identical bits. */
+long mg_note_acc_words(int n_classes);
+int mg_note_acc_reset(void* acc, int n_classes, mg_stream_t stream);
+int mg_note_stats(const float* real, const float* fake, int B, int T, int C, const int64_t* emot_idx, int n_classes, void* acc,
+                  int32_t* row_i, double* row_beats, long dst_rows, const uint64_t* counter, const uint64_t* base,
+                  mg_stream_t stream);
+
 /* ---- fused flat Adam / AdamW (torch.optim.Adam defaults; src/gan/train_gan.py:136-145,
  *      src/ae/train_ae.py:79).  state: double[4] = {step, beta1^step, beta2^step, unused},
  *      advanced on device so the launch is hipGraph-replayable.  grad_scale multiplies g first

@@ -8,7 +8,7 @@ ed_model.py):
     python -m melo_gan_amd.gan.evaluate --config config/gan_config.yaml \
         [--ckpt <CHECKPOINT_DIR>/gan_final.pth | gan_epochNNNN.pth] [--split <VAL_SPLIT>] [--feats <ENCODER_FEATS_VAL>] \
         [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--seed <SEED>] [--batch 64] \
-        [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3]] [--memorisation]
+        [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3]] [--memorisation] [--music-metrics]
 
 One pass over the split in row order.  Per batch ONE replayed hipGraph: stage the batch by a device-side cursor -> noise
 (mg_eval_noise: Philox keyed by (seed, split row), so the report does not depend on the batch size) -> E_num -> G (eval:
@@ -21,6 +21,11 @@ A full checkpoint (gan_epochNNNN.pth) carries the critic; gan_final.pth does not
 pass the pair kernels (mg_pair_ksum / mg_pair_knn / mg_pair_margin) give KID, k-NN precision / recall, both per emotion, and
 the real-emotion x generated-emotion KID table (gan/feature_metrics.py).  --memorisation runs the real side over TRAIN_SPLIT
 as well and reports every generated and validation row's distance to its nearest training row.
+--music-metrics reports in notes what analyze_midi.py reads off written files: one more launch per batch (mg_note_stats, in
+front of mg_eval_acc) decodes every real and every generated row into note events by the output contract and adds them to
+device-resident integer histograms per side and true emotion; after the pass the host reads them once and
+gan/music_metrics.py builds the `music` block -- note count, pitch, velocity, rests, density per emotion, and the
+Jensen-Shannon divergence of seven histograms between real and generated music.  NOTE_DIM 4 only.
 Every input from outside is checked on the host before any GPU use.
 """
 from __future__ import annotations
@@ -40,6 +45,7 @@ import torch
 from . import config as C
 from . import feature_metrics as FM
 from . import generate as G
+from . import music_metrics as MM
 from .generate import EMOTIONS, GenerateError
 from .utils import check_labels, emotion_to_index
 
@@ -74,6 +80,19 @@ def check_feature_options(features: bool, knn_k: int, ed_cfg: Optional[dict]):
     if ed_cfg.get("input_mode", "notes") != "notes":
         raise EvaluateError("--feature-metrics needs a notes-mode classifier: a latent-mode one never sees the real rolls, so "
                             "the real side of every metric is missing")
+
+
+def check_music_options(music: bool, cfg: dict, batch: int = DEFAULT_BATCH):
+    """The note-level statistics decode (T, 4) note rows; the piano-roll configuration has no such decode.  The batch and the
+    row length must lie in mg_note_stats' domain."""
+    if not music:
+        return
+    if int(cfg["NOTE_DIM"]) != MM.NOTE_DIM:
+        raise EvaluateError(f"--music-metrics: NOTE_DIM = {cfg['NOTE_DIM']}: only the note-row format (NOTE_DIM "
+                            f"{MM.NOTE_DIM}: pitch, velocity, duration, step) decodes into notes")
+    if int(batch) > 32767 or not 1 <= int(cfg["MAX_NOTES"]) <= 1 << 20:
+        raise EvaluateError(f"--music-metrics: --batch {batch} / MAX_NOTES {cfg['MAX_NOTES']}: at most 32767 rows per batch and "
+                            "2^20 positions per row")
 
 
 def check_checkpoint(ck, cfg: dict, path: str = "checkpoint") -> bool:
@@ -225,6 +244,8 @@ def format_table(rep: dict) -> str:
         lines.append(f"  {name:<8} " + "   ".join(cells))
     if "feature_space" in rep:
         lines.append(FM.format_block(rep["feature_space"], rep["feature_space"].get("nn_train")))
+    if "music" in rep:
+        lines.append(MM.format_block(rep["music"]))
     return "\n".join(lines)
 
 
@@ -234,16 +255,18 @@ def format_table(rep: dict) -> str:
 class Evaluator:
     """One GanEngine of `batch` rows in eval mode: encoder dropout off, generator BatchNorm on running statistics, no
     optimiser, no update of any buffer.  features: also keep every row's encoder features of the real and the generated roll
-    and report the feature-space metrics over them (notes-mode classifier only); knn_k: the manifolds' neighbour count."""
+    and report the feature-space metrics over them (notes-mode classifier only); knn_k: the manifolds' neighbour count.
+    music: also decode every real and generated row into notes and report the `music` block (NOTE_DIM 4 only)."""
 
     def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH, features: bool = False,
-                 knn_k: int = DEFAULT_KNN_K):
+                 knn_k: int = DEFAULT_KNN_K, music: bool = False):
         from .. import ops
         from .engine import GanEngine
         if int(batch) < 1:
             raise EvaluateError(f"batch = {batch}: must be >= 1")
         check_feature_options(features, knn_k, ed_cfg)
         cfg = {"LR_G": 0.0, "LR_D": 0.0, **C.with_gan_defaults(cfg, require=False)}      # the rates are never used here
+        check_music_options(music, cfg, batch)
         self.has_ed = ed_cfg is not None
         if self.has_ed:
             check_ed_config(ed_cfg, cfg)
@@ -262,6 +285,8 @@ class Evaluator:
         self.logits_real = torch.zeros(self.B, self.K, device=d)
         self.features, self.knn_k = bool(features), int(knn_k)
         self.feat_real = self.feat_fake = self.feat_train = None      # (whole batches, notes_hidden) stashes in split row order
+        self.music = bool(music)
+        self.music_buf = self.note_acc = self.note_row_i = self.note_row_beats = None      # one buffer, three views of it
         self._graph, self._graph_key, self._hold, self._labels_host = None, None, None, None
 
     # ---- weights ----
@@ -351,6 +376,9 @@ class Evaluator:
                 ops.scatter_rows_cursor(eng.ed_proj, self.feat_fake, self.ctr, self.base)
         if not metrics:
             return
+        if self.music:                                      # in front of eval_acc, which advances the cursor
+            ops.note_stats(eng.real, eng.fake_d, eng.emot_idx, self.note_acc, self.note_row_i, self.note_row_beats, self.ctr,
+                           self.base, self.K)
         ops.eval_acc(eng.real, eng.fake_d, eng.emot_idx, eng.s[:B] if self.has_d else None,
                      eng.s[B:2 * B] if self.has_d else None, lf, lr, self.acc, tick=self.ctr, n_classes=self.K)
 
@@ -460,7 +488,7 @@ class Evaluator:
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         nb = (n + B - 1) // B
         key = (dataset.notes.data_ptr(), dataset.emot_idx.data_ptr(), n, seed, None if noise is None else noise.data_ptr(),
-               self.has_d)
+               self.has_d, self.music)
         train = None
         with torch.cuda.stream(eng.stream):
             if train_dataset is not None:
@@ -469,6 +497,12 @@ class Evaluator:
                 if self.features:
                     self.feat_real = torch.zeros(nb * B, eng.ed_feat_dim, device=eng.dev)
                     self.feat_fake = torch.zeros(nb * B, eng.ed_feat_dim, device=eng.dev)
+                if self.music:      # accumulator | per-row fp64 sums | per-row int32 numbers: one device -> host read
+                    words = ops.note_acc_layout(self.K)["words"]
+                    self.music_buf = torch.zeros(words + 2 * nb * B * 2 + 2 * nb * B * 4, dtype=torch.int64, device=eng.dev)
+                    self.note_acc = self.music_buf[:words]
+                    self.note_row_beats = self.music_buf[words:words + 4 * nb * B].view(torch.float64).view(2, nb * B, 2)
+                    self.note_row_i = self.music_buf[words + 4 * nb * B:].view(torch.int32).view(2, nb * B, 8)
                 # the labels padded to whole batches with -1: the staging clamps the other arrays' padding rows into the split
                 labels = torch.full((nb * B,), -1, dtype=torch.int64, device=eng.dev)
                 labels[:n] = dataset.emot_idx
@@ -488,18 +522,33 @@ class Evaluator:
                 finally:
                     g.end()
                 self._graph, self._graph_key, self._hold = g, key, (dataset, labels, order, noise)
-                self._labels_host = dataset.emot_idx.cpu() if self.features else None      # the grouping of the feature metrics
+                # the grouping of the feature metrics and of the per-row note statistics
+                self._labels_host = dataset.emot_idx.cpu() if self.features or self.music else None
             ops.eval_acc_reset(self.acc, self.K, eng.C)
+            if self.music:
+                self.music_buf.zero_()          # the empty accumulator (mg_note_acc_reset's zeros) and the per-row stashes
             self.ctr.zero_()
             for _ in range(nb):
                 self._graph.launch()
-            acc = self.acc.cpu()                # the pass's only device -> host read
+            acc = self.acc.cpu()                # the pass's only device -> host read (with the note statistics' buffer)
+            music_host = self.music_buf.cpu() if self.music else None
             block = self.feature_space(self._labels_host, n, train) if self.features else None
         raw = raw_from_acc(acc, self.K, eng.C)
         rep = build_report(raw, eng.T, seed, B, self.has_d, self.has_ed, self.ed_real)
         if block is not None:
             rep["feature_space"] = block
+        if music_host is not None:
+            rep["music"] = self._music_block(music_host, n, nb)
         return rep
+
+    def _music_block(self, host: torch.Tensor, n: int, nb: int) -> dict:
+        """The `music` block from the host copy of music_buf (the layout of evaluate())."""
+        from .. import ops
+        words, rows = ops.note_acc_layout(self.K)["words"], nb * self.B
+        raw = {k: v.numpy() for k, v in ops.note_acc_views(host[:words], self.K).items()}
+        beats = host[words:words + 4 * rows].view(torch.float64).view(2, rows, 2).numpy()
+        row_i = host[words + 4 * rows:].view(torch.int32).view(2, rows, 8).numpy()
+        return MM.music_block(raw, {"row_i": row_i[:, :n], "row_beats": beats[:, :n]}, self._labels_host.numpy(), EMOTIONS)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -524,6 +573,8 @@ def parse_args(argv=None):
     ap.add_argument("--memorisation", action="store_true",
                     help="also report every generated / validation row's distance to its nearest TRAIN_SPLIT row (implies "
                          "--feature-metrics)")
+    ap.add_argument("--music-metrics", action="store_true",
+                    help="add the note-level musical statistics of the real and the generated rolls, per emotion (NOTE_DIM 4)")
     return ap.parse_args(argv)
 
 
@@ -544,6 +595,7 @@ class Plan:
     knn_k: int = DEFAULT_KNN_K
     memorisation: bool = False
     train_arrays: Optional[tuple] = None
+    music: bool = False
 
 
 def _read_config(path: str, what: str) -> dict:
@@ -573,6 +625,8 @@ def plan(args) -> Plan:
     if int(cfg["NOTE_DIM"]) % 4 or not 4 <= int(cfg["NOTE_DIM"]) <= 1024:
         raise EvaluateError(f"config {args.config}: NOTE_DIM = {cfg['NOTE_DIM']}: the metrics kernel reads 4 channels per lane "
                             "(a multiple of 4 in 4..1024)")
+    music = bool(getattr(args, "music_metrics", False))
+    check_music_options(music, cfg, args.batch)
     if args.ed_ckpt is not None and args.ed_config is None:
         raise EvaluateError("--ed_ckpt needs --ed_config (the classifier's architecture)")
     if args.ed_config is not None and args.ed_ckpt is None:
@@ -604,7 +658,7 @@ def plan(args) -> Plan:
     out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/gan/logs"), "eval.json")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
     return Plan(cfg, ed_cfg, ckpt_path, ckpt, has_critic, args.ed_ckpt, arrays, int(args.synthetic), seed, args.batch, out,
-                features, knn_k, memorisation, train_arrays)
+                features, knn_k, memorisation, train_arrays, music)
 
 
 def main(argv=None) -> int:
@@ -628,7 +682,7 @@ def main(argv=None) -> int:
         train_ds = (GANDataset.synthetic(p.synthetic, int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg["LATENT_DIM"]),
                                          int(cfg.get("SEED", 42)), "cuda") if p.synthetic else
                     GANDataset(*p.train_arrays, int(cfg["LATENT_DIM"]), "cuda", resident=True))
-    ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch, features=p.features, knn_k=p.knn_k)
+    ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch, features=p.features, knn_k=p.knn_k, music=p.music)
     ev.load_generator(p.ckpt)
     if p.has_critic:
         ev.load_critic(p.ckpt)

@@ -1859,6 +1859,79 @@ def scatter_rows_cursor(src, dst, counter, base):
     return dst
 
 
+NOTE_ACC_FIELDS = (("counters", (8,)), ("pitch", (128,)), ("velocity", (128,)), ("dur16", (16,)), ("step16", (16,)),
+                   ("interval", (64,)), ("pctm", (12, 12)))
+
+
+def note_acc_layout(n_classes: int) -> dict:
+    """The accumulator of note_stats (include/melo_gan_hip.h, mg_note_stats): name -> (offset in int64 words inside a
+    [side][class] block, shape), plus 'block' (words of one block) and 'words' (2 * K blocks)."""
+    K = int(n_classes)
+    if not 1 <= K <= 32:
+        raise ValueError("note_stats: 1..32 classes")
+    lay, off = {}, 0
+    for name, shape in NOTE_ACC_FIELDS:
+        lay[name] = (off, shape)
+        off += math.prod(shape)
+    lay["block"], lay["words"] = off, 2 * K * off
+    if lay["words"] != L.load().mg_note_acc_words(K):
+        raise RuntimeError("note_acc_layout disagrees with mg_note_acc_words")
+    return lay
+
+
+def note_acc_views(acc: Tensor, n_classes: int) -> dict:
+    """Views of an accumulator (device or host int64 tensor of note_acc_layout(...)['words'] words) by name, each
+    (2 sides, K, *shape)."""
+    lay = note_acc_layout(n_classes)
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] \
+            or not acc.is_contiguous():
+        raise ValueError(f"note_stats: the accumulator is a contiguous int64 vector of {lay['words']} words")
+    blocks = acc.view(2, int(n_classes), lay["block"])
+    return {name: blocks[:, :, off:off + math.prod(shape)].reshape(2, int(n_classes), *shape)
+            for name, (off, shape) in ((n, lay[n]) for n, _ in NOTE_ACC_FIELDS)}
+
+
+def note_acc_new(n_classes: int, device) -> Tensor:
+    """A fresh (zero) accumulator for note_stats."""
+    return torch.zeros(note_acc_layout(n_classes)["words"], dtype=torch.int64, device=device)
+
+
+def note_acc_reset(acc: Tensor, n_classes: int) -> Tensor:
+    _chk(acc, "acc", (note_acc_layout(n_classes)["words"],), torch.int64)
+    L.check(L.load().mg_note_acc_reset(_p(acc), int(n_classes), _stream()), "mg_note_acc_reset")
+    return acc
+
+
+def note_stats(real, fake, emot_idx, acc, row_i, row_beats, counter, base, n_classes: int):
+    """The note events of one evaluated batch added to the pass's note accumulator (mg_note_stats): real / fake (B, T, 4),
+    emot_idx (B,) int64 (-1 = a padding row), acc from note_acc_new(n_classes), row_i (2, dst_rows, 8) int32 and row_beats
+    (2, dst_rows, 2) float64 receive the per-row numbers at split position (counter - base) * B + row; counter / base: int64
+    device scalars (1,).  Goes in front of eval_acc, which advances the counter."""
+    _chk(real, "real")
+    if real.dim() != 3:
+        raise ValueError("note_stats: real (B, T, 4) expected")
+    B, T, C = real.shape
+    if C != 4:
+        raise ValueError(f"note_stats: C = {C}: only the (T, 4) note-row format decodes into notes")
+    _chk(fake, "fake", (B, T, C))
+    _chk(emot_idx, "emot_idx", (B,), torch.int64)
+    if not (1 <= B <= 32767 and 1 <= T <= 1 << 20):
+        raise ValueError("note_stats: B must be in 1..32767 and T in 1..2^20")
+    if real.data_ptr() % 16 or fake.data_ptr() % 16:
+        raise ValueError("note_stats: real and fake must be 16-byte aligned")
+    K = int(n_classes)
+    _chk(acc, "acc", (note_acc_layout(K)["words"],), torch.int64)
+    _chk(row_i, "row_i", dtype=torch.int32)
+    if row_i.dim() != 3 or row_i.shape[0] != 2 or row_i.shape[1] < 1 or row_i.shape[2] != 8:
+        raise ValueError(f"note_stats: row_i (2, dst_rows, 8) expected, got {tuple(row_i.shape)}")
+    _chk(row_beats, "row_beats", (2, row_i.shape[1], 2), torch.float64)
+    _chk(counter, "counter", (1,), torch.int64)
+    _chk(base, "base", (1,), torch.int64)
+    L.check(L.load().mg_note_stats(_p(real), _p(fake), B, T, C, _p(emot_idx), K, _p(acc), _p(row_i), _p(row_beats),
+                                   row_i.shape[1], _p(counter), _p(base), _stream()), "mg_note_stats")
+    return acc
+
+
 def wq_table(entries):
     """ctypes table for adam_flat(wq=...): entries = [(start, N, Cc, K, w_sn, w_sc, dst tensor), ...] (mg_wq_entry)."""
     if len(entries) > L.MAX_WQ_ENTRIES:

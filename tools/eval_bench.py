@@ -1,7 +1,7 @@
 """What the metrics accumulation costs in an evaluation batch (melo_gan_amd/gan/evaluate.py), at cfg2 size (B = 64, T = 256,
 C = 128) and at the shipped config's (B = 64, T = 512, C = 4):
 
-    python tools/eval_bench.py [--repeats 5]
+    python tools/eval_bench.py [--repeats 5] [--music]
 
   batch        us per replayed evaluation batch (stage -> noise -> E_num -> G -> critic -> classifier [-> mg_eval_acc]), the graph
                with and the graph without the metrics call, alternating, device events around 60 passes of 16 batches; their
@@ -14,6 +14,9 @@ and two yardsticks that are not the code under test:
   floor        the bytes the pass must read (2 B T C floats) over the 6.3 TB/s of HBM bandwidth a streaming kernel achieves
                (MI355X_MICROARCH.md)
 then the evaluator's rows/s over a whole pass (evaluate(): wall clock, ends in the accumulator's device->host read).
+--music runs the leg of --music-metrics instead, at the shipped config's size (the note decode needs C = 4): us per replayed
+batch of an Evaluator(music=True) with mg_note_stats in the graph and without it -- the latter is the batch as it was before
+the launch existed -- alternating as above, and mg_note_stats alone, 500 calls replayed as one graph.
 """
 import argparse
 import os
@@ -68,11 +71,100 @@ def events_us(fn, reps):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
+def batch_graphs(ev, ds, n, variants):
+    """One captured evaluation batch per variant: name -> a function that sets the evaluator up for that variant's capture and
+    returns the `metrics` argument of _launches."""
+    eng = ev.eng
+    _, labels, order, _ = ev._hold
+    jobs = [(ds.notes, eng.real), (ds.numeric, eng.numeric), (labels, eng.emot_idx), (ds.latent, eng.latent)]
+    graphs = {}
+    for name, prepare in variants:
+        metrics = prepare()
+        torch.cuda.synchronize()
+        g = ops.Graph()
+        g.begin()
+        try:
+            ev._launches(jobs, order, n, n, 1, True, metrics=metrics)
+        finally:
+            g.end()
+        graphs[name] = g
+    return graphs
+
+
+def time_graphs(ev, graphs, repeats):
+    times = {k: [] for k in graphs}
+    for _ in range(repeats):
+        for name, g in graphs.items():
+            ev.ctr.zero_()
+            for _ in range(16):
+                g.launch()
+            torch.cuda.synchronize()
+            e0, e1 = ops.Event(), ops.Event()
+            e0.record()
+            for _ in range(PASSES):
+                ev.ctr.zero_()
+                for _ in range(16):
+                    g.launch()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_ms(e1) / (16 * PASSES) * 1e3)
+    return times
+
+
+def music_leg(repeats, med):
+    B, T, C = 64, 512, 4
+    cfg, ed_cfg = default_gan_cfg(B, T, C), default_ed_cfg(C)
+    n = 16 * B
+    ds = GANDataset.synthetic(n, T, C, cfg["LATENT_DIM"], 1, "cuda")
+    ev = EV.Evaluator(cfg, ed_cfg, "cuda", B, music=True)
+    ev.has_d = True
+    rep = ev.evaluate(ds, 1)
+    assert rep["n"] == n and "music" in rep
+    eng = ev.eng
+
+    def variant(music):
+        def prepare():
+            ev.music = music
+            return True
+        return prepare
+
+    with torch.cuda.stream(eng.stream):
+        graphs = batch_graphs(ev, ds, n, (("with", variant(True)), ("without", variant(False))))
+        ev.music = True
+        times = time_graphs(ev, graphs, repeats)
+    print(f"music: B={B} T={T} C={C}: replayed evaluation batch, us", flush=True)
+    for name, ts in times.items():
+        print(f"  {name:8s} note_stats  {' '.join(f'{t:8.2f}' for t in ts)}   median {med(ts):8.2f}", flush=True)
+    diff = med(times["with"]) - med(times["without"])
+    print(f"  difference (mg_note_stats inside the batch): {diff:.2f} us = {100 * diff / med(times['without']):.1f} % of the batch "
+          "without it", flush=True)
+    ev.ctr.zero_()                                        # split positions inside the stashes: the per-row stores happen
+    torch.cuda.synchronize()
+    a = (eng.real, eng.fake_d, eng.emot_idx, ev.note_acc, ev.note_row_i, ev.note_row_beats, ev.ctr, ev.base, K)
+    alone = [timeit(lambda: ops.note_stats(*a), reps=500) for _ in range(repeats)]
+    print(f"  mg_note_stats alone        {' '.join(f'{t:8.2f}' for t in alone)}   median {med(alone):8.2f}", flush=True)
+    nbytes = 2 * B * T * 16
+    floor = nbytes / HBM_ACHIEVABLE * 1e6
+    print(f"  bytes read {nbytes / 1e6:.2f} MB -> floor {floor:.2f} us at 6.3 TB/s; the call alone is {med(alone) / floor:.1f} x its floor "
+          "(launch-bound)", flush=True)
+    ws = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ev.evaluate(ds, 1)
+        ws.append(time.perf_counter() - t0)
+    print(f"  evaluate(music=True): {n} rows in {med(ws) * 1e3:.3f} ms (median of {repeats}) = {n / med(ws):,.0f} rows/s", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--music", action="store_true", help="time the --music-metrics launch (mg_note_stats) instead")
     args = ap.parse_args()
     med = lambda ts: sorted(ts)[len(ts) // 2]  # noqa: E731
+    if args.music:
+        music_leg(args.repeats, med)
+        return
     for tag, (B, T, C) in (("cfg2", (64, 256, 128)), ("shipped", (64, 512, 4))):
         cfg, ed_cfg = default_gan_cfg(B, T, C), default_ed_cfg(C)
         n = 16 * B
@@ -82,35 +174,9 @@ def main():
         rep = ev.evaluate(ds, 1)                          # builds the pass's graph; every workspace exists from here on
         assert rep["n"] == n
         eng = ev.eng
-        _, labels, order, _ = ev._hold
-        jobs = [(ds.notes, eng.real), (ds.numeric, eng.numeric), (labels, eng.emot_idx), (ds.latent, eng.latent)]
-        graphs = {}
         with torch.cuda.stream(eng.stream):
-            for name, metrics in (("with", True), ("without", False)):
-                torch.cuda.synchronize()
-                g = ops.Graph()
-                g.begin()
-                try:
-                    ev._launches(jobs, order, n, n, 1, True, metrics=metrics)
-                finally:
-                    g.end()
-                graphs[name] = g
-            times = {k: [] for k in graphs}
-            for _ in range(args.repeats):
-                for name, g in graphs.items():
-                    ev.ctr.zero_()
-                    for _ in range(16):
-                        g.launch()
-                    torch.cuda.synchronize()
-                    e0, e1 = ops.Event(), ops.Event()
-                    e0.record()
-                    for _ in range(PASSES):
-                        ev.ctr.zero_()
-                        for _ in range(16):
-                            g.launch()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    times[name].append(e0.elapsed_ms(e1) / (16 * PASSES) * 1e3)
+            graphs = batch_graphs(ev, ds, n, (("with", lambda: True), ("without", lambda: False)))
+            times = time_graphs(ev, graphs, args.repeats)
         print(f"{tag}: B={B} T={T} C={C}: replayed evaluation batch, us", flush=True)
         for name, ts in times.items():
             print(f"  {name:8s} metrics  {' '.join(f'{t:8.2f}' for t in ts)}   median {med(ts):8.2f}", flush=True)
