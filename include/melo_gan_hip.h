@@ -693,6 +693,40 @@ int mg_note_stats(const float* real, const float* fake, int B, int T, int C, con
                   int32_t* row_i, double* row_beats, long dst_rows, const uint64_t* counter, const uint64_t* base,
                   mg_stream_t stream);
 
+/* ---- exact t-SNE of a feature set (melo_gan_amd.gan.tsne, melo_gan_amd.gan.evaluate --tsne; csrc/tsne.hip) ----
+ * The reference's tsne.py asks whether the VAE latents cluster by emotion and hands the answer to scikit-learn; here the
+ * affinities and the descent run on the device.  4 <= N <= 16384 (the dense P is 1 GiB there), everything fp32 unless said.
+ * mg_tsne_affinities: X (N, D) contiguous, D >= 1 -> the symmetric joint P (N, N) and, if `beta` is not null, the N precisions.
+ *   d2_ij = max(|x_i|^2 + |x_j|^2 - 2 x_i . x_j, 0)   mg_pair_*'s formula on the exact-fp32 matrix pipe; the row norms are the
+ *                          rows' own Gram diagonal by the same multiply-add chain, so identical rows are exactly 0 apart
+ *   p_j|i ~ exp(-beta_i (d2_ij - min_{j != i} d2_ij)), j != i, with beta_i the root of  entropy(p_.|i) = log(perplexity):
+ *                          bracketed by doubling from beta = 1 (at most 100 times), then bisected 64 times; no early exit.  The
+ *                          sums of an entropy evaluation are fp64.  1 <= perplexity < N - 1, there is no root otherwise.
+ *   P_ij = (p_j|i + p_i|j) / 2N                        P_ij and P_ji hold the same bits, the diagonal is exactly 0
+ *   Four launches: norms, one 64x64 tile of d2 per workgroup (into P), one workgroup per row with the row of d2 in LDS, one
+ *   workgroup per tile pair (I <= J) for the symmetric sum in place.
+ * mg_tsne_step: one iteration of scikit-learn's _gradient_descent on Y (N, 2), in place, with w_ij = 1 / (1 + |y_i - y_j|^2):
+ *   launch 1  a workgroup owns 16 rows and a run of 64-column tiles (runs sized for ~1024 workgroups) and writes, per row,
+ *             attr = sum_j p_ij w_ij (y_i - y_j) and rep = sum_j w_ij^2 (y_i - y_j) to its slab entry, and z = sum_{j != i} w_ij
+ *             of its rows to its own entry; every sum is fp64 under a fixed lane tree.  With a trace the instantiation that
+ *             also sums p_ij (log p_ij - log w_ij) (fp64 logarithms) runs instead.
+ *   launch 2  every workgroup folds the z entries in the same fixed order into Z, then per row
+ *             grad = 4 (exaggeration attr - rep / Z);  gains += 0.2 where update grad < 0, else gains *= 0.8, floored at 0.01;
+ *             update = momentum update - lr gains grad;  Y += update.      grad (N, 2), if not null, receives the gradient.
+ *   trace     if not null, record r = trace_cursor ? trace_cursor[0] : 0 of `trace` (4 doubles each; dropped when
+ *             r >= trace_cap) receives KL = sum p log p - sum p log w + log Z (of the plain P, whatever the exaggeration),
+ *             |grad|_2, Z, and sum p (log p - log w); trace_cursor[0], if given, is then advanced by one, so that a replayed
+ *             graph of iterations fills consecutive records without the host.
+ * `work`: mg_tsne_workspace_bytes(N) bytes (0 for an N outside the range), 16-byte aligned, shared by both calls.  No grid-wide
+ * barrier, no signalling between workgroups, no floating-point atomics: workgroups of a launch write disjoint memory, and two
+ * runs, an eager run and a graph replay, and runs on different streams leave identical bits.  Capturable. */
+size_t mg_tsne_workspace_bytes(long N);
+int mg_tsne_affinities(const float* X, long N, int D, float perplexity, float* P, float* beta, void* work, size_t work_bytes,
+                       mg_stream_t stream);
+int mg_tsne_step(const float* P, long N, float* Y, float* update, float* gains, float exaggeration, float momentum, float lr,
+                 float* grad, double* trace, uint64_t* trace_cursor, long trace_cap, void* work, size_t work_bytes,
+                 mg_stream_t stream);
+
 /* ---- fused flat Adam / AdamW (torch.optim.Adam defaults; src/gan/train_gan.py:136-145,
  *      src/ae/train_ae.py:79).  state: double[4] = {step, beta1^step, beta2^step, unused},
  *      advanced on device so the launch is hipGraph-replayable.  grad_scale multiplies g first

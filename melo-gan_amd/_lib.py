@@ -173,6 +173,9 @@ SIGNATURES = {
     "mg_note_acc_words": (i64, [i32]),
     "mg_note_acc_reset": (i32, [vp, i32, vp]),
     "mg_note_stats": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp]),
+    "mg_tsne_workspace_bytes": (sz, [i64]),
+    "mg_tsne_affinities": (i32, [vp, i64, i32, f32, vp, vp, vp, sz, vp]),
+    "mg_tsne_step": (i32, [vp, i64, vp, vp, vp, f32, f32, f32, vp, vp, vp, i64, vp, sz, vp]),
     "mg_adam_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, i32, vp, vp, i32, vp]),
     "mg_mlp_cls_fwd_bwd": (i32, [C.POINTER(MlpCls), i32, vp, vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, f32, C.c_uint64, vp, vp, f32, f32,
                                  vp, vp, vp, vp]),

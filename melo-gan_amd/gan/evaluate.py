@@ -8,7 +8,7 @@ ed_model.py):
     python -m melo_gan_amd.gan.evaluate --config config/gan_config.yaml \
         [--ckpt <CHECKPOINT_DIR>/gan_final.pth | gan_epochNNNN.pth] [--split <VAL_SPLIT>] [--feats <ENCODER_FEATS_VAL>] \
         [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--seed <SEED>] [--batch 64] \
-        [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3]] [--memorisation] [--music-metrics]
+        [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3] [--tsne]] [--memorisation] [--music-metrics]
 
 One pass over the split in row order.  Per batch ONE replayed hipGraph: stage the batch by a device-side cursor -> noise
 (mg_eval_noise: Philox keyed by (seed, split row), so the report does not depend on the batch size) -> E_num -> G (eval:
@@ -26,6 +26,9 @@ front of mg_eval_acc) decodes every real and every generated row into note event
 device-resident integer histograms per side and true emotion; after the pass the host reads them once and
 gan/music_metrics.py builds the `music` block -- note count, pitch, velocity, rests, density per emotion, and the
 Jensen-Shannon divergence of seven histograms between real and generated music.  NOTE_DIM 4 only.
+--tsne (needs --feature-metrics) lets one LOOK at those features: after the pass the stashed real and generated features are
+embedded jointly by exact t-SNE on the device (gan/tsne.py) and written next to the report as <out stem>_tsne.npy / .svg --
+colour = emotion, marker shape = real / generated -- with a `tsne` block (parameters, final KL, file names) in the report.
 Every input from outside is checked on the host before any GPU use.
 """
 from __future__ import annotations
@@ -80,6 +83,21 @@ def check_feature_options(features: bool, knn_k: int, ed_cfg: Optional[dict]):
     if ed_cfg.get("input_mode", "notes") != "notes":
         raise EvaluateError("--feature-metrics needs a notes-mode classifier: a latent-mode one never sees the real rolls, so "
                             "the real side of every metric is missing")
+
+
+def check_tsne_options(tsne: bool, features: bool, n: Optional[int] = None):
+    """The t-SNE plot embeds the feature stashes, which only --feature-metrics fills; 2 n rows must fit the dense affinities and
+    leave the default perplexity a root."""
+    if not tsne:
+        return
+    from . import tsne as TS
+    if not features:
+        raise EvaluateError("--tsne needs --feature-metrics: it embeds the classifier features that pass stashes")
+    if n is not None:
+        try:
+            TS.Tsne().check(2 * int(n), 1)
+        except TS.TsneError as e:
+            raise EvaluateError(f"--tsne: {e} (the real and the generated rows are embedded jointly: 2 x {n})") from e
 
 
 def check_music_options(music: bool, cfg: dict, batch: int = DEFAULT_BATCH):
@@ -541,6 +559,27 @@ class Evaluator:
             rep["music"] = self._music_block(music_host, n, nb)
         return rep
 
+    def tsne(self, n: int, stem: str, **params) -> dict:
+        """After evaluate() with features=True: the joint exact t-SNE of [feat_real[:n]; feat_fake[:n]] (2 n rows) written to
+        <stem>_tsne.npy and <stem>_tsne.svg (colour = true emotion, marker = real / generated); returns the report's `tsne`
+        block.  params: gan.tsne.Tsne's."""
+        from . import tsne as TS
+        if not self.features or self.feat_real is None or self._labels_host is None:
+            raise EvaluateError("tsne: needs an Evaluator built with features=True, after evaluate()")
+        check_tsne_options(True, True, n)
+        ts = TS.Tsne(**params)
+        with torch.cuda.stream(self.eng.stream):
+            X = torch.cat([self.feat_real[:n], self.feat_fake[:n]])
+            Y = ts.fit_transform(X)
+        names = [EMOTIONS[int(k)] if 0 <= int(k) < len(EMOTIONS) else TS.OTHER for k in self._labels_host[:n].tolist()]
+        files = {"embedding": stem + "_tsne.npy", "plot": stem + "_tsne.svg"}
+        np.save(files["embedding"], Y)
+        TS.write_svg(files["plot"], Y, names + names, title=f"t-SNE of the classifier features: {n} real, {n} generated",
+                     groups=[0] * n + [1] * n)
+        return {"n": 2 * n, "dim": int(X.shape[1]), "rows": "real rows 0..n-1, then generated rows 0..n-1", "params": ts.params(),
+                "kl": ts.kl_, "trace_iters": ts.trace_iters, "kl_trace": ts.kl_trace.tolist(),
+                "files": {k: os.path.basename(v) for k, v in files.items()}}
+
     def _music_block(self, host: torch.Tensor, n: int, nb: int) -> dict:
         """The `music` block from the host copy of music_buf (the layout of evaluate())."""
         from .. import ops
@@ -575,6 +614,9 @@ def parse_args(argv=None):
                          "--feature-metrics)")
     ap.add_argument("--music-metrics", action="store_true",
                     help="add the note-level musical statistics of the real and the generated rolls, per emotion (NOTE_DIM 4)")
+    ap.add_argument("--tsne", action="store_true",
+                    help="also embed the real and the generated features jointly by exact t-SNE and write <out stem>_tsne.npy / "
+                         ".svg (needs --feature-metrics)")
     return ap.parse_args(argv)
 
 
@@ -596,6 +638,7 @@ class Plan:
     memorisation: bool = False
     train_arrays: Optional[tuple] = None
     music: bool = False
+    tsne: bool = False
 
 
 def _read_config(path: str, what: str) -> dict:
@@ -616,6 +659,8 @@ def plan(args) -> Plan:
     knn_k = int(getattr(args, "knn_k", DEFAULT_KNN_K))
     if not 1 <= knn_k <= MAX_KNN_K:
         raise EvaluateError(f"--knn-k {knn_k}: must be in 1..{MAX_KNN_K}")
+    tsne = bool(getattr(args, "tsne", False))
+    check_tsne_options(tsne, features, args.synthetic or None)
     if features and args.ed_config is None:
         check_feature_options(True, knn_k, None)
     cfg = C.with_gan_defaults(_read_config(args.config, "config"), require=False)
@@ -650,6 +695,7 @@ def plan(args) -> Plan:
         if not split:
             raise EvaluateError(f"config {args.config} lacks VAL_SPLIT and no --split was given")
         arrays = load_split_arrays(cfg, split, args.feats or cfg.get("ENCODER_FEATS_VAL"), feats_required=args.feats is not None)
+        check_tsne_options(tsne, features, arrays[0].shape[0])
     train_arrays = None
     if memorisation and not args.synthetic:     # with --synthetic the training side is the trainer's synthetic split (SEED)
         if not cfg.get("TRAIN_SPLIT"):
@@ -658,7 +704,7 @@ def plan(args) -> Plan:
     out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/gan/logs"), "eval.json")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
     return Plan(cfg, ed_cfg, ckpt_path, ckpt, has_critic, args.ed_ckpt, arrays, int(args.synthetic), seed, args.batch, out,
-                features, knn_k, memorisation, train_arrays, music)
+                features, knn_k, memorisation, train_arrays, music, tsne)
 
 
 def main(argv=None) -> int:
@@ -691,9 +737,14 @@ def main(argv=None) -> int:
     rep = ev.evaluate(ds, p.seed, train_dataset=train_ds)
     rep["checkpoint"], rep["ed_checkpoint"] = p.ckpt_path, p.ed_ckpt
     os.makedirs(os.path.dirname(os.path.abspath(p.out)), exist_ok=True)
+    if p.tsne:
+        rep["tsne"] = ev.tsne(rep["n"], os.path.splitext(p.out)[0], seed=p.seed)
     with open(p.out, "w") as f:
         json.dump(rep, f, indent=1)
     print(format_table(rep))
+    if p.tsne:
+        print(f"t-SNE of {rep['tsne']['n']} feature rows: KL {rep['tsne']['kl']:.4f}; wrote {rep['tsne']['files']['embedding']}, "
+              f"{rep['tsne']['files']['plot']}")
     print(f"wrote {p.out}")
     return 0
 

@@ -1859,6 +1859,75 @@ def scatter_rows_cursor(src, dst, counter, base):
     return dst
 
 
+TSNE_MIN_ROWS, TSNE_MAX_ROWS, TSNE_TRACE_FIELDS = 4, 16384, ("kl", "grad_norm", "z", "plogp_minus_plogw")
+
+
+def tsne_workspace(n: int, device) -> Tensor:
+    """A scratch buffer of mg_tsne_workspace_bytes(n) for tsne_affinities / tsne_step, owned by the caller (a captured graph
+    of iterations keeps its address)."""
+    if not TSNE_MIN_ROWS <= int(n) <= TSNE_MAX_ROWS:
+        raise ValueError(f"tsne: {n} rows: {TSNE_MIN_ROWS}..{TSNE_MAX_ROWS} (the dense P)")
+    return torch.empty(L.load().mg_tsne_workspace_bytes(int(n)), dtype=torch.uint8, device=device)
+
+
+def _tsne_work(n, device, work):
+    if work is None:
+        return workspace(L.load().mg_tsne_workspace_bytes(n), device, "tsne")
+    _chk(work, "tsne: work", dtype=torch.uint8)
+    return work
+
+
+def tsne_affinities(X, perplexity: float, P=None, beta=None, work=None):
+    """The symmetric joint probabilities P (N, N) of exact t-SNE from X (N, D) (mg_tsne_affinities); beta (N), if given,
+    receives the per-row precisions.  Returns P."""
+    _chk(X, "tsne_affinities: X")
+    if X.dim() != 2 or X.shape[1] < 1 or not TSNE_MIN_ROWS <= X.shape[0] <= TSNE_MAX_ROWS:
+        raise ValueError(f"tsne_affinities: X (N, D) with N in {TSNE_MIN_ROWS}..{TSNE_MAX_ROWS} and D >= 1 expected, got "
+                         f"{tuple(X.shape)}")
+    n, D = X.shape
+    if not 1.0 <= float(perplexity) < n - 1:
+        raise ValueError(f"tsne_affinities: perplexity {perplexity}: 1 <= perplexity < N - 1 = {n - 1}")
+    if P is None:
+        P = torch.empty(n, n, device=X.device)
+    _chk(P, "tsne_affinities: P", (n, n))
+    if beta is not None:
+        _chk(beta, "tsne_affinities: beta", (n,))
+    work = _tsne_work(n, X.device, work)
+    L.check(L.load().mg_tsne_affinities(_p(X), n, D, float(perplexity), _p(P), _p(beta), _p(work), work.numel(), _stream()),
+            "mg_tsne_affinities")
+    return P
+
+
+def tsne_step(P, Y, update, gains, exaggeration: float, momentum: float, lr: float, grad=None, trace=None, cursor=None, work=None):
+    """One descent iteration of t-SNE on Y (N, 2) in place (mg_tsne_step: forces, then fold + scikit-learn's update).
+    grad (N, 2): receives the gradient.  trace (records, 4) fp64: record cursor[0] (0 without a cursor) receives
+    TSNE_TRACE_FIELDS, and cursor (1,) int64, if given, advances by one."""
+    _chk(P, "tsne_step: P")
+    if P.dim() != 2 or P.shape[0] != P.shape[1] or not TSNE_MIN_ROWS <= P.shape[0] <= TSNE_MAX_ROWS:
+        raise ValueError(f"tsne_step: P (N, N) with N in {TSNE_MIN_ROWS}..{TSNE_MAX_ROWS} expected, got {tuple(P.shape)}")
+    n = P.shape[0]
+    for nm, t in (("Y", Y), ("update", update), ("gains", gains)):
+        _chk(t, f"tsne_step: {nm}", (n, 2))
+    if grad is not None:
+        _chk(grad, "tsne_step: grad", (n, 2))
+    cap = 0
+    if trace is not None:
+        _chk(trace, "tsne_step: trace", dtype=torch.float64)
+        if trace.dim() != 2 or trace.shape[1] != 4 or trace.shape[0] < 1:
+            raise ValueError(f"tsne_step: trace (records, 4) expected, got {tuple(trace.shape)}")
+        cap = trace.shape[0]
+    if cursor is not None:
+        if trace is None:
+            raise ValueError("tsne_step: a trace cursor without a trace")
+        _chk(cursor, "tsne_step: cursor", (1,), torch.int64)
+    if not (exaggeration > 0 and 0 <= momentum < 1 and lr > 0):
+        raise ValueError("tsne_step: exaggeration and lr must be positive, momentum in [0, 1)")
+    work = _tsne_work(n, P.device, work)
+    L.check(L.load().mg_tsne_step(_p(P), n, _p(Y), _p(update), _p(gains), float(exaggeration), float(momentum), float(lr), _p(grad),
+                                  _p(trace), _p(cursor), cap, _p(work), work.numel(), _stream()), "mg_tsne_step")
+    return Y
+
+
 NOTE_ACC_FIELDS = (("counters", (8,)), ("pitch", (128,)), ("velocity", (128,)), ("dur16", (16,)), ("step16", (16,)),
                    ("interval", (64,)), ("pctm", (12, 12)))
 
