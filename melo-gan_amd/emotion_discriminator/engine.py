@@ -356,23 +356,7 @@ class EdEngine:
             return fn()
         key = name + ("#ticked" if name == "update" and self.P.ticked else "")
         try:
-            st = self._graphs.get(key)
-            if st is None:
-                fn()
-                self._graphs[key] = "warm"
-                return
-            if st == "warm":
-                if torch.cuda.current_stream() == torch.cuda.default_stream():
-                    raise RuntimeError("EdEngine.run: capture needs a non-default stream")
-                torch.cuda.synchronize()
-                g = ops.Graph()
-                g.begin()
-                try:
-                    fn()
-                finally:
-                    g.end()
-                self._graphs[key] = st = g
-            st.launch()
+            ops.run_graphed(self._graphs, key, fn)
         finally:
             if name.endswith("_rng"):
                 self.P.ticked = True

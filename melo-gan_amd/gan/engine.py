@@ -1422,35 +1422,20 @@ class GanEngine:
                 fp_upd.ticked = False
 
     def _run_graph(self, name: str, fn):
-        st = self._graphs.get(name)
-        if st is None:
-            fn()                                  # eager warm-up (allocates workspaces, sets func attrs)
-            self._graphs[name] = "warm"
-            return
-        if st == "warm":
-            if getattr(self, "capture_locked", False):
-                raise RuntimeError(f"GanEngine.run({name}): graph capture after DataParallel.prepare() -- every sub-step of "
-                                   "a data-parallel run must be captured before the first collective is issued")
-            st = self._capture(name, fn)
-        st[0].launch()
-        self.num_batches_tracked += st[1]
+        st = ops.run_graphed(self._graphs, name, fn, lambda f: self._capture(name, f))
+        if st is not None:
+            self.num_batches_tracked += st[1]
 
     def _capture(self, name: str, fn):
         """Capture fn's launches from the current stream into a hipGraph; returns (graph, BatchNorm forward passes it
         contains -- num_batches_tracked is host state a replay does not touch)."""
-        if torch.cuda.current_stream() == torch.cuda.default_stream():
-            raise RuntimeError("GanEngine.run: capture needs a non-default stream (use `with torch.cuda.stream(eng.stream)`)")
+        if getattr(self, "capture_locked", False):
+            raise RuntimeError(f"GanEngine.run({name}): graph capture after DataParallel.prepare() -- every sub-step of "
+                               "a data-parallel run must be captured before the first collective is issued")
         nbt = self.num_batches_tracked
-        torch.cuda.synchronize()
-        g = ops.Graph()
-        g.begin()
-        try:
-            fn()
-        finally:
-            g.end()
+        g = ops.Graph.capture(fn)
         delta, self.num_batches_tracked = self.num_batches_tracked - nbt, nbt
-        self._graphs[name] = (g, delta)
-        return self._graphs[name]
+        return g, delta                 # ops.run_graphed stores it under self._graphs[name]
 
     # -------------------------------------------------------------------------------------
     # inference (app.py:92-119: E_num -> G in eval mode)

@@ -45,10 +45,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import config as C
 from . import feature_metrics as FM
 from . import generate as G
 from . import music_metrics as MM
+from .eval_engine import EvalEngine
 from .generate import EMOTIONS, GenerateError
 from .utils import check_labels, emotion_to_index
 
@@ -66,10 +66,7 @@ class EvaluateError(GenerateError):
 # host checks
 # ---------------------------------------------------------------------------------------------------------------------
 def check_ed_config(ed_cfg: dict, cfg: dict, path: str = "ED config"):
-    try:
-        G.check_ed_config(ed_cfg, cfg)
-    except GenerateError as e:
-        raise EvaluateError(f"{path}: {e}") from e
+    G.check_ed_config(ed_cfg, cfg, err=EvaluateError, prefix=f"{path}: ")
 
 
 def check_feature_options(features: bool, knn_k: int, ed_cfg: Optional[dict]):
@@ -116,10 +113,7 @@ def check_music_options(music: bool, cfg: dict, batch: int = DEFAULT_BATCH):
 def check_checkpoint(ck, cfg: dict, path: str = "checkpoint") -> bool:
     """G and E_num as the sampler needs them; returns whether the checkpoint also holds a critic ('D') of the config's shapes."""
     from .engine import discriminator_spec
-    try:
-        G.check_generator_checkpoint(ck, cfg, path)
-    except GenerateError as e:
-        raise EvaluateError(str(e)) from e
+    G.check_generator_checkpoint(ck, cfg, path, err=EvaluateError)
     if "D" not in ck:
         return False
     spec = discriminator_spec(int(cfg["NOTE_DIM"]), 256, int(cfg.get("ENCODER_OUT_DIM", 128)))
@@ -270,29 +264,19 @@ def format_table(rep: dict) -> str:
 # ---------------------------------------------------------------------------------------------------------------------
 # the engine
 # ---------------------------------------------------------------------------------------------------------------------
-class Evaluator:
+class Evaluator(EvalEngine):
     """One GanEngine of `batch` rows in eval mode: encoder dropout off, generator BatchNorm on running statistics, no
     optimiser, no update of any buffer.  features: also keep every row's encoder features of the real and the generated roll
     and report the feature-space metrics over them (notes-mode classifier only); knn_k: the manifolds' neighbour count.
     music: also decode every real and generated row into notes and report the `music` block (NOTE_DIM 4 only)."""
+    error = EvaluateError
 
     def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH, features: bool = False,
                  knn_k: int = DEFAULT_KNN_K, music: bool = False):
         from .. import ops
-        from .engine import GanEngine
-        if int(batch) < 1:
-            raise EvaluateError(f"batch = {batch}: must be >= 1")
-        check_feature_options(features, knn_k, ed_cfg)
-        cfg = {"LR_G": 0.0, "LR_D": 0.0, **C.with_gan_defaults(cfg, require=False)}      # the rates are never used here
-        check_music_options(music, cfg, batch)
-        self.has_ed = ed_cfg is not None
-        if self.has_ed:
-            check_ed_config(ed_cfg, cfg)
-        else:       # the engine always holds a classifier: the smallest one (latent mode), never run
-            ed_cfg = dict(input_mode="latent", latent_dim=int(cfg["LATENT_DIM"]), mlp_hidden=[256, 128], n_classes=len(EMOTIONS))
-        self.cfg, self.B = cfg, int(batch)
-        self.eng = eng = GanEngine(cfg, ed_cfg, device, self.B)
-        eng.init_weights(int(cfg.get("SEED", 42)))          # defines every parameter
+        self.features, self.knn_k, self.music = bool(features), int(knn_k), bool(music)      # _check_config reads them
+        super().__init__(cfg, ed_cfg, device, batch)
+        eng = self.eng
         self.has_d = False                                  # load_critic / copy_from: the critic's weights mean something
         self.ed_real = self.has_ed and eng.ed_mode == "notes"
         d = eng.dev
@@ -301,24 +285,17 @@ class Evaluator:
         self.base = torch.zeros(1, dtype=torch.int64, device=d)
         self.acc = ops.eval_acc_new(self.K, eng.C, d)
         self.logits_real = torch.zeros(self.B, self.K, device=d)
-        self.features, self.knn_k = bool(features), int(knn_k)
         self.feat_real = self.feat_fake = self.feat_train = None      # (whole batches, notes_hidden) stashes in split row order
-        self.music = bool(music)
         self.music_buf = self.note_acc = self.note_row_i = self.note_row_beats = None      # one buffer, three views of it
-        self._graph, self._graph_key, self._hold, self._labels_host = None, None, None, None
+        self._hold = self._labels_host = None
+
+    def _check_config(self, cfg: dict, ed_cfg: Optional[dict]):
+        check_feature_options(self.features, self.knn_k, ed_cfg)
+        check_music_options(self.music, cfg, self.B)
+        if ed_cfg is not None:
+            check_ed_config(ed_cfg, cfg)
 
     # ---- weights ----
-    def load_generator(self, ck):
-        """G (with its BatchNorm running statistics) and E_num from a checkpoint dict or path."""
-        from .train_gan import load_generator_state
-        ck, path = self._read(ck)
-        try:
-            G.check_generator_checkpoint(ck, self.cfg, path)
-        except GenerateError as e:
-            raise EvaluateError(str(e)) from e
-        load_generator_state(self.eng, ck)
-        self.eng.params_changed()
-
     def load_critic(self, ck) -> bool:
         """The critic from a full gan_epochNNNN.pth (key 'D').  gan_final.pth holds none: returns False and the critic metrics
         of the report are null."""
@@ -330,15 +307,6 @@ class Evaluator:
         self.eng.params_changed()
         self.has_d = True
         return True
-
-    def load_ed(self, path: str):
-        """The frozen classifier (train_ed's ed_best.pth or a bare state_dict; spectral-norm keys folded)."""
-        from .train_gan import load_ed_checkpoint
-        if not self.has_ed:
-            raise EvaluateError("this Evaluator was built without an ED config")
-        if not os.path.isfile(path):
-            raise EvaluateError(f"ED checkpoint {path} does not exist")
-        load_ed_checkpoint(self.eng, path)
 
     def copy_from(self, src):
         """The current weights of a training engine (same configs), device to device: generator + encoder, critic, frozen
@@ -357,16 +325,6 @@ class Evaluator:
                 e.EDbuf[k].copy_(src.EDbuf[k])
             e.params_changed()
         self.has_d = True
-
-    @staticmethod
-    def _read(ck):
-        if isinstance(ck, (str, os.PathLike)):
-            path = str(ck)
-            try:
-                return G.load_checkpoint(path), path
-            except GenerateError as e:
-                raise EvaluateError(str(e)) from e
-        return ck, "checkpoint"
 
     # ---- the pass ----
     def _launches(self, jobs, order, order_len, n, seed, draw, metrics=True):
@@ -530,16 +488,9 @@ class Evaluator:
                     jobs.append((dataset.latent, eng.latent))
                 if noise is not None:
                     jobs.append((noise, eng.noise))
-                args = (jobs, order, nb * B, n, seed, noise is None)
-                self._launches(*args)          # one eager run allocates every workspace this set of launches needs
-                torch.cuda.synchronize()
-                g = ops.Graph()
-                g.begin()
-                try:
-                    self._launches(*args)
-                finally:
-                    g.end()
-                self._graph, self._graph_key, self._hold = g, key, (dataset, labels, order, noise)
+                # every new key runs eagerly first: other jobs or a music / critic switch can need other workspaces
+                self._graph_for(key, lambda: self._launches(jobs, order, nb * B, n, seed, noise is None))
+                self._hold = (dataset, labels, order, noise)
                 # the grouping of the feature metrics and of the per-row note statistics
                 self._labels_host = dataset.emot_idx.cpu() if self.features or self.music else None
             ops.eval_acc_reset(self.acc, self.K, eng.C)
@@ -641,13 +592,6 @@ class Plan:
     tsne: bool = False
 
 
-def _read_config(path: str, what: str) -> dict:
-    try:
-        return G._read_config(path, what)
-    except GenerateError as e:
-        raise EvaluateError(str(e)) from e
-
-
 def plan(args) -> Plan:
     """Every check of what comes from outside, on the host (no GPU needed); raises EvaluateError."""
     if args.batch < 1:
@@ -663,28 +607,17 @@ def plan(args) -> Plan:
     check_tsne_options(tsne, features, args.synthetic or None)
     if features and args.ed_config is None:
         check_feature_options(True, knn_k, None)
-    cfg = C.with_gan_defaults(_read_config(args.config, "config"), require=False)
-    missing = [k for k in ("NOISE_DIM", "LATENT_DIM", "MAX_NOTES", "NOTE_DIM") if k not in cfg]
-    if missing:
-        raise EvaluateError(f"config {args.config} lacks {', '.join(missing)}")
+    cfg, ckpt_path = G.plan_config(args, EvaluateError)
     if int(cfg["NOTE_DIM"]) % 4 or not 4 <= int(cfg["NOTE_DIM"]) <= 1024:
         raise EvaluateError(f"config {args.config}: NOTE_DIM = {cfg['NOTE_DIM']}: the metrics kernel reads 4 channels per lane "
                             "(a multiple of 4 in 4..1024)")
     music = bool(getattr(args, "music_metrics", False))
     check_music_options(music, cfg, args.batch)
-    if args.ed_ckpt is not None and args.ed_config is None:
-        raise EvaluateError("--ed_ckpt needs --ed_config (the classifier's architecture)")
-    if args.ed_config is not None and args.ed_ckpt is None:
-        raise EvaluateError("--ed_config needs --ed_ckpt (an untrained classifier's verdict means nothing)")
-    ckpt_path = args.ckpt or os.path.join(cfg.get("CHECKPOINT_DIR", "experiments/gan/checkpoints"), "gan_final.pth")
-    try:
-        ckpt = G.load_checkpoint(ckpt_path)
-    except GenerateError as e:
-        raise EvaluateError(str(e)) from e
+    ckpt = G.load_checkpoint(ckpt_path, err=EvaluateError)
     has_critic = check_checkpoint(ckpt, cfg, ckpt_path)
     ed_cfg = None
     if args.ed_config is not None:
-        ed_cfg = _read_config(args.ed_config, "ED config")
+        ed_cfg = G._read_config(args.ed_config, "ED config", EvaluateError)
         check_ed_config(ed_cfg, cfg, f"ED config {args.ed_config}")
         check_feature_options(features, knn_k, ed_cfg)
         if not os.path.isfile(args.ed_ckpt):

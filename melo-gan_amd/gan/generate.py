@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import config as C
+from .eval_engine import EvalEngine
 
 EMOTIONS = ("happy", "sad", "angry", "calm")          # emotion_to_index (gan/utils.py) = the classifier's class order
 # app.py:53-65 (get_gan_features): the base vector of each emotion and the jitter added to it
@@ -63,29 +64,29 @@ def check_gan_config(cfg: dict):
                             "numeric vectors")
 
 
-def check_ed_config(ed_cfg: dict, cfg: dict):
-    """The classifier must score the four emotions and read what this generator produces."""
+def check_ed_config(ed_cfg: dict, cfg: dict, err=GenerateError, prefix: str = ""):
+    """The classifier must score the four emotions and read what this generator produces.  prefix: put in front of the message."""
     n = ed_cfg.get("n_classes", 4)
     if n != len(EMOTIONS):
-        raise GenerateError(f"ED config: n_classes = {n}, the sampler scores the {len(EMOTIONS)} emotions {', '.join(EMOTIONS)}")
+        raise err(f"{prefix}ED config: n_classes = {n}, the sampler scores the {len(EMOTIONS)} emotions {', '.join(EMOTIONS)}")
     mode = ed_cfg.get("input_mode", "notes")
     if mode == "notes":
         if ed_cfg.get("note_dim", 4) != cfg["NOTE_DIM"]:
-            raise GenerateError(f"ED config: note_dim = {ed_cfg.get('note_dim', 4)} but the GAN config's NOTE_DIM = {cfg['NOTE_DIM']}")
+            raise err(f"{prefix}ED config: note_dim = {ed_cfg.get('note_dim', 4)} but the GAN config's NOTE_DIM = {cfg['NOTE_DIM']}")
     elif mode == "latent":
         if ed_cfg.get("latent_dim", 128) != cfg["LATENT_DIM"]:
-            raise GenerateError(f"ED config: latent_dim = {ed_cfg.get('latent_dim', 128)} but the GAN config's LATENT_DIM = "
-                                f"{cfg['LATENT_DIM']}")
+            raise err(f"{prefix}ED config: latent_dim = {ed_cfg.get('latent_dim', 128)} but the GAN config's LATENT_DIM = "
+                      f"{cfg['LATENT_DIM']}")
     else:
-        raise GenerateError(f"ED config: input_mode = {mode!r}, expected 'notes' or 'latent'")
+        raise err(f"{prefix}ED config: input_mode = {mode!r}, expected 'notes' or 'latent'")
 
 
-def check_generator_checkpoint(ck, cfg: dict, path: str = "checkpoint"):
+def check_generator_checkpoint(ck, cfg: dict, path: str = "checkpoint", err=GenerateError):
     """A dict with 'G' (with its BatchNorm running statistics) and 'E_num' whose tensors have the shapes the config implies."""
     from .engine import feature_encoder_spec, generator_spec
     if not isinstance(ck, dict) or "G" not in ck or "E_num" not in ck:
         have = sorted(ck) if isinstance(ck, dict) else type(ck).__name__
-        raise GenerateError(f"{path}: not a generator checkpoint (needs 'G' and 'E_num'; has {have})")
+        raise err(f"{path}: not a generator checkpoint (needs 'G' and 'E_num'; has {have})")
     gspec = generator_spec(int(cfg["NOISE_DIM"]), int(cfg["LATENT_DIM"]), cfg.get("INTEGRATION_MODE", "conditioning"), 512,
                            int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg.get("ENCODER_OUT_DIM", 128)))
     for bn, ch in (("decoder.deconv.1", 128), ("decoder.deconv.4", 64)):
@@ -96,18 +97,18 @@ def check_generator_checkpoint(ck, cfg: dict, path: str = "checkpoint"):
         sd = ck[part]
         for k, shape in spec.items():
             if k not in sd:
-                raise GenerateError(f"{path}: {part} lacks {k}")
+                raise err(f"{path}: {part} lacks {k}")
             if tuple(sd[k].shape) != tuple(shape):
-                raise GenerateError(f"{path}: {part}.{k} has shape {tuple(sd[k].shape)}, the GAN config implies {tuple(shape)}")
+                raise err(f"{path}: {part}.{k} has shape {tuple(sd[k].shape)}, the GAN config implies {tuple(shape)}")
 
 
-def load_checkpoint(path: str) -> dict:
+def load_checkpoint(path: str, err=GenerateError) -> dict:
     if not os.path.isfile(path):
-        raise GenerateError(f"checkpoint {path} does not exist")
+        raise err(f"checkpoint {path} does not exist")
     try:
         return torch.load(path, map_location="cpu")
     except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
-        raise GenerateError(f"cannot read checkpoint {path}: {e}") from e
+        raise err(f"cannot read checkpoint {path}: {e}") from e
 
 
 @dataclass
@@ -121,52 +122,24 @@ class Samples:
     summary: Dict[str, dict]            # emotion -> {n, ed_accuracy, ed_mean_p_target}
 
 
-class Sampler:
+class Sampler(EvalEngine):
     """One GanEngine of `batch` rows in eval mode: E_num -> G, and the frozen emotion classifier when ed_cfg is given."""
+    error = GenerateError
+    eager_once = True           # a new seed changes a launch argument only: the first eager run's workspaces serve
 
     def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH):
-        from .engine import GanEngine
-        if int(batch) < 1:
-            raise GenerateError(f"batch = {batch}: must be >= 1")
-        cfg = {"LR_G": 0.0, "LR_D": 0.0, **C.with_gan_defaults(cfg, require=False)}      # the rates are never used here
-        check_gan_config(cfg)
-        self.has_ed = ed_cfg is not None
-        if self.has_ed:
-            check_ed_config(ed_cfg, cfg)
-        else:       # the engine always holds a classifier: the smallest one (latent mode), never run
-            ed_cfg = dict(input_mode="latent", latent_dim=int(cfg["LATENT_DIM"]), mlp_hidden=[256, 128], n_classes=len(EMOTIONS))
-        self.cfg, self.B = cfg, int(batch)
-        self.eng = eng = GanEngine(cfg, ed_cfg, device, self.B)
-        eng.init_weights(int(cfg.get("SEED", 42)))          # defines every parameter, the critic's unused ones included
-        d = eng.dev
+        super().__init__(cfg, ed_cfg, device, batch)
+        d = self.eng.dev
         self.keys = torch.full((2, self.B), -1, dtype=torch.int32, device=d)      # (emotion, sample) of every row
         self.table = torch.tensor(EMOTION_TABLE, dtype=torch.float32, device=d)
         self.p_target = torch.zeros(self.B, device=d)
         self.pred = torch.zeros(self.B, dtype=torch.int32, device=d)
         self.acc = torch.zeros(len(EMOTIONS), 3, dtype=torch.float64, device=d)
-        self._graph, self._graph_seed, self._warm = None, None, False
 
-    def load_generator(self, ck):
-        """G (with its BatchNorm running statistics) and E_num from a checkpoint dict or path (gan_final.pth,
-        gan_epochNNNN.pth; this trainer's or the reference's)."""
-        from .train_gan import load_generator_state
-        if isinstance(ck, (str, os.PathLike)):
-            path = str(ck)
-            ck = load_checkpoint(path)
-        else:
-            path = "checkpoint"
-        check_generator_checkpoint(ck, self.cfg, path)
-        load_generator_state(self.eng, ck)
-        self.eng.params_changed()
-
-    def load_ed(self, path: str):
-        """The frozen classifier (train_ed's ed_best.pth or a bare state_dict; spectral-norm keys folded)."""
-        from .train_gan import load_ed_checkpoint
-        if not self.has_ed:
-            raise GenerateError("this Sampler was built without an ED config")
-        if not os.path.isfile(path):
-            raise GenerateError(f"ED checkpoint {path} does not exist")
-        load_ed_checkpoint(self.eng, path)
+    def _check_config(self, cfg: dict, ed_cfg: Optional[dict]):
+        check_gan_config(cfg)
+        if ed_cfg is not None:
+            check_ed_config(ed_cfg, cfg)
 
     def _launches(self, seed: int):
         from .. import ops
@@ -178,25 +151,6 @@ class Sampler:
         if self.has_ed:
             eng._ed_fwd(eng.notes)
             ops.emotion_score(eng.logits, self.keys[0], self.p_target, self.pred, self.acc)
-
-    def _graph_for(self, seed: int):
-        """The chunk graph of this seed (the seed is a launch argument): captured on first use, after one eager run that
-        allocates every workspace."""
-        from .. import ops
-        if self._graph is not None and self._graph_seed == seed:
-            return self._graph
-        if not self._warm:
-            self._launches(seed)
-            self._warm = True
-        torch.cuda.synchronize()
-        g = ops.Graph()
-        g.begin()
-        try:
-            self._launches(seed)
-        finally:
-            g.end()
-        self._graph, self._graph_seed = g, seed
-        return g
 
     def sample(self, emotions: Sequence[str], samples: int, seed: int) -> Samples:
         names = []
@@ -213,7 +167,7 @@ class Sampler:
         pred = np.empty(M, np.int64) if self.has_ed else None
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         with torch.cuda.stream(eng.stream):
-            g = self._graph_for(seed)
+            g = self._graph_for(seed, lambda: self._launches(seed))
             self.acc.zero_()
             for c0 in range(0, M, B):
                 chunk = keys[c0:c0 + B]
@@ -269,13 +223,27 @@ class Plan:
     batch: int
 
 
-def _read_config(path: str, what: str) -> dict:
+def _read_config(path: str, what: str, err=GenerateError) -> dict:
     if not os.path.isfile(path):
-        raise GenerateError(f"{what} {path} does not exist")
+        raise err(f"{what} {path} does not exist")
     cfg = C.load_config(path)
     if not isinstance(cfg, dict):
-        raise GenerateError(f"{what} {path} is not a YAML mapping")
+        raise err(f"{what} {path} is not a YAML mapping")
     return cfg
+
+
+def plan_config(args, err=GenerateError):
+    """What generate's and evaluate's command lines share: the GAN config with its defaults and the keys every later check
+    reads, the pairing of --ed_ckpt with --ed_config, and the checkpoint's path.  Returns (cfg, checkpoint path)."""
+    cfg = C.with_gan_defaults(_read_config(args.config, "config", err), require=False)
+    missing = [k for k in ("NOISE_DIM", "LATENT_DIM", "MAX_NOTES", "NOTE_DIM") if k not in cfg]
+    if missing:
+        raise err(f"config {args.config} lacks {', '.join(missing)}")
+    if args.ed_ckpt is not None and args.ed_config is None:
+        raise err("--ed_ckpt needs --ed_config (the classifier's architecture)")
+    if args.ed_config is not None and args.ed_ckpt is None:
+        raise err("--ed_config needs --ed_ckpt (an untrained classifier's verdict means nothing)")
+    return cfg, args.ckpt or os.path.join(cfg.get("CHECKPOINT_DIR", "experiments/gan/checkpoints"), "gan_final.pth")
 
 
 def plan(args) -> Plan:
@@ -283,21 +251,13 @@ def plan(args) -> Plan:
     emotions = emotion_names(args.emotion)
     if args.batch < 1:
         raise GenerateError(f"--batch {args.batch}: must be >= 1")
-    cfg = C.with_gan_defaults(_read_config(args.config, "config"), require=False)
-    missing = [k for k in ("NOISE_DIM", "LATENT_DIM", "MAX_NOTES", "NOTE_DIM") if k not in cfg]
-    if missing:
-        raise GenerateError(f"config {args.config} lacks {', '.join(missing)}")
+    cfg, ckpt_path = plan_config(args)
     samples = args.samples if args.samples is not None else int(cfg.get("N_SAMPLES_PER_EMOTION", 2))
     if samples < 1:
         raise GenerateError(f"--samples {samples}: must be >= 1")
     check_gan_config(cfg)
     if int(cfg["NOTE_DIM"]) != 4:
         raise GenerateError(f"NOTE_DIM = {cfg['NOTE_DIM']}: the MIDI writer reads (pitch, velocity, duration, step) rows")
-    if args.ed_ckpt is not None and args.ed_config is None:
-        raise GenerateError("--ed_ckpt needs --ed_config (the classifier's architecture)")
-    if args.ed_config is not None and args.ed_ckpt is None:
-        raise GenerateError("--ed_config needs --ed_ckpt (an untrained classifier's verdict means nothing)")
-    ckpt_path = args.ckpt or os.path.join(cfg.get("CHECKPOINT_DIR", "experiments/gan/checkpoints"), "gan_final.pth")
     ckpt = load_checkpoint(ckpt_path)
     check_generator_checkpoint(ckpt, cfg, ckpt_path)
     ed_cfg = None

@@ -261,6 +261,10 @@ class Tsne:
                 ops.tsne_step(P, Y, update, gains, ee, mom, lr, trace=trace if traced else None,
                               cursor=cursor if traced else None, work=work)
 
+            def block(it0):
+                for k in range(te):
+                    one(it0 + k, k == te - 1)
+
             it = 0
             while it < self.iters:
                 if it == self.exaggeration_iters and it > 0:      # scikit-learn runs _gradient_descent once per phase
@@ -271,13 +275,7 @@ class Tsne:
                 if self.graphs and it % te == 0 and it + te <= end and te > 1:      # a whole block inside one phase: replay
                     g = graphs.get(phase)
                     if g is None:                   # te iterations of this phase, the last one traced; capturing runs nothing
-                        g = graphs[phase] = ops.Graph(execs=1)
-                        g.begin()
-                        try:
-                            for k in range(te):
-                                one(it + k, k == te - 1)
-                        finally:
-                            g.end()
+                        g = graphs[phase] = ops.Graph.capture(lambda: block(it), execs=1)
                     g.launch()
                     it += te
                 else:

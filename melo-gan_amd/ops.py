@@ -2109,6 +2109,21 @@ class Graph:
         L.check(L.load().mg_graph_end(_stream(), self.handles, self.n), "mg_graph_end")
         self.kernel_nodes = L.load().mg_graph_last_kernel_nodes()      # launches one replay stands for
 
+    @staticmethod
+    def capture(fn, execs: Optional[int] = None) -> "Graph":
+        """The graph of what fn() enqueues on PyTorch's current stream.  Nothing runs: the caller has run fn eagerly before
+        wherever its launches allocate workspaces.  The capture ends even when fn raises."""
+        if torch.cuda.current_stream() == torch.cuda.default_stream():
+            raise RuntimeError("Graph.capture: capture needs a non-default stream (use `with torch.cuda.stream(...)`)")
+        torch.cuda.synchronize()
+        g = Graph(execs)
+        g.begin()
+        try:
+            fn()
+        finally:
+            g.end()
+        return g
+
     def launch(self):
         h = self.handles[self._next]
         self._next = (self._next + 1) % self.n
@@ -2125,6 +2140,22 @@ class Graph:
             self.release()
         except Exception:
             pass
+
+
+def run_graphed(graphs: dict, key: str, fn, capture=Graph.capture):
+    """One call of a sub-step that is replayed as a hipGraph.  graphs[key] goes None -> "warm" -> captured: the first call
+    runs fn eagerly (which allocates every workspace and sets the function attributes), the second captures and launches,
+    later ones launch.  capture(fn) makes what is stored here -- a Graph, or GanEngine's (Graph, BatchNorm passes) -- and may
+    refuse.  Returns the stored entry when a graph was launched, None after the eager call."""
+    st = graphs.get(key)
+    if st is None:
+        fn()
+        graphs[key] = "warm"
+        return None
+    if st == "warm":
+        st = graphs[key] = capture(fn)
+    (st[0] if isinstance(st, tuple) else st).launch()
+    return st
 
 
 class Event:

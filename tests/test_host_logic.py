@@ -109,3 +109,62 @@ def test_spectral_norm_checkpoint_weights_fold_at_load():
         got = spectral_norm_weight(sd, "x.weight")
         torch.testing.assert_close(got, m.weight.detach(), rtol=1e-6, atol=1e-7)
     assert spectral_norm_weight({"x.weight": torch.ones(2)}, "x.weight").sum() == 2 and spectral_norm_weight({}, "x.weight") is None
+
+
+def test_run_graphed_goes_eager_then_captures_then_replays():
+    """ops.run_graphed, the one copy of the training engines' None -> "warm" -> captured step, with a stand-in capture: the
+    dict keeps the format bench.py and the tests read ("warm", then what capture returned: a graph or a tuple led by one)."""
+    from melo_gan_amd import ops
+
+    class FakeGraph:
+        launches = 0
+
+        def launch(self):
+            self.launches += 1
+
+    for wrap in (lambda g: g, lambda g: (g, 2)):
+        graphs, calls, g = {}, [], FakeGraph()
+
+        def capture(fn):
+            calls.append("capture")
+            return wrap(g)
+
+        fn = lambda: calls.append("eager")  # noqa: E731
+        assert ops.run_graphed(graphs, "k", fn, capture) is None and graphs == {"k": "warm"} and calls == ["eager"]
+        for n in (1, 2, 3):
+            assert ops.run_graphed(graphs, "k", fn, capture) is graphs["k"] and graphs["k"] == wrap(g) and g.launches == n
+        assert calls == ["eager", "capture"]
+        # a capture that raises leaves the key warm: the next call captures again
+        graphs["j"] = "warm"
+        with pytest.raises(RuntimeError):
+            ops.run_graphed(graphs, "j", fn, lambda f: (_ for _ in ()).throw(RuntimeError("locked")))
+        assert graphs["j"] == "warm"
+
+
+def test_eval_engine_graph_cache_rules(monkeypatch):
+    """EvalEngine._graph_for with a stand-in for ops.Graph.capture: the Sampler runs eagerly once in its life and re-captures
+    on a new seed; the Evaluator runs eagerly in front of every capture, a returning key included; neither touches a graph
+    whose key holds.  A capture that raises leaves the old key: the next call captures again."""
+    from melo_gan_amd import ops
+    from melo_gan_amd.gan.evaluate import Evaluator
+    from melo_gan_amd.gan.generate import Sampler
+    log = []
+    monkeypatch.setattr(ops.Graph, "capture", staticmethod(lambda fn: (log.append("capture"), fn(), object())[-1]))
+    for cls, want in ((Sampler, ["launch", "capture", "launch", "capture", "launch", "capture", "launch"]),
+                      (Evaluator, ["launch", "capture", "launch", "launch", "capture", "launch", "launch", "capture", "launch"])):
+        e = object.__new__(cls)                 # the cache alone: no engine, no device
+        e._graph, e._graph_key, e._warm = None, None, False
+        del log[:]
+        launches = lambda: log.append("launch")  # noqa: E731
+        g1 = e._graph_for(1, launches)
+        assert e._graph_for(1, launches) is g1
+        g2 = e._graph_for(2, launches)
+        assert g2 is not g1 and e._graph_for(2, launches) is g2
+        assert e._graph_for(1, launches) not in (g1, g2)
+        assert log == want, (cls.__name__, log)
+
+        def fail():
+            raise RuntimeError("capture failed")
+        with pytest.raises(RuntimeError):
+            e._graph_for(3, fail)
+        assert e._graph_key == 1

@@ -469,3 +469,43 @@ def test_dhead_fwd_bwd_equals_separate_launches():
         assert torch.equal(s0, s1) and torch.equal(dU0, dU1)
         if with_demb:
             assert torch.equal(de0, de1)
+
+
+def test_graph_capture_refuses_the_default_stream_ends_on_an_exception_and_replays(ops):
+    """ops.Graph.capture: (a) on the default stream it raises before anything is enqueued; (b) an exception of fn's
+    propagates and leaves the stream out of capture mode; (c) three replays of y += x give y0 + 3 x exactly (small integers:
+    every sum is exact in fp32)."""
+    x = torch.arange(1024, dtype=torch.float32).cuda()
+    y0 = (torch.arange(1024, dtype=torch.float32) % 7).cuda()
+    y = y0.clone()
+    calls = []
+
+    def add():
+        calls.append(1)
+        ops.axpby(x, y, 1.0, 1.0)
+
+    def add_and_fail():
+        add()
+        raise ValueError("after the launch")
+
+    with pytest.raises(RuntimeError, match=r"with torch\.cuda\.stream"):
+        ops.Graph.capture(add)
+    assert not calls
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with pytest.raises(ValueError, match="after the launch"):
+            ops.Graph.capture(add_and_fail)
+        assert not torch.cuda.is_current_stream_capturing()
+        torch.cuda.synchronize()
+        assert torch.equal(y, y0)                   # the captured launch never ran
+        add()                                       # eager again on the same stream
+        torch.cuda.synchronize()
+        assert torch.equal(y, y0 + x)
+        y.copy_(y0)
+        g = ops.Graph.capture(add)
+        assert g.kernel_nodes == 1
+        for _ in range(3):
+            g.launch()
+        torch.cuda.synchronize()
+        assert torch.equal(y, y0 + 3 * x)

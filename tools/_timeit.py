@@ -8,11 +8,10 @@ def timeit(fn, reps=20):
     with torch.cuda.stream(s):
         for _ in range(2):
             fn()
-        torch.cuda.synchronize()
-        g = ops.Graph(); g.begin()
-        for _ in range(reps):
-            fn()
-        g.end()
+        def body():
+            for _ in range(reps):
+                fn()
+        g = ops.Graph.capture(body)
         g.launch(); torch.cuda.synchronize()
         e0, e1 = ops.Event(), ops.Event()
         e0.record(); g.launch(); g.launch(); e1.record()

@@ -4,7 +4,8 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, melo_gan_amd  # noqa
 from melo_gan_amd import ops
-from layer_bench import timeit, R  # noqa
+from _timeit import timeit  # noqa
+from layer_bench import R  # noqa
 
 def wq_of(w, N, Cc, sn, sc):
     wq = torch.empty(N * Cc * 5, device="cuda"); ops.wq_relayout(w, wq, N, Cc, 5, sn, sc); return wq

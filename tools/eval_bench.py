@@ -80,14 +80,7 @@ def batch_graphs(ev, ds, n, variants):
     graphs = {}
     for name, prepare in variants:
         metrics = prepare()
-        torch.cuda.synchronize()
-        g = ops.Graph()
-        g.begin()
-        try:
-            ev._launches(jobs, order, n, n, 1, True, metrics=metrics)
-        finally:
-            g.end()
-        graphs[name] = g
+        graphs[name] = ops.Graph.capture(lambda: ev._launches(jobs, order, n, n, 1, True, metrics=metrics))
     return graphs
 
 

@@ -10,19 +10,7 @@ if os.environ.get("MELO_LIB_VARIANT"):      # a tools/build_variant.sh build
     _lib.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_build", "libmelogan_" + os.environ["MELO_LIB_VARIANT"] + ".so")
 from melo_gan_amd import ops
 
-def timeit(fn, reps=20):
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        for _ in range(2): fn()
-        torch.cuda.synchronize()
-        g = ops.Graph(); g.begin()
-        for _ in range(reps): fn()
-        g.end()
-        g.launch(); torch.cuda.synchronize()
-        e0, e1 = ops.Event(), ops.Event()
-        e0.record(); g.launch(); g.launch(); e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_ms(e1) / (2 * reps) * 1e3
+from _timeit import timeit  # noqa: E402  (after LIB_PATH is set: it imports ops too)
 
 def R(*s): return torch.randn(*s, device='cuda')
 B = 64
