@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ invstd, int act, long R,
                                                              int C, long rows_per, double* __restrict__ part,
-                                                             int want_sq, const float* __restrict__ gamma = nullptr,
+                                                             int want_sq, int al16, const float* __restrict__ gamma = nullptr,
                                                              const float* __restrict__ beta = nullptr) {
     __shared__ double sh[2][16][65];
     // blockIdx.z = row group (BatchNorm over several independent batches in one launch): R rows each, contiguous
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
     long r1 = r0 + rows_per;
     if (r1 > R) r1 = R;
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    const bool vec = ((C & 3) == 0) && (c0 + 3 < C);
+    const bool vec = al16 && (c0 + 3 < C);      // al16: C % 4 == 0 and 16-byte aligned tensors (vec_ok, host side)
     if (c0 < C) {
         float mu[4] = {0, 0, 0, 0}, is[4] = {0, 0, 0, 0}, ga[4] = {1, 1, 1, 1}, be[4] = {0, 0, 0, 0};
         const bool pre = MODE == 1 && act == MG_ACT_GELU;       // GELU' needs the BN output, not the activation
@@ -109,6 +109,13 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
             part[((long)blockIdx.y * 2 + w) * C + c] = t;
         }
     }
+}
+
+// The 16-byte path of the column-sum / BatchNorm kernels: C % 4 == 0 (every row then starts as aligned as the tensor) and
+// every tensor the launch touches with float4 accesses 16-byte aligned.  Evaluated on the host; otherwise the scalar path.
+template <class... P>
+int vec_ok(int C, P... ptrs) {
+    return (C & 3) == 0 && ((((uintptr_t)ptrs | ...) & 15) == 0);
 }
 
 struct RedPlan { int nsplit; long rows_per; };
@@ -266,7 +273,7 @@ __global__ __launch_bounds__(BNA_THREADS) void bn_parts_apply_kernel(const PT* _
                                                              float momentum, float eps, float* running_mean, float* running_var,
                                                              float* save_mean, float* save_invstd, const float* __restrict__ z,
                                                              float* __restrict__ a, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, int act, long rows_per) {
+                                                             const float* __restrict__ beta, int act, long rows_per, int al16) {
     __shared__ double sh[4 * BNA_PL][64];
     __shared__ float s_mean[64], s_istd[64];
     const int c0 = blockIdx.x * 64, cx = threadIdx.x & 63;
@@ -306,7 +313,7 @@ __global__ __launch_bounds__(BNA_THREADS) void bn_parts_apply_kernel(const PT* _
     const long r0 = (long)blockIdx.y * rows_per;
     long r1 = r0 + rows_per;
     if (r1 > R) r1 = R;
-    const bool vec = ((C & 3) == 0) && (c + 3 < C);
+    const bool vec = al16 && (c + 3 < C);
     double mu[4], is[4], ga[4], be[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -351,7 +358,7 @@ __global__ __launch_bounds__(BNA_THREADS) void bn_bwd_parts_apply_kernel(const P
                                                                  const float* __restrict__ z, float* __restrict__ dz,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                                 float* dgamma, float* dbeta, int act, long rows_per) {
+                                                                 float* dgamma, float* dbeta, int act, long rows_per, int al16) {
     __shared__ double sh[2 * BNA_PL][64];
     __shared__ double s1[64], s2[64];
     const int c0 = blockIdx.x * 64, cx = threadIdx.x & 63, pl = threadIdx.x >> 6;
@@ -394,7 +401,7 @@ __global__ __launch_bounds__(BNA_THREADS) void bn_bwd_parts_apply_kernel(const P
     const long r0 = (long)blockIdx.y * rows_per;
     long r1 = r0 + rows_per;
     if (r1 > R) r1 = R;
-    const bool vec = ((C & 3) == 0) && (c + 3 < C);
+    const bool vec = al16 && (c + 3 < C);
     const bool pre = act == MG_ACT_GELU;
     const double invR = 1.0 / (double)R;
     double mu[4], is[4], ga[4], be[4], k1[4], k2[4];
@@ -1478,7 +1485,7 @@ int mg_colsum(const float* x, long R, int C, float* sum, float* sumsq, void* wor
     const RedPlan pl = red_plan(R);
     dim3 grid((unsigned)mg_cdiv(C, 64), (unsigned)pl.nsplit);
     hipLaunchKernelGGL(colsum_partial_kernel<0>, grid, dim3(256), 0, ST, x, nullptr, nullptr, nullptr, nullptr, 0, R, C,
-                       pl.rows_per, (double*)work, sumsq ? 1 : 0);
+                       pl.rows_per, (double*)work, sumsq ? 1 : 0, vec_ok(C, x));
     hipLaunchKernelGGL(colsum_final_kernel, dim3(nblk(C, FIN_CH)), dim3(256), 0, ST, (const double*)work, pl.nsplit, C, sum, sumsq);
     MG_CHECK_LAUNCH("colsum");
     return MG_OK;
@@ -1507,13 +1514,13 @@ int mg_bn_train_fwd(const float* z, float* a, long R, int C, int groups, const f
     const RedPlan pl = red_plan(R);
     dim3 grid((unsigned)mg_cdiv(C, 64), (unsigned)pl.nsplit, (unsigned)groups);
     hipLaunchKernelGGL(colsum_partial_kernel<0>, grid, dim3(256), 0, ST, z, nullptr, nullptr, nullptr, nullptr, 0, R, C,
-                       pl.rows_per, (double*)work, 1);
+                       pl.rows_per, (double*)work, 1, vec_ok(C, z));
     const long cb = mg_cdiv(C, 64);
     long slices;
     const long rows_per = bn_row_slices(R, C, groups, &slices);
     hipLaunchKernelGGL(bn_parts_apply_kernel<double>, dim3((unsigned)cb, (unsigned)slices, (unsigned)groups), dim3(BNA_THREADS), 0, ST,
                        (const double*)work, pl.nsplit, groups, R, C, momentum, eps, running_mean, running_var, save_mean,
-                       save_invstd, z, a, gamma, beta, act, rows_per);
+                       save_invstd, z, a, gamma, beta, act, rows_per, vec_ok(C, z, a));
     MG_CHECK_LAUNCH("bn_train_fwd");
     return MG_OK;
 }
@@ -1529,7 +1536,7 @@ int mg_bn_train_fwd_parts(const float* part, int part_rows_per_group, int groups
     const long rows_per = bn_row_slices(R, C, groups, &slices);
     hipLaunchKernelGGL(bn_parts_apply_kernel<float>, dim3((unsigned)cb, (unsigned)slices, (unsigned)groups), dim3(BNA_THREADS), 0, ST, part,
                        part_rows_per_group, groups, R, C, momentum, eps, running_mean, running_var, save_mean, save_invstd, z, a,
-                       gamma, beta, act, rows_per);
+                       gamma, beta, act, rows_per, vec_ok(C, z, a));
     MG_CHECK_LAUNCH("bn_train_fwd_parts");
     return MG_OK;
 }
@@ -1537,19 +1544,21 @@ int mg_bn_train_fwd_parts(const float* part, int part_rows_per_group, int groups
 int mg_bn_train_bwd(const float* da, const float* a, const float* z, float* dz, long R, int C, const float* gamma,
                     const float* beta, const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
                     int act, void* work, size_t work_bytes, mg_stream_t stream) {
-    MG_CHECK_ARG(da && a && z && dz && gamma && save_mean && save_invstd && dgamma && dbeta, "mg_bn_train_bwd: bad args");
+    MG_CHECK_ARG(da && a && z && dz && gamma && save_mean && save_invstd && dgamma && dbeta && R > 0 && C > 0,
+                 "mg_bn_train_bwd: bad args");
     MG_CHECK_ARG(act != MG_ACT_GELU || beta, "mg_bn_train_bwd: GELU needs beta (its derivative is taken at the BN output)");
     if (!work || work_bytes < mg_bn_workspace_bytes(C, 1)) { mg_set_error("mg_bn_train_bwd: workspace too small"); return MG_EWORK; }
     const RedPlan pl = red_plan(R);
     double* part = (double*)work;
     dim3 grid((unsigned)mg_cdiv(C, 64), (unsigned)pl.nsplit);
     hipLaunchKernelGGL(colsum_partial_kernel<1>, grid, dim3(256), 0, ST, da, a, z, save_mean, save_invstd, act, R, C,
-                       pl.rows_per, part, 1, gamma, beta);
+                       pl.rows_per, part, 1, vec_ok(C, da, a, z), gamma, beta);
     const long cb = mg_cdiv(C, 64);
     long slices;
     const long rows_per = bn_row_slices(R, C, 1, &slices);
     hipLaunchKernelGGL(bn_bwd_parts_apply_kernel<double>, dim3((unsigned)cb, (unsigned)slices), dim3(BNA_THREADS), 0, ST, (const double*)part,
-                       pl.nsplit, C, R, da, a, z, dz, gamma, beta, save_mean, save_invstd, dgamma, dbeta, act, rows_per);
+                       pl.nsplit, C, R, da, a, z, dz, gamma, beta, save_mean, save_invstd, dgamma, dbeta, act, rows_per,
+                       vec_ok(C, da, a, z, dz));
     MG_CHECK_LAUNCH("bn_train_bwd");
     return MG_OK;
 }
@@ -1564,14 +1573,14 @@ int mg_bn_train_bwd_parts(const double* part, int part_rows, const float* da, co
     long slices;
     const long rows_per = bn_row_slices(R, C, 1, &slices);
     hipLaunchKernelGGL(bn_bwd_parts_apply_kernel<double>, dim3((unsigned)cb, (unsigned)slices), dim3(BNA_THREADS), 0, ST, part, part_rows,
-                       C, R, da, a, z, dz, gamma, beta, save_mean, save_invstd, dgamma, dbeta, act, rows_per);
+                       C, R, da, a, z, dz, gamma, beta, save_mean, save_invstd, dgamma, dbeta, act, rows_per, vec_ok(C, da, a, z, dz));
     MG_CHECK_LAUNCH("bn_train_bwd_parts");
     return MG_OK;
 }
 
 int mg_bn_eval_fwd(const float* z, float* a, long R, int C, const float* gamma, const float* beta,
                    const float* running_mean, const float* running_var, float eps, int act, mg_stream_t stream) {
-    MG_CHECK_ARG(z && a && gamma && beta && running_mean && running_var, "mg_bn_eval_fwd: bad args");
+    MG_CHECK_ARG(z && a && gamma && beta && running_mean && running_var && R > 0 && C > 0, "mg_bn_eval_fwd: bad args");
     hipLaunchKernelGGL(bn_eval_kernel, dim3(nblk(R * C)), dim3(256), 0, ST, z, a, R * C, C, gamma, beta, running_mean,
                        running_var, eps, act);
     MG_CHECK_LAUNCH("bn_eval_fwd");
@@ -1621,7 +1630,7 @@ int mg_layernorm_fwd(const float* x, float* y, float* xhat, int B, int D, const 
 
 int mg_layernorm_bwd_params(const float* dy, const float* xhat, float* dgamma, float* dbeta, int B, int D,
                             mg_stream_t stream) {
-    MG_CHECK_ARG(dy && xhat && dgamma && dbeta && D <= 64, "mg_layernorm_bwd_params: bad args");
+    MG_CHECK_ARG(dy && xhat && dgamma && dbeta && B > 0 && D > 0 && D <= 64, "mg_layernorm_bwd_params: bad args (0<D<=64)");
     hipLaunchKernelGGL(layernorm_bwd_params_kernel, dim3(1), dim3(256), 0, ST, dy, xhat, dgamma, dbeta, B, D);
     MG_CHECK_LAUNCH("layernorm_bwd_params");
     return MG_OK;

@@ -2049,8 +2049,12 @@ def reparam_fwd(mu, logvar, eps, z):
 
 
 def reparam_bwd(dz, logvar, eps, dmu_kld, dlv_kld, dmu, dlv):
-    for t in (dz, logvar, eps, dmu_kld, dlv_kld, dmu, dlv):
+    """dmu_kld / dlv_kld may be None: the gradient of the reparameterisation alone."""
+    for t in (dz, logvar, eps, dmu, dlv):
         _chk(t, "t", dz.shape)
+    for t in (dmu_kld, dlv_kld):
+        if t is not None:
+            _chk(t, "t", dz.shape)
     L.check(L.load().mg_reparam_bwd(_p(dz), _p(logvar), _p(eps), _p(dmu_kld), _p(dlv_kld), _p(dmu), _p(dlv),
                                     dz.numel(), _stream()), "mg_reparam_bwd")
 

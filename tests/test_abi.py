@@ -53,6 +53,13 @@ def test_bad_arguments_are_rejected_before_any_launch():
     st[0].dst_pitch, st[0].src_rows = 0, 2
     assert lib.mg_stage_rows(st, 1, 4, None) == -1                      # unindexed source shorter than the batch
     assert lib.mg_dhead_fwd_bwd(None, None, None, None, None, None, None, None, 4, 4, 8, 8, 0, None) == -1
+    # empty shapes (non-null dummy addresses): R = 0 used to reach the launch plan of mg_bn_train_bwd, which divides by the rows per slice
+    q = 256
+    for R_, C_ in ((0, 64), (64, 0)):
+        assert lib.mg_bn_train_bwd(q, q, q, q, R_, C_, q, None, q, q, q, q, 1, q, 1 << 24, None) == -1 and b"mg_bn_train_bwd" in lib.mg_last_error()
+        assert lib.mg_bn_eval_fwd(q, q, R_, C_, q, q, q, q, 1e-5, 0, None) == -1 and b"mg_bn_eval_fwd" in lib.mg_last_error()
+    for B_, D_ in ((0, 6), (4, 0), (4, 65)):
+        assert lib.mg_layernorm_bwd_params(q, q, q, q, B_, D_, None) == -1 and b"mg_layernorm_bwd_params" in lib.mg_last_error()
 
 
 def test_lds_pad_outside_its_range_is_rejected_on_the_host():
