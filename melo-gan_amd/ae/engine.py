@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from .. import ops
-from ..gan.engine import FlatParams, BN_EPS, BN_MOM
+from ..gan.engine import FlatParams, BN_EPS, BN_MOM, norm_buffers
 from ..ops import ACT_RELU, ACT_TANH
 
 ENC = ((0, 4, 32), (3, 32, 64), (6, 64, 128))       # (index in encoder.conv, Cin, Cout)
@@ -64,7 +64,7 @@ class VaeEngine:
             self.P, self.buf = share.P, share.buf
         else:
             self.P = FlatParams(spec, d)
-            self.buf = {k: (torch.ones(s, device=d) if k.endswith("running_var") else torch.zeros(s, device=d)) for k, s in bufs.items()}
+            self.buf = norm_buffers(bufs, d)
         self._tails = {}
         z = lambda *s: torch.zeros(*s, device=d)  # noqa: E731
         self.x, self.eps = z(B, T, 4), z(B, self.latent)

@@ -1,7 +1,9 @@
 """Pre-training of the emotion discriminator on MI355X: one step of
 /root/reference/src/emotion_discriminator/train_ed.py:51-82 -- train-mode forward (BatchNorm batch statistics, classifier
 dropout), mean cross-entropy, backward, AdamW -- over libmelogan_hip.  The frozen, eval-mode use of the same network on
-the GAN hot path lives in melo_gan_amd.gan.engine.GanEngine.
+the GAN hot path lives in melo_gan_amd.gan.engine.GanEngine; the MLP tail's per-layer launches (layers.tail_fwd / tail_bwd)
+are shared with it.  EdEngine's constructor builds what every classifier engine needs and then the input side (_init_input):
+the convolutional encoder here, the batch of latents in latent_engine.EdLatentEngine.
 
 Layout: activations (B, T, C) channels-last like everywhere else; parameters / gradients / Adam moments in one flat
 fp32 buffer each (one fused AdamW launch); BatchNorm running statistics in `buf`.  Backward is hand-derived:
@@ -15,14 +17,16 @@ per forward runs the power iteration (training mode) and writes the effective we
 from __future__ import annotations
 
 import math
+import os
 from collections import OrderedDict
 from typing import Dict, Optional, Sequence
 
 import torch
 
 from .. import ops
-from ..ops import ACT_GELU, ACT_NONE
-from ..gan.engine import FlatParams, emotion_disc_spec
+from ..ops import ACT_GELU
+from ..gan.engine import FlatParams, emotion_disc_spec, norm_buffers
+from .layers import tail_bwd, tail_fwd
 
 Tensor = torch.Tensor
 
@@ -30,19 +34,22 @@ Tensor = torch.Tensor
 class EdEngine:
     """One replica of the emotion discriminator's training state on one GPU (input_mode == 'notes')."""
 
+    input_mode = "notes"
+    _mode_error = ("EdEngine pre-trains input_mode='notes' (the convolutional encoder); input_mode='latent' is "
+                   "latent_engine.EdLatentEngine (latent_engine.make_engine picks by input_mode)")
+
     def __init__(self, cfg: dict, device="cuda", batch_size: Optional[int] = None, max_notes: Optional[int] = None,
                  share: Optional["EdEngine"] = None):
-        """share: another EdEngine whose parameters, optimiser state, BatchNorm buffers and Philox counter this one
+        """What every classifier engine needs -- parameters, optimiser settings, spectral-norm state, the MLP tail's
+        activations, the Philox counter, the staged split's fields -- then the input side (_init_input).
+        share: another engine of this class whose parameters, optimiser state, BatchNorm buffers and Philox counter this one
         uses as its own -- the same model at a different batch size (the trailing partial batch of an epoch: the
         reference's loaders have no drop_last, ed_dataset.py:542-558)."""
-        if cfg.get("input_mode", "latent") != "notes":
-            raise ValueError("EdEngine pre-trains input_mode='notes' (the convolutional encoder); input_mode='latent' is "
-                             "latent_engine.EdLatentEngine (latent_engine.make_engine picks by input_mode)")
+        if cfg.get("input_mode", "latent") != self.input_mode:
+            raise ValueError(self._mode_error)
         self.cfg = cfg
         self.dev = d = torch.device(device)
         self.B = B = int(batch_size or cfg.get("batch_size", 64))
-        self.T = T = int(max_notes or cfg.get("max_notes", 512))
-        self.C = C = int(cfg.get("note_dim", 4))
         self.n_classes = int(cfg.get("n_classes", 4))
         self.p_drop = float(cfg.get("dropout", 0.2))
         opt = cfg.get("optimizer", {})
@@ -50,33 +57,20 @@ class EdEngine:
         self.betas = tuple(float(b) for b in opt.get("betas", (0.9, 0.999)))
         self.weight_decay = float(opt.get("weight_decay", 0.0))
         self.decoupled = str(opt.get("name", "adamw")).lower() == "adamw"
-        spec, bufs, chans = emotion_disc_spec(cfg)
+        spec, bufs, self.chans = emotion_disc_spec(cfg)          # latent mode: no buffers, no convolutions
         if share is not None:
             if share.P.spec != spec:
-                raise ValueError("EdEngine(share=...): the two engines must have the same model configuration")
+                raise ValueError(f"{type(self).__name__}(share=...): the two engines must have the same model configuration")
             self.P, self.buf = share.P, share.buf
         else:
             self.P = FlatParams(spec, d)
-            self.buf: Dict[str, Tensor] = OrderedDict()
-            for k, s in bufs.items():
-                self.buf[k] = torch.ones(s, device=d) if k.endswith("running_var") else torch.zeros(s, device=d)
-        self.chans = chans
-        self.mlp = tuple(cfg.get("mlp_hidden", (256, 128)))
-        # three-tap layers by minimal filtering (csrc/conv_wino.hip: 2/3 of the direct form's matrix-pipe work) where the
-        # problem is big enough to be bound by it: forward with >= 128 output columns, data-gradient with >= 128 input channels
-        # (the GAN engine's rule); the weights change every step, so both filter images of every such layer are transformed
-        # by ONE launch at the top of the step.  MELO_ED_WINO=0: the direct window GEMMs.
-        import os
-        wino = os.environ.get("MELO_ED_WINO", "1") == "1" and B * T >= 4096
-        self.wino_f = [bool(wino and k == 3 and co >= 128 and ops.wino3_supported(B, T, ci, co)) for (ci, co, k) in chans]
-        self.wino_d = [bool(wino and k == 3 and ci >= 128 and i > 0 and ops.wino3_supported(B, T, co, ci)) for i, (ci, co, k) in enumerate(chans)]
-        wimg = lambda on, cin, n: torch.zeros(cin // 4, 4, n, 4, device=d) if on else None  # noqa: E731
-        self.wino_wf = [wimg(f_, ci, co) for f_, (ci, co, _) in zip(self.wino_f, chans)]
-        self.wino_wd = [wimg(f_, co, ci) for f_, (ci, co, _) in zip(self.wino_d, chans)]
+            self.buf: Dict[str, Tensor] = norm_buffers(bufs, d)
+        self.mlp = tuple(int(h) for h in cfg.get("mlp_hidden", (256, 128)))
+        self.names = [f"classifier.net.{3 * j}" for j in range(len(self.mlp))] + ["classifier.head"]      # the MLP tail's layers
         # spectral normalisation: which layers, their u / v buffers (module state), effective weights and sigmas (derived)
         self.sn_names = []
         if cfg.get("use_spectral_norm", False):
-            self.sn_names = [f"encoder.conv.{i}.net.0" for i in range(len(chans))] + [f"classifier.net.{3 * j}" for j in range(len(self.mlp))]
+            self.sn_names = [f"encoder.conv.{i}.net.0" for i in range(len(self.chans))] + self.names[:-1]
         if share is not None:
             self.w_eff, self.sn_sigma = share.w_eff, share.sn_sigma
         else:
@@ -87,18 +81,8 @@ class EdEngine:
                 self.buf[nm + ".weight_v"] = torch.zeros(math.prod(shp[1:]), device=d)
                 self.w_eff[nm] = torch.zeros(shp, device=d)
                 self.sn_sigma[nm] = torch.ones(1, device=d)
-        hid = cfg.get("notes_hidden", 256)
         f = lambda *s: torch.empty(*s, device=d)      # noqa: E731
-        self.x = f(B, T, C)
         self.y = torch.zeros(B, dtype=torch.int64, device=d)
-        self.z = [f(B, T, co) for (_, co, _) in chans]           # conv output (bias included), BatchNorm input
-        self.a = [f(B, T, co) for (_, co, _) in chans]           # GELU(BatchNorm(z))
-        self.dz = [f(B, T, co) for (_, co, _) in chans]
-        self.da = [f(B, T, co) for (_, co, _) in chans]
-        self.bn_mean = [f(co) for (_, co, _) in chans]
-        self.bn_invstd = [f(co) for (_, co, _) in chans]
-        self.pool, self.dpool = f(B, chans[-1][1]), f(B, chans[-1][1])
-        self.proj, self.dproj = f(B, hid), f(B, hid)
         self.cz = [f(B, h) for h in self.mlp]                    # classifier pre-activations
         self.ca = [f(B, h) for h in self.mlp]                    # after GELU and dropout
         self.dcz = [f(B, h) for h in self.mlp]
@@ -113,6 +97,34 @@ class EdEngine:
         # the resident training split of the staged step (attach_split); a tail stages from its owner's
         self._owner = share if share is not None else self
         self.split_x = self.split_y = self.order = self.batch_base = self.serial_base = self.metrics = self.aug = None
+        self._init_input(max_notes)
+
+    def _init_input(self, max_notes: Optional[int]):
+        """The convolutional encoder's side of the state: the batch of notes and everything up to the classifier's input."""
+        cfg, d, B, chans = self.cfg, self.dev, self.B, self.chans
+        self.T = T = int(max_notes or cfg.get("max_notes", 512))
+        self.C = C = int(cfg.get("note_dim", 4))
+        # three-tap layers by minimal filtering (csrc/conv_wino.hip: 2/3 of the direct form's matrix-pipe work) where the
+        # problem is big enough to be bound by it: forward with >= 128 output columns, data-gradient with >= 128 input channels
+        # (the GAN engine's rule); the weights change every step, so both filter images of every such layer are transformed
+        # by ONE launch at the top of the step.  MELO_ED_WINO=0: the direct window GEMMs.
+        wino = os.environ.get("MELO_ED_WINO", "1") == "1" and B * T >= 4096
+        self.wino_f = [bool(wino and k == 3 and co >= 128 and ops.wino3_supported(B, T, ci, co)) for (ci, co, k) in chans]
+        self.wino_d = [bool(wino and k == 3 and ci >= 128 and i > 0 and ops.wino3_supported(B, T, co, ci)) for i, (ci, co, k) in enumerate(chans)]
+        wimg = lambda on, cin, n: torch.zeros(cin // 4, 4, n, 4, device=d) if on else None  # noqa: E731
+        self.wino_wf = [wimg(f_, ci, co) for f_, (ci, co, _) in zip(self.wino_f, chans)]
+        self.wino_wd = [wimg(f_, co, ci) for f_, (ci, co, _) in zip(self.wino_d, chans)]
+        hid = cfg.get("notes_hidden", 256)
+        f = lambda *s: torch.empty(*s, device=d)      # noqa: E731
+        self.x = f(B, T, C)
+        self.z = [f(B, T, co) for (_, co, _) in chans]           # conv output (bias included), BatchNorm input
+        self.a = [f(B, T, co) for (_, co, _) in chans]           # GELU(BatchNorm(z))
+        self.dz = [f(B, T, co) for (_, co, _) in chans]
+        self.da = [f(B, T, co) for (_, co, _) in chans]
+        self.bn_mean = [f(co) for (_, co, _) in chans]
+        self.bn_invstd = [f(co) for (_, co, _) in chans]
+        self.pool, self.dpool = f(B, chans[-1][1]), f(B, chans[-1][1])
+        self.proj, self.dproj = f(B, hid), f(B, hid)
 
     # ---- state in / out ---------------------------------------------------------------------------------
     def init_weights(self, seed: int = 42):
@@ -149,9 +161,13 @@ class EdEngine:
         if not 0 < rows < self.B:
             raise ValueError(f"tail: rows={rows} must be in (0, {self.B})")
         if rows not in self._tails:
-            self._tails[rows] = EdEngine(self.cfg, self.dev, rows, self.T, share=self)
+            self._tails[rows] = type(self)(self.cfg, self.dev, rows, self.T, share=self, **self._tail_args())
             self._tails[rows].lr = self.lr
         return self._tails[rows]
+
+    def _tail_args(self) -> dict:
+        """Constructor arguments of a tail() engine beyond EdEngine's."""
+        return {}
 
     def load_state(self, params: Dict[str, Tensor], buffers: Optional[Dict[str, Tensor]] = None):
         """params may be a torch state_dict of the reference module: a spectrally normalised layer's weight is `weight_orig`
@@ -181,7 +197,11 @@ class EdEngine:
         for k, v in P.items():
             if k not in sd:
                 sd[k] = v
-        for nm in self.sn_names:          # torch.nn.utils.spectral_norm's keys: weight_orig (parameter), weight_u, weight_v (buffers)
+        return self._sn_keys(sd)
+
+    def _sn_keys(self, sd):
+        """torch.nn.utils.spectral_norm's keys in a state_dict: weight_orig (parameter), weight_u, weight_v (buffers)."""
+        for nm in self.sn_names:
             sd[nm + ".weight_orig"] = sd.pop(nm + ".weight")
             sd[nm + ".weight_u"] = self.buf[nm + ".weight_u"].cpu().clone()
             sd[nm + ".weight_v"] = self.buf[nm + ".weight_v"].cpu().clone()
@@ -192,23 +212,27 @@ class EdEngine:
         self.y.copy_(y, non_blocking=True)
 
     def attach_split(self, x: Tensor, y: Tensor, aug=None):
-        """Make (x, y) -- (n, T, C) fp32 and (n,) int64, resident on the device -- the split step_staged stages its batches
-        from, augmented by `aug` (ops.augment_spec(...); None: everything off, keyed by this engine's seed).  Captured staged
-        steps hold the old addresses and parameters and are dropped."""
+        """Make (x, y) -- (n, <a row of self.x>) fp32 and (n,) int64, resident on the device -- the split step_staged stages
+        its batches from; `aug`: _split_aug.  Captured staged steps hold the old addresses and parameters and are dropped."""
         if self._owner is not self:
             raise ValueError("attach_split: attach to the full-batch engine; its tails share the split")
+        aug = self._split_aug(aug)
         ops._chk(x, "x")
         ops._chk(y, "y", (x.shape[0],), torch.int64)
-        if x.dim() != 3 or tuple(x.shape[1:]) != (self.T, self.C) or x.shape[0] == 0:
-            raise ValueError(f"attach_split: x must be (n > 0, {self.T}, {self.C}), got {tuple(x.shape)}")
-        self.split_x, self.split_y = x, y
-        self.aug = aug if aug is not None else ops.augment_spec("ed", self.rng_seed)
+        row = tuple(self.x.shape[1:])
+        if tuple(x.shape[1:]) != row or x.shape[0] == 0:
+            raise ValueError(f"attach_split: x must be (n > 0, {', '.join(map(str, row))}), got {tuple(x.shape)}")
+        self.split_x, self.split_y, self.aug = x, y, aug
         self.order = torch.arange(x.shape[0], dtype=torch.int64, device=self.dev)
         self.batch_base = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.serial_base = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.metrics = torch.zeros(2, device=self.dev)
         for e in (self, *self._tails.values()):
             e._graphs.pop("step_staged", None)
+
+    def _split_aug(self, aug):
+        """The split's augmentation (ops.augment_spec(...)); None: everything off, keyed by this engine's seed."""
+        return aug if aug is not None else ops.augment_spec("ed", self.rng_seed)
 
     def set_epoch(self, order: Optional[Tensor], epoch_index: int):
         """Start an epoch of staged steps: `order` (n int64 row indices, host or device; None: the order buffer was written
@@ -251,6 +275,17 @@ class EdEngine:
         """The weight layer `name` computes with: w_orig / sigma when it is spectrally normalised."""
         return self.w_eff[name] if name in self.w_eff else self.P.p[name + ".weight"]
 
+    def _tail_layers(self):
+        """The classifier tail's [(weight it computes with, bias)], the head last (layers.tail_fwd / tail_bwd)."""
+        return [(self._w(nm), self.P.p[nm + ".bias"]) for nm in self.names]
+
+    def _tail_bwd(self, feat: Tensor, dfeat: Optional[Tensor], jobs: list):
+        """dlogits back through the tail (d/d(pre-activation) = dropout mask * GELU'(cz)) to dfeat, the gradient of the
+        tail's input `feat`; every layer's weight-gradient job is appended to `jobs`."""
+        G = self.P.g
+        grads = [(G[nm + ".weight"], G[nm + ".bias"]) for nm in self.names]
+        tail_bwd(self.dlogits, feat, self._tail_layers(), self.cz, self.ca, self.dcz, self.dmask, dfeat, jobs, grads)
+
     def forward(self, train: bool = True):
         P, x = self.P.p, self.x
         if self.sn_names:          # power iteration (training mode) + effective weights of every normalised layer: one launch
@@ -279,29 +314,15 @@ class EdEngine:
             x = self.a[i]
         ops.meanT_fwd(x, self.pool)
         ops.linear_fwd(self.pool, P["encoder.project.weight"], self.proj, bias=P["encoder.project.bias"])
-        feat = self.proj
-        for j in range(len(self.mlp)):
-            ops.linear_fwd(feat, self._w(f"classifier.net.{3 * j}"), self.ca[j], bias=P[f"classifier.net.{3 * j}.bias"],
-                           zout=self.cz[j], act=ACT_GELU, emul=self.dmask[j] if train else None)
-            feat = self.ca[j]
-        ops.linear_fwd(feat, P["classifier.head.weight"], self.logits, bias=P["classifier.head.bias"])
+        tail_fwd(self.proj, self._tail_layers(), self.cz, self.ca, self.logits, self.dmask if train else None)
 
     def backward(self):
         """Train-mode forward + cross-entropy + gradients of every parameter into self.P.grad."""
         P, G = self.P.p, self.P.g
         self.forward(train=True)
         ops.softmax_ce(self.logits, self.y, self.loss, self.dlogits, 1.0)
-        n = len(self.mlp)
-        g, wname, inp = self.dlogits, "classifier.head", self.ca[n - 1]
         jobs = []        # weight gradients: collected, launched together at the end (ops.wgrad_multi)
-        for j in reversed(range(n)):
-            jobs.append(ops.linear_wgrad(inp, g, G[wname + ".weight"], db=G[wname + ".bias"], defer=True))
-            # d/d(pre-activation) = dropout mask * GELU'(cz)
-            ops.linear_dgrad(g, self._w(wname), self.dcz[j], gref=self.cz[j], gact=ACT_GELU, emul=self.dmask[j])
-            g, wname = self.dcz[j], f"classifier.net.{3 * j}"
-            inp = self.ca[j - 1] if j > 0 else self.proj
-        jobs.append(ops.linear_wgrad(self.proj, g, G[wname + ".weight"], db=G[wname + ".bias"], defer=True))
-        ops.linear_dgrad(g, self._w(wname), self.dproj)
+        self._tail_bwd(self.proj, self.dproj, jobs)
         jobs.append(ops.linear_wgrad(self.pool, self.dproj, G["encoder.project.weight"], db=G["encoder.project.bias"], defer=True))
         ops.linear_dgrad(self.dproj, P["encoder.project.weight"], self.dpool)
         last = len(self.chans) - 1

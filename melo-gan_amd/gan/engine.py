@@ -18,6 +18,9 @@ hand-derived backward passes:
     train_gan.py:136-145) live in ONE flat fp32 buffer each -> one fused Adam launch and one
     all-reduce bucket per step; state_dict tensors are views into it.
 
+The frozen emotion discriminator's branch is _ed_fwd / _ed_bwd: its convolutions are _ed_convs_fwd / _ed_bwd_convs (which
+hold the bf16 switch), its MLP tail emotion_discriminator.layers.tail_fwd / tail_bwd -- or, as one row chain, _ed_chain_tail.
+
 Randomness (noise, alpha, dropout keep-masks) is an INPUT of every step, so parity runs inject
 the oracle's draws and production runs fill the same buffers from the device RNG.
 """
@@ -32,6 +35,7 @@ import torch
 
 from .. import ops
 from ..ops import ACT_GELU, ACT_LRELU, ACT_RELU
+from ..emotion_discriminator.layers import tail_bwd, tail_fwd
 
 Tensor = torch.Tensor
 BN_EPS, BN_MOM, P_DROP = 1e-5, 0.1, 0.2
@@ -158,6 +162,12 @@ class FlatParams:
         return OrderedDict((k, v.detach().cpu().clone()) for k, v in self.p.items())
 
 
+def norm_buffers(bufs: "Dict[str, tuple]", device) -> "OrderedDict[str, Tensor]":
+    """BatchNorm running statistics at their initial values: running_var one, everything else zero."""
+    return OrderedDict((k, torch.ones(s, device=device) if k.endswith("running_var") else torch.zeros(s, device=device))
+                       for k, s in bufs.items())
+
+
 class GanEngine:
     """One replica of the GAN training state on one GPU."""
 
@@ -202,8 +212,7 @@ class GanEngine:
             raise ValueError(f"emotion discriminator config: note_dim={self.ed_chans[0][0]} but the GAN's NOTE_DIM={C} -- the "
                              "frozen classifier reads the generated notes, both must agree (ed_model.py:24, models.py:67)")
         self.ED = FlatParams(edspec, d, with_opt=False)
-        self.EDbuf = {k: (torch.ones(s, device=d) if k.endswith("running_var") else torch.zeros(s, device=d))
-                      for k, s in edbufs.items()}
+        self.EDbuf = norm_buffers(edbufs, d)
         self.Gbuf = {"decoder.deconv.1.running_mean": torch.zeros(128, device=d),
                      "decoder.deconv.1.running_var": torch.ones(128, device=d),
                      "decoder.deconv.4.running_mean": torch.zeros(64, device=d),
@@ -854,10 +863,13 @@ class GanEngine:
         self._ed_folded = True
 
     def _ed_conv_fwd(self, i: int, x: Tensor, lds_pad: int = 0):
-        """Layer i of the frozen encoder, fp32: Conv1d -> folded BatchNorm (z kept) -> GELU (ed_model.py:24-46).  lds_pad:
-        the occupancy cap of the side branch (ED_SIDE_LDS_PAD)."""
+        """Layer i of the frozen encoder: Conv1d -> folded BatchNorm (z kept) -> GELU (ed_model.py:24-46).  lds_pad: the
+        occupancy cap of the side branch (ED_SIDE_LDS_PAD); the bf16 kernel takes none."""
         ci, co, k = self.ed_chans[i]
-        if self.ed_wino_f[i]:
+        if self.ed_dtype == "bf16":
+            ops.conv_s1_bf16(x, self.ed_wb_f[i], self.ed_a[i], scale=self.ed_scale[i], shift=self.ed_shift[i],
+                             zout=self.ed_z[i], act=ACT_GELU)
+        elif self.ed_wino_f[i]:
             ops.conv_wino3(x, self.ed_wino_wf[i], self.ed_a[i], lds_pad=lds_pad, scale=self.ed_scale[i], shift=self.ed_shift[i],
                            zout=self.ed_z[i], act=ACT_GELU)
         else:
@@ -872,49 +884,38 @@ class GanEngine:
         else:
             ops.conv1d_dgrad(self.ed_dz[i], self.ED.p[f"encoder.conv.{i}.net.0.weight"], out, 1, lds_pad=lds_pad, **epi)
 
+    def _ed_convs_fwd(self, x: Tensor, lds_pad: int = 0) -> Tensor:
+        """The frozen encoder's convolution layers on x (fp32 notes); returns the last activation."""
+        for i in range(len(self.ed_chans)):
+            self._ed_conv_fwd(i, x, lds_pad)
+            x = self.ed_a[i]
+        return x
+
+    def _ed_tail(self):
+        """The classifier tail's [(weight, bias)], the head last (emotion_discriminator.layers)."""
+        P = self.ED.p
+        names = [f"classifier.net.{3 * j}" for j in range(len(self.ed_cz))] + ["classifier.head"]
+        return [(P[nm + ".weight"], P[nm + ".bias"]) for nm in names]
+
     def _ed_fwd(self, notes: Tensor, lds_pad: int = 0):
         """EmotionDiscriminator.forward in eval mode (ed_model.py:63-69,92-95,147-165)."""
         P = self.ED.p
-        if self.ed_mode == "notes" and self.ed_dtype == "bf16":
-            x = notes                                                  # fp32, converted on its way into LDS
-            for i in range(len(self.ed_chans)):
-                ops.conv_s1_bf16(x, self.ed_wb_f[i], self.ed_a[i], scale=self.ed_scale[i], shift=self.ed_shift[i],
-                                 zout=self.ed_z[i], act=ACT_GELU)
-                x = self.ed_a[i]
-            ops.meanT_fwd_bf16(x, self.ed_pool)
+        feat = self.lat
+        if self.ed_mode == "notes":
+            x = self._ed_convs_fwd(notes, lds_pad)
+            (ops.meanT_fwd_bf16 if self.ed_dtype == "bf16" else ops.meanT_fwd)(x, self.ed_pool)
             ops.linear_fwd(self.ed_pool, P["encoder.project.weight"], self.ed_proj, bias=P["encoder.project.bias"])
             feat = self.ed_proj
-        elif self.ed_mode == "notes":
-            x = notes
-            for i in range(len(self.ed_chans)):
-                self._ed_conv_fwd(i, x, lds_pad)
-                x = self.ed_a[i]
-            ops.meanT_fwd(x, self.ed_pool)
-            ops.linear_fwd(self.ed_pool, P["encoder.project.weight"], self.ed_proj, bias=P["encoder.project.bias"])
-            feat = self.ed_proj
-        else:
-            feat = self.lat
-        for j in range(len(self.ed_cz)):
-            ops.linear_fwd(feat, P[f"classifier.net.{3 * j}.weight"], self.ed_ca[j], bias=P[f"classifier.net.{3 * j}.bias"],
-                           zout=self.ed_cz[j], act=ACT_GELU)
-            feat = self.ed_ca[j]
-        ops.linear_fwd(feat, P["classifier.head.weight"], self.logits, bias=P["classifier.head.bias"])
+        tail_fwd(feat, self._ed_tail(), self.ed_cz, self.ed_ca, self.logits)
 
     def _ed_bwd(self, dnotes: Tensor, lds_pad: int = 0):
         """Input gradient of the frozen ED: dlogits -> dnotes (notes mode) or -> ed_dfeat (latent mode)."""
-        P = self.ED.p
-        n = len(self.ed_cz)
-        g = self.dlogits
-        w = P["classifier.head.weight"]
-        for j in reversed(range(n)):
-            ops.linear_dgrad(g, w, self.ed_dcz[j], gref=self.ed_cz[j], gact=ACT_GELU)
-            g, w = self.ed_dcz[j], P[f"classifier.net.{3 * j}.weight"]
-        if self.ed_mode != "notes":
-            ops.linear_dgrad(g, w, self.ed_dfeat)
-            return
-        ops.linear_dgrad(g, w, self.ed_dproj)
-        ops.linear_dgrad(self.ed_dproj, P["encoder.project.weight"], self.ed_dpool)
-        self._ed_bwd_convs(dnotes, lds_pad=lds_pad)
+        notes = self.ed_mode == "notes"
+        tail_bwd(self.dlogits, None, self._ed_tail(), self.ed_cz, self.ed_ca, self.ed_dcz,
+                 dfeat=self.ed_dproj if notes else self.ed_dfeat)
+        if notes:
+            ops.linear_dgrad(self.ed_dproj, self.ED.p["encoder.project.weight"], self.ed_dpool)
+            self._ed_bwd_convs(dnotes, lds_pad=lds_pad)
 
     def _ed_bwd_convs(self, dnotes: Tensor, mean=None, lds_pad: int = 0):
         """From the pooled features' gradient back to the notes: pooling backward (times conv3's GELU' and BatchNorm scale)
@@ -1159,21 +1160,19 @@ class GanEngine:
 
     def _ed_chain_front(self, lds_pad: int):
         """g_ed_branch with the classifier's tail -- pooling, project, MLP, head, cross-entropy and every data-gradient back
-        to the pooled features (ed_model.py:61,86-95,147-165) -- as ONE row-chain launch behind the convolutions' forward
-        (was: 10 launches of ~5 us); _ed_chain_back runs the convolutions' data-gradients.  The fp32 branch's loss scalar (the
-        mean of the per-sample terms) rides in the pooling-backward launch there.  lds_pad: the convolutions' occupancy cap."""
+        to the pooled features (ed_model.py:61,86-95,147-165) -- as ONE row-chain launch (_ed_chain_tail) behind the
+        convolutions' forward (was: 10 launches of ~5 us); _ed_chain_back runs the convolutions' data-gradients.  The fp32
+        branch's loss scalar (the mean of the per-sample terms) rides in the pooling-backward launch there.  lds_pad: the
+        convolutions' occupancy cap."""
+        self._ed_chain_tail(self._ed_convs_fwd(self.notes, lds_pad) if self.ed_mode == "notes" else None)
+
+    def _ed_chain_tail(self, x: Optional[Tensor]):
+        """The row chain of _ed_chain_front: from x, the last convolution's activation (notes mode; latent mode reads
+        self.lat), to ed_dpool (notes) / ed_dfeat (latent), and the loss scalar where no later launch carries it."""
         P = self.ED.p
         notes, bf16 = self.ed_mode == "notes", self.ed_dtype == "bf16"
         ch = ops.Chain(self.B)
         if notes:
-            x = self.notes
-            for i in range(len(self.ed_chans)):
-                if bf16:
-                    ops.conv_s1_bf16(x, self.ed_wb_f[i], self.ed_a[i], scale=self.ed_scale[i], shift=self.ed_shift[i],
-                                     zout=self.ed_z[i], act=ACT_GELU)
-                else:
-                    self._ed_conv_fwd(i, x, lds_pad)
-                x = self.ed_a[i]
             if bf16:
                 ops.meanT_fwd_bf16(x, self.ed_pool)
                 ch.load(0, self.ed_pool)
@@ -1184,25 +1183,24 @@ class GanEngine:
             ch.load(1, self.lat)
         cur = 1
         nxt = lambda c: (c + 1) % ops.L.CHAIN_SLOTS  # noqa: E731
+        tail = self._ed_tail()
         n = len(self.ed_cz)
         for j in range(n):
-            ch.linear_fwd(cur, nxt(cur), P[f"classifier.net.{3 * j}.weight"], P[f"classifier.net.{3 * j}.bias"], ACT_GELU,
-                          zout=self.ed_cz[j], out=self.ed_ca[j])
+            ch.linear_fwd(cur, nxt(cur), *tail[j], ACT_GELU, zout=self.ed_cz[j], out=self.ed_ca[j])
             cur = nxt(cur)
-        ch.linear_fwd(cur, nxt(cur), P["classifier.head.weight"], P["classifier.head.bias"], out=self.logits)
+        ch.linear_fwd(cur, nxt(cur), *tail[n], out=self.logits)
         cur = nxt(cur)
         # F.cross_entropy (mean over the batch) forward + backward; the generator's loss weighs it by lambda_emo
         ch.softmax_ce(cur, nxt(cur), self.emot_idx, self.ed_loss_rows, self.lambda_emo / self.B, self.n_classes)
         cur = nxt(cur)
         ch.store(cur, self.dlogits)
-        w = P["classifier.head.weight"]
         for j in reversed(range(n)):
-            ch.linear_dgrad(cur, nxt(cur), w, gref=self.ed_cz[j], gact=ACT_GELU, out=self.ed_dcz[j])
-            cur, w = nxt(cur), P[f"classifier.net.{3 * j}.weight"]
+            ch.linear_dgrad(cur, nxt(cur), tail[j + 1][0], gref=self.ed_cz[j], gact=ACT_GELU, out=self.ed_dcz[j])
+            cur = nxt(cur)
         if not notes:
-            ch.linear_dgrad(cur, nxt(cur), w, out=self.ed_dfeat)
+            ch.linear_dgrad(cur, nxt(cur), tail[0][0], out=self.ed_dfeat)
         else:
-            ch.linear_dgrad(cur, nxt(cur), w, out=self.ed_dproj)
+            ch.linear_dgrad(cur, nxt(cur), tail[0][0], out=self.ed_dproj)
             cur = nxt(cur)
             ch.linear_dgrad(cur, nxt(cur), P["encoder.project.weight"], out=self.ed_dpool)
         ch.launch()

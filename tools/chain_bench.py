@@ -6,6 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, melo_gan_amd  # noqa
 from melo_gan_amd import ops
 from melo_gan_amd.gan.engine import GanEngine
+from melo_gan_amd.emotion_discriminator.layers import tail_bwd, tail_fwd
 from melo_gan_amd.gan.config import default_gan_cfg, default_ed_cfg
 from _timeit import timeit
 
@@ -28,38 +29,16 @@ def make(chains):
 
 
 def ed_tail(e):
+    """From the last convolution's activation to ed_dpool: the engine's chain, or the same tail per layer."""
     if e._chain_ed:
-        # the chain part only: skip the convolutions by timing the whole branch minus them is not possible; rebuild the chain here
-        P = e.ED.p
-        ch = ops.Chain(B)
-        ch.mean_t(0, e.ed_a[3], out=e.ed_pool)
-        ch.linear_fwd(0, 1, P["encoder.project.weight"], P["encoder.project.bias"], out=e.ed_proj)
-        ch.linear_fwd(1, 2, P["classifier.net.0.weight"], P["classifier.net.0.bias"], ops.ACT_GELU, zout=e.ed_cz[0], out=e.ed_ca[0])
-        ch.linear_fwd(2, 3, P["classifier.net.3.weight"], P["classifier.net.3.bias"], ops.ACT_GELU, zout=e.ed_cz[1], out=e.ed_ca[1])
-        ch.linear_fwd(3, 4, P["classifier.head.weight"], P["classifier.head.bias"], out=e.logits)
-        ch.softmax_ce(4, 5, e.emot_idx, e.ed_loss_rows, e.lambda_emo / B, 4)
-        ch.store(5, e.dlogits)
-        ch.linear_dgrad(5, 0, P["classifier.head.weight"], gref=e.ed_cz[1], gact=ops.ACT_GELU, out=e.ed_dcz[1])
-        ch.linear_dgrad(0, 1, P["classifier.net.3.weight"], gref=e.ed_cz[0], gact=ops.ACT_GELU, out=e.ed_dcz[0])
-        ch.linear_dgrad(1, 2, P["classifier.net.0.weight"], out=e.ed_dproj)
-        ch.linear_dgrad(2, 3, P["encoder.project.weight"], out=e.ed_dpool)
-        ch.launch()
-    else:
-        P = e.ED.p
-        ops.meanT_fwd(e.ed_a[3], e.ed_pool)
-        ops.linear_fwd(e.ed_pool, P["encoder.project.weight"], e.ed_proj, bias=P["encoder.project.bias"])
-        feat = e.ed_proj
-        for j in range(2):
-            ops.linear_fwd(feat, P[f"classifier.net.{3 * j}.weight"], e.ed_ca[j], bias=P[f"classifier.net.{3 * j}.bias"], zout=e.ed_cz[j], act=ops.ACT_GELU)
-            feat = e.ed_ca[j]
-        ops.linear_fwd(feat, P["classifier.head.weight"], e.logits, bias=P["classifier.head.bias"])
-        ops.softmax_ce(e.logits, e.emot_idx, e.emo, e.dlogits, e.lambda_emo)
-        g, w = e.dlogits, P["classifier.head.weight"]
-        for j in (1, 0):
-            ops.linear_dgrad(g, w, e.ed_dcz[j], gref=e.ed_cz[j], gact=ops.ACT_GELU)
-            g, w = e.ed_dcz[j], P[f"classifier.net.{3 * j}.weight"]
-        ops.linear_dgrad(g, w, e.ed_dproj)
-        ops.linear_dgrad(e.ed_dproj, P["encoder.project.weight"], e.ed_dpool)
+        return e._ed_chain_tail(e.ed_a[-1])
+    P, tail = e.ED.p, e._ed_tail()
+    ops.meanT_fwd(e.ed_a[-1], e.ed_pool)
+    ops.linear_fwd(e.ed_pool, P["encoder.project.weight"], e.ed_proj, bias=P["encoder.project.bias"])
+    tail_fwd(e.ed_proj, tail, e.ed_cz, e.ed_ca, e.logits)
+    ops.softmax_ce(e.logits, e.emot_idx, e.emo, e.dlogits, e.lambda_emo)
+    tail_bwd(e.dlogits, None, tail, e.ed_cz, e.ed_ca, e.ed_dcz, dfeat=e.ed_dproj)
+    ops.linear_dgrad(e.ed_dproj, P["encoder.project.weight"], e.ed_dpool)
 
 
 def e_bwd(e):
