@@ -693,6 +693,51 @@ int mg_note_stats(const float* real, const float* fake, int B, int T, int C, con
                   int32_t* row_i, double* row_beats, long dst_rows, const uint64_t* counter, const uint64_t* base,
                   mg_stream_t stream);
 
+/* ---- held-out evaluation of a trained VAE (melo_gan_amd.ae.evaluate; csrc/vae_metrics.hip) ----
+ * The reference asks twice whether the VAE's latents are any good -- src/gan/diagnose.py:82-91 warns of posterior collapse
+ * when latents.std() < 0.1, src/gan/tsne.py asks whether they cluster by emotion -- and measures neither; of the
+ * reconstruction it keeps one MSE over four channels of different scales.  mg_vae_eval_acc adds ONE evaluated batch to a
+ * device-resident accumulator that lives for a whole pass.  Capturable; no host round trip.
+ *   x, recon        (B, T, 4) fp32, 16-byte aligned; C != 4 is an argument error
+ *   mu, logvar      (B, L) fp32, 1 <= L <= 1024
+ *   labels          (B) int64, the true class; a label outside [0, n_classes) is padding: the row counts nowhere and writes
+ *                   nothing
+ *   B in 1..32767, T in 1..2^20, n_classes in 1..32; anything else, a null pointer or a workspace smaller than
+ *   mg_vae_eval_acc_workspace_bytes(B, L) returns -1 before a launch
+ * A time position is decoded on both sides by mg_note_stats' decode (one function, csrc/note_decode.h); it is valid when all
+ * four values are finite on both sides, and an invalid position is counted as such and otherwise absent.
+ * Accumulator: mg_vae_eval_acc_words(K = n_classes, L) = K (26 + 5 L) 8-byte words, one block per true class:
+ *   int64  c[16]       rows; valid positions; invalid positions; both sounding; both rest; missed (real sounding,
+ *                      reconstruction rest); extra (real rest, reconstruction sounding); over both-sounding positions: pitch
+ *                      equal, |pitch difference| <= 1, pitch class equal, sum |pitch difference|, sum |velocity difference|;
+ *                      four zero words
+ *   double se[4], ae[4]   per channel, sum (recon - x)^2 and sum |recon - x| over valid positions, each element widened to
+ *                      fp64 before the subtraction
+ *   double dur_abs, step_abs   sum |dur difference| in beats over both-sounding positions, sum |step difference| over valid ones
+ *   double lat[5][L]   per latent dimension, summed over rows, in fp64 from the fp32 inputs: mu, mu^2, logvar, exp(logvar),
+ *                      -1/2 (1 + logvar - mu^2 - exp(logvar))
+ * mg_vae_eval_acc_reset writes zeros.
+ * Per-row outputs at the split position p = (counter[0] - base[0]) * B + row (mg_scatter_rows_cursor's rule; rows with
+ * p >= dst_rows are dropped; the caller zeroes both arrays):
+ *   row_d  [dst_rows][4] double: squared error summed over the four channels, KL summed over the dimensions, sum |dur
+ *          difference|, sum |step difference|
+ *   row_i  [dst_rows][8] int32: c[1 .. 8] of the row
+ * Launch shape: launch 1 has one workgroup of 256 lanes per row; a lane loads one time position of x and one of recon as a
+ * 16-byte load each, the workgroup walks the row in chunks of 256 positions, a lane adds its own positions in order (and the
+ * KL terms of dimensions u, u + 256, ...), the 256 lanes are reduced by a fixed tree, and the row's partial goes to the row's
+ * own entry of `work` and to row_d / row_i.  In launch 2 of the same call one lane owns one accumulator word of one class and
+ * adds the batch's rows of that class onto it one at a time, rows 0 .. B-1 in order: acc = ((acc + r0) + r1) + ...; the latent
+ * words are computed there straight from mu / logvar.  No atomics of any kind: two runs, and an eager run and a graph
+ * replay, leave identical bits, and for fixed input arrays the accumulator does not depend on how the rows are cut into
+ * batches.  tick != NULL: tick[0] += 1 at the end of launch 2 (mg_eval_acc's batch counter). */
+long mg_vae_eval_acc_words(int n_classes, int L);
+size_t mg_vae_eval_acc_workspace_bytes(int B, int L);
+int mg_vae_eval_acc_reset(void* acc, int n_classes, int L, mg_stream_t stream);
+int mg_vae_eval_acc(const float* x, const float* recon, int B, int T, int C, const float* mu, const float* logvar, int L,
+                    const int64_t* labels, int n_classes, void* acc, int32_t* row_i, double* row_d, long dst_rows,
+                    const uint64_t* counter, const uint64_t* base, void* work, size_t work_bytes, uint64_t* tick,
+                    mg_stream_t stream);
+
 /* ---- exact t-SNE of a feature set (melo_gan_amd.gan.tsne, melo_gan_amd.gan.evaluate --tsne; csrc/tsne.hip) ----
  * The reference's tsne.py asks whether the VAE latents cluster by emotion and hands the answer to scikit-learn; here the
  * affinities and the descent run on the device.  4 <= N <= 16384 (the dense P is 1 GiB there), everything fp32 unless said.

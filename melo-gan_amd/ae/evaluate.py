@@ -1,0 +1,270 @@
+#!/usr/bin/env python3
+"""Held-out evaluation of a trained VAE on the device.
+
+    python -m melo_gan_amd.ae.evaluate --config config/ae_config.yaml --model data/models/ae/ae_best.pth
+        [--split val|train|test|PATH/notes.npy] [--labels PATH/emotion.npy] [--batch 64]
+        [--out <LOG_DIR>/ae_eval.json] [--save-latents PATH.npy] [--recon-midi N] [--synthetic N]
+
+The reference keeps three loss scalars per epoch and six reconstructed .mid files of its VAE, although the VAE's `mu` is what
+the latent-mode classifier trains on and the generator is warm-started from (full_script.sh).  This is the held-out pass the
+GAN has in gan/evaluate.py: one pass over a resident split in row order, eval-mode BatchNorm, the reconstruction decoded
+from mu (eps = 0, so it is deterministic), every statistic accumulated where the batch lies (ops.vae_eval_acc) and read by
+the host once, at the end.  The numbers and their definitions are ae/metrics.py's.
+
+Labels default to <SPLITS_DIR>/<split>/emotion.npy; without that file every row goes to class 0 and the report holds the
+`overall` block alone, with fisher_ratio null.  --save-latents writes the pass's mu: the array ae.encode writes.
+--recon-midi N writes the N worst and the N best rows by squared error as <out dir>/ae_eval_midi/{worst,best}<i>_row<r>_{in,out}.mid.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+from typing import Optional
+
+import numpy as np
+import torch
+
+from ..gan.config import load_config
+from ..gan.generate import EMOTIONS
+from ..gan.utils import emotion_to_index
+from . import metrics as M
+from .encode import load_model
+from .engine import VaeEngine
+
+DEFAULT_BATCH = 64
+SPLITS = ("val", "train", "test")
+
+
+class AeEvaluateError(RuntimeError):
+    """What every check of this module raises: no device, a config that does not fit the checkpoint or the split, an empty
+    split."""
+
+
+class VaeEvaluator:
+    """One VaeEngine of `batch` rows that only ever runs forward(train=False) with eps = 0.  share: a training engine whose
+    parameters, BatchNorm buffers and stream this one reads (train_ae --eval-every); nothing of it is written."""
+
+    def __init__(self, cfg: dict, device="cuda", batch: int = DEFAULT_BATCH, share: Optional[VaeEngine] = None,
+                 n_classes: int = len(EMOTIONS)):
+        from .. import ops
+        if not torch.cuda.is_available():
+            raise AeEvaluateError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+        if int(batch) < 1 or int(batch) > 32767:
+            raise AeEvaluateError(f"batch = {batch}: must be in 1..32767")
+        for k in ("MAX_NOTES", "LATENT_DIM"):
+            if k not in cfg:
+                raise AeEvaluateError(f"the AE config has no {k}")
+        if not 1 <= int(cfg["LATENT_DIM"]) <= 1024:
+            raise AeEvaluateError(f"LATENT_DIM = {cfg['LATENT_DIM']}: the evaluation reads 1..1024 latent dimensions")
+        try:
+            self.eng = VaeEngine(cfg, device, int(batch), share=share)
+        except ValueError as e:
+            raise AeEvaluateError(str(e)) from e
+        eng = self.eng
+        self.B, self.K = eng.B, int(n_classes)
+        d = eng.dev
+        self.ctr = torch.zeros(1, dtype=torch.int64, device=d)      # batch cursor, advanced by mg_vae_eval_acc
+        self.base = torch.zeros(1, dtype=torch.int64, device=d)
+        self.labels = torch.zeros(self.B, dtype=torch.int64, device=d)
+        self.words = ops.vae_eval_acc_layout(self.K, eng.latent)["words"]
+        self.buf = self.acc = self.row_d = self.row_i = None         # one buffer, three views of it: one device -> host read
+        self.mu = self.logvar = self.recon = None                    # split-position arrays of the last pass
+        self.acc_host = self.rows = None
+        self._graphs, self._key, self._hold = {}, None, None
+
+    def load(self, path: str):
+        """The weights and BatchNorm buffers of train_ae's ae_best.pth / ae_final.pth (encode.load_model)."""
+        if not os.path.isfile(path):
+            raise AeEvaluateError(f"checkpoint {path} does not exist")
+        eng = self.eng
+        ck = torch.load(path, map_location="cpu", weights_only=False)
+        sd = ck["model_state"] if isinstance(ck, dict) and "model_state" in ck else ck
+        for k, shape in list(eng.P.spec.items()) + [(k, tuple(v.shape)) for k, v in eng.buf.items()]:
+            if k not in sd:
+                raise AeEvaluateError(f"{path}: no '{k}': not a checkpoint of this VAE")
+            if tuple(sd[k].shape) != tuple(shape):
+                raise AeEvaluateError(f"{path}: '{k}' has shape {tuple(sd[k].shape)}, the config (MAX_NOTES {eng.T}, LATENT_DIM "
+                                      f"{eng.latent}) implies {tuple(shape)}")
+        load_model(eng, path)
+
+    def _launches(self, jobs, order, order_len, keep_recon, metrics=True):
+        """One batch.  metrics=False leaves the accumulation out (the pass is then timed without it; the cursor is the
+        caller's to advance)."""
+        from .. import ops
+        eng = self.eng
+        ops.stage_rows_cursor(jobs, self.B, order, order_len, self.ctr, self.base)
+        eng.forward(train=False)
+        ops.scatter_rows_cursor(eng.mu, self.mu, self.ctr, self.base)       # in front of vae_eval_acc, which advances the cursor
+        ops.scatter_rows_cursor(eng.lv, self.logvar, self.ctr, self.base)
+        if keep_recon:
+            ops.scatter_rows_cursor(eng.recon.view(self.B, -1), self.recon.view(self.recon.shape[0], -1), self.ctr, self.base)
+        if metrics:
+            ops.vae_eval_acc(eng.x, eng.recon, eng.mu, eng.lv, self.labels, self.acc, self.row_i, self.row_d, self.ctr, self.base,
+                             self.K, tick=self.ctr)
+
+    def evaluate(self, notes: torch.Tensor, labels: Optional[torch.Tensor] = None, keep_recon: bool = False, names=None) -> dict:
+        """One pass over a resident split notes (n, MAX_NOTES, 4) in row order; returns ae.metrics.report's block.  labels: the
+        n true classes (int64, on the device), or None: every row is class 0 and the block holds `overall` alone.  Afterwards
+        self.mu / self.logvar (n, L), self.recon (n, T, 4; keep_recon) lie on the device in split order; self.acc_host
+        (the accumulator by name) and self.rows (the per-row numbers) are on the host."""
+        from .. import ops
+        eng, B = self.eng, self.B
+        if not isinstance(notes, torch.Tensor) or not notes.is_cuda or notes.dtype != torch.float32 or not notes.is_contiguous():
+            raise AeEvaluateError("evaluate: the split must be a contiguous fp32 array on the device")
+        if notes.dim() != 3 or tuple(notes.shape[1:]) != (eng.T, 4):
+            raise AeEvaluateError(f"evaluate: the split's notes have shape {tuple(notes.shape)}, the config implies "
+                                  f"(n, {eng.T}, 4)")
+        n = notes.shape[0]
+        if n < 1:
+            raise AeEvaluateError("evaluate: the split is empty")
+        if labels is not None and (not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.int64
+                                   or tuple(labels.shape) != (n,)):
+            raise AeEvaluateError(f"evaluate: labels must be an int64 device array of {n} entries")
+        if labels is not None and bool(((labels < 0) | (labels >= self.K)).any()):
+            raise AeEvaluateError(f"evaluate: labels outside [0, {self.K})")
+        nb = (n + B - 1) // B
+        key = (notes.data_ptr(), None if labels is None else labels.data_ptr(), n, bool(keep_recon))
+        with torch.cuda.stream(eng.stream):
+            if self._key != key:
+                self.buf = torch.zeros(self.words + 4 * n + 4 * n, dtype=torch.int64, device=eng.dev)
+                self.acc = self.buf[:self.words]
+                self.row_d = self.buf[self.words:self.words + 4 * n].view(torch.float64).view(n, 4)
+                self.row_i = self.buf[self.words + 4 * n:].view(torch.int32).view(n, 8)
+                self.mu, self.logvar = (torch.zeros(n, eng.latent, device=eng.dev) for _ in range(2))
+                self.recon = torch.zeros(n, eng.T, 4, device=eng.dev) if keep_recon else None
+                # the labels padded to whole batches with -1: the staging clamps the notes' padding rows into the split
+                pad = torch.full((nb * B,), -1, dtype=torch.int64, device=eng.dev)
+                pad[:n] = 0 if labels is None else labels
+                order = torch.arange(nb * B, dtype=torch.int64, device=eng.dev)
+                jobs = [(notes, eng.x), (pad, self.labels)]
+                self._hold = (notes, labels, pad, order, jobs)
+                self._graphs, self._key = {}, key
+            _, _, _, order, jobs = self._hold
+            eng.eps.zero_()
+            self.buf.zero_()            # the empty accumulator (mg_vae_eval_acc_reset's zeros) and the per-row stashes
+            self.ctr.zero_()
+            for _ in range(nb):         # eager, then captured, then replayed: one graph per batch
+                ops.run_graphed(self._graphs, "batch", lambda: self._launches(jobs, order, nb * B, keep_recon))
+            host = self.buf.cpu()       # the pass's only device -> host read
+        views = {k: v.numpy() for k, v in ops.vae_eval_acc_views(host[:self.words], self.K, eng.latent).items()}
+        self.rows = {"row_d": host[self.words:self.words + 4 * n].view(torch.float64).view(n, 4).numpy(),
+                     "row_i": host[self.words + 4 * n:].view(torch.int32).view(n, 8).numpy()}
+        self.acc_host = views
+        rep = M.report(views, eng.T, eng.latent, names)
+        rep["rows"], rep["batch"] = n, B
+        if labels is None:
+            del rep["per_class"]
+        return rep
+
+
+def _load_labels(path: str, n: int, K: int) -> np.ndarray:
+    try:
+        emo = np.load(path, allow_pickle=True)
+    except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
+        raise AeEvaluateError(f"cannot read labels {path}: {e}") from e
+    if len(emo) != n:
+        raise AeEvaluateError(f"{path} holds {len(emo)} entries, the split {n} rows")
+    idx = np.array([emotion_to_index(e) for e in emo], dtype=np.int64)
+    if ((idx < 0) | (idx >= K)).any():
+        raise AeEvaluateError(f"{path}: labels outside [0, {K}) (unknown emotion names map to -1)")
+    return idx
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="Held-out evaluation of a trained VAE")
+    ap.add_argument("--config", type=str, default="config/ae_config.yaml")
+    ap.add_argument("--model", type=str, default=None, help="ae_best.pth or ae_final.pth (not needed with --synthetic)")
+    ap.add_argument("--split", type=str, default="val", help="val | train | test | PATH/notes.npy")
+    ap.add_argument("--labels", type=str, default=None, help="emotion.npy (default: next to the split's notes.npy)")
+    ap.add_argument("--batch", type=int, default=DEFAULT_BATCH)
+    ap.add_argument("--out", type=str, default=None, help="report (default <LOG_DIR>/ae_eval.json)")
+    ap.add_argument("--save-latents", type=str, default=None, help="write the pass's mu (n, LATENT_DIM) here")
+    ap.add_argument("--recon-midi", type=int, default=0, metavar="N", help="write the N worst and N best reconstructions")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N random rows and labels, untrained weights")
+    return ap.parse_args(argv)
+
+
+def run(args) -> dict:
+    from ..midi import save_recon_midi
+    if not torch.cuda.is_available():
+        raise AeEvaluateError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+    if not os.path.isfile(args.config):
+        raise AeEvaluateError(f"config {args.config} does not exist")
+    cfg = load_config(args.config)
+    if args.recon_midi < 0:
+        raise AeEvaluateError("--recon-midi must be >= 0")
+    ev = VaeEvaluator(cfg, "cuda", args.batch)
+    K, T = ev.K, ev.eng.T
+    labels_path = None
+    if args.synthetic:
+        g = torch.Generator().manual_seed(0)
+        notes = torch.rand(args.synthetic, T, 4, generator=g) * 2 - 1
+        idx = np.arange(args.synthetic, dtype=np.int64) % K
+        ev.eng.init_weights(0)
+        source = f"synthetic:{args.synthetic}"
+    else:
+        if args.model is None:
+            raise AeEvaluateError("give --model (or --synthetic N)")
+        path = args.split
+        if args.split in SPLITS:
+            path = os.path.join(cfg.get("SPLITS_DIR", "data/splits"), args.split, "notes.npy")
+        if not os.path.isfile(path):
+            raise AeEvaluateError(f"split array {path} does not exist")
+        notes = torch.from_numpy(np.ascontiguousarray(np.load(path), dtype=np.float32))
+        labels_path = args.labels or os.path.join(os.path.dirname(path), "emotion.npy")
+        if args.labels and not os.path.isfile(labels_path):
+            raise AeEvaluateError(f"labels {labels_path} do not exist")
+        idx = _load_labels(labels_path, notes.shape[0], K) if os.path.isfile(labels_path) else None
+        ev.load(args.model)
+        source = path
+    if notes.dim() != 3 or notes.shape[0] < 1:
+        raise AeEvaluateError(f"{source}: an (n, {T}, 4) array with n >= 1 expected, got {tuple(notes.shape)}")
+    dev_notes = notes.cuda()
+    dev_labels = None if idx is None else torch.from_numpy(idx).cuda()
+    rep = ev.evaluate(dev_notes, dev_labels, keep_recon=args.recon_midi > 0, names=EMOTIONS)
+    rep.update(model=args.model, split=source, labels=labels_path if idx is not None and not args.synthetic else None)
+    out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/ae"), "ae_eval.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    if args.save_latents:
+        os.makedirs(os.path.dirname(os.path.abspath(args.save_latents)), exist_ok=True)
+        np.save(args.save_latents, ev.mu.cpu().numpy())
+        rep["latents"] = args.save_latents
+    if args.recon_midi:
+        se = ev.rows["row_d"][:, 0]
+        by_err = np.argsort(se, kind="stable")
+        n_each = min(args.recon_midi, len(se))
+        midi_dir = os.path.join(os.path.dirname(os.path.abspath(out)), "ae_eval_midi")
+        rep["recon_midi"] = {"dir": midi_dir}
+        recon = ev.recon.cpu().numpy()
+        for tag, rows in (("worst", by_err[::-1][:n_each]), ("best", by_err[:n_each])):
+            rep["recon_midi"][tag] = []
+            for i, r in enumerate(rows):
+                prefix = f"{tag}{i}_row{int(r):06d}"
+                save_recon_midi(notes[int(r)].numpy(), recon[int(r)], midi_dir, prefix)
+                rep["recon_midi"][tag].append({"row": int(r), "squared_error": float(se[r]), "mse": float(se[r]) / (4 * T),
+                                               "files": [f"{prefix}_in.mid", f"{prefix}_out.mid"]})
+    with open(out, "w") as f:
+        json.dump(rep, f, indent=1, allow_nan=False)
+    o = rep["overall"]
+    print(f"VAE evaluation of {source}: {rep['rows']} rows, recon_mse {o['recon_mse']}, kld_mean {o['kld_mean']}, "
+          f"active_units {o['active_units']}/{rep['latent_dim']}, latent_std {o['latent_std']}, "
+          f"pitch_accuracy {o['pitch_accuracy']}, onset_recall {o['onset_recall']}, fisher_ratio {o['fisher_ratio_mean']}")
+    if o["latent_warning"]:
+        print("[WARNING]", o["latent_warning"])
+    print("report ->", out)
+    return rep
+
+
+def main(argv=None) -> int:
+    try:
+        run(parse_args(argv))
+    except AeEvaluateError as e:
+        print(f"ae.evaluate: error: {e}", file=sys.stderr)
+        return 2
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

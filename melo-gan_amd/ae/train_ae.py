@@ -13,7 +13,9 @@ scope).  AUGMENT.{tempo_jitter, pitch_shift, note_dropout, velocity_jitter, timi
 training split only): when any is non-zero the training batch is gathered AND augmented by one launch on the device
 (ops.stage_augment, program 'ae'); with all of them zero (the committed config) the gather is index_select.  Per epoch the first
 (up to) 6 validation rolls are reconstructed in eval mode and written as <RECON_DIR>/ep<E>_val<NNN>_{in,out}.mid
-(train_ae.py:94,173-188; RECON_FREQ, RECON_DIR) through melo_gan_amd.midi.
+(train_ae.py:94,173-188; RECON_FREQ, RECON_DIR) through melo_gan_amd.midi.  --eval-every N (default 0: off): every N epochs the
+held-out pass of ae/evaluate.py runs over the validation split on the training engine's weights and logs val/active_units,
+val/pitch_accuracy, val/onset_recall and, when <SPLITS_DIR>/val/emotion.npy exists, val/fisher_ratio.
 """
 import argparse
 import os
@@ -54,7 +56,19 @@ def augment_from_cfg(cfg, seed: int = 0):
     return aug if any(acfg.get(k, 0) != 0 for k in ops.AUG_AE_KEYS) else None
 
 
-def train(cfg, synthetic: int = 0):
+def _val_labels(cfg, n, device):
+    """The validation split's class indices for --eval-every, or None without <SPLITS_DIR>/val/emotion.npy."""
+    from ..gan.utils import emotion_to_index
+    p = os.path.join(cfg.get("SPLITS_DIR", "data/splits"), "val", "emotion.npy")
+    if not os.path.exists(p):
+        return None
+    idx = np.array([emotion_to_index(e) for e in np.load(p, allow_pickle=True)], dtype=np.int64)
+    if len(idx) != n:
+        raise ValueError(f"{p} holds {len(idx)} entries, the validation split {n} rows")
+    return torch.from_numpy(idx).to(device)
+
+
+def train(cfg, synthetic: int = 0, eval_every: int = 0):
     aug = augment_from_cfg(cfg, int(cfg.get("SEED", 0)))
     if not torch.cuda.is_available():
         raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
@@ -72,6 +86,11 @@ def train(cfg, synthetic: int = 0):
     eng = VaeEngine(cfg, dev, B)
     eng.init_weights(0)
     writer = _scalar_writer(log_dir)
+    evaluator = val_y = None
+    if eval_every > 0:          # reads the training engine's parameters and buffers; writes nothing of it
+        from .evaluate import VaeEvaluator
+        evaluator = VaeEvaluator(cfg, dev, B, share=eng)
+        val_y = None if synthetic else _val_labels(cfg, len(val_x), dev)
     best_val, no_improve, patience = float("inf"), 0, cfg.get("EARLY_STOP_PATIENCE", 10)
     warm, final_beta = cfg.get("KLD_WARMUP_EPOCHS", 25), float(cfg.get("BETA", 1.0))
     sched_bad, sched_best = 0, float("inf")
@@ -124,6 +143,13 @@ def train(cfg, synthetic: int = 0):
                            ("loss/val_total", va[0]), ("loss/val_recon", va[1]), ("loss/val_kld", va[2]),
                            ("lr", eng.lr), ("beta", beta)):
                 writer.add_scalar(tag, v, epoch)
+            if evaluator is not None and epoch % eval_every == 0:
+                o = evaluator.evaluate(val_x, val_y)["overall"]
+                for tag in ("active_units", "pitch_accuracy", "onset_recall"):
+                    if o[tag] is not None:
+                        writer.add_scalar("val/" + tag, o[tag], epoch)
+                if val_y is not None and o["fisher_ratio_mean"] is not None:
+                    writer.add_scalar("val/fisher_ratio", o["fisher_ratio_mean"], epoch)
             # reconstructions of the first (up to) 6 validation rolls, eval mode, batch 1 (train_ae.py:94,173-188)
             if epoch % cfg.get("RECON_FREQ", 1) == 0:
                 recon_dir = cfg.get("RECON_DIR", os.path.join(log_dir, "reconstructions"))
@@ -153,11 +179,12 @@ def main(argv=None):
     parser.add_argument("--config", type=str, default="config/ae_config.yaml", help="Path to config yaml")
     parser.add_argument("--synthetic", type=int, default=0)
     parser.add_argument("--epochs", type=int, default=None)
+    parser.add_argument("--eval-every", type=int, default=0, help="held-out VAE metrics of the validation split every N epochs")
     args = parser.parse_args(argv)
     cfg = load_config(args.config)
     if args.epochs is not None:
         cfg["EPOCHS"] = args.epochs
-    train(cfg, args.synthetic)
+    train(cfg, args.synthetic, args.eval_every)
 
 
 if __name__ == "__main__":

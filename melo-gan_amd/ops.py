@@ -2001,6 +2001,89 @@ def note_stats(real, fake, emot_idx, acc, row_i, row_beats, counter, base, n_cla
     return acc
 
 
+def vae_eval_acc_layout(n_classes: int, latent_dim: int) -> dict:
+    """The accumulator of vae_eval_acc (include/melo_gan_hip.h, mg_vae_eval_acc): name -> (offset in 8-byte words inside a
+    class's block, shape), plus 'block' (words of one block, 26 + 5 L) and 'words' (K blocks).  'c' is int64, the rest fp64."""
+    K, Ld = int(n_classes), int(latent_dim)
+    if not (1 <= K <= 32 and 1 <= Ld <= 1024):
+        raise ValueError("vae_eval_acc: 1..32 classes and a latent width in 1..1024")
+    lay, off = {}, 0
+    for name, shape in (("c", (16,)), ("se", (4,)), ("ae", (4,)), ("beats_abs", (2,)), ("lat", (5, Ld))):
+        lay[name] = (off, shape)
+        off += math.prod(shape)
+    lay["block"], lay["words"] = off, K * off
+    if lay["words"] != L.load().mg_vae_eval_acc_words(K, Ld):
+        raise RuntimeError("vae_eval_acc_layout disagrees with mg_vae_eval_acc_words")
+    return lay
+
+
+def vae_eval_acc_views(acc: Tensor, n_classes: int, latent_dim: int) -> dict:
+    """Typed views of an accumulator (device or host int64 tensor of vae_eval_acc_layout(...)['words'] words) by name, each
+    (K, *shape): what ae.metrics.report reads."""
+    lay = vae_eval_acc_layout(n_classes, latent_dim)
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] \
+            or not acc.is_contiguous():
+        raise ValueError(f"vae_eval_acc: the accumulator is a contiguous int64 vector of {lay['words']} words")
+    blocks = acc.view(int(n_classes), lay["block"])
+    out = {}
+    for name in ("c", "se", "ae", "beats_abs", "lat"):
+        off, shape = lay[name]
+        v = blocks[:, off:off + math.prod(shape)]
+        out[name] = (v if name == "c" else v.view(torch.float64)).reshape(int(n_classes), *shape)
+    return out
+
+
+def vae_eval_acc_new(n_classes: int, latent_dim: int, device) -> Tensor:
+    """A fresh (zero) accumulator for vae_eval_acc."""
+    return torch.zeros(vae_eval_acc_layout(n_classes, latent_dim)["words"], dtype=torch.int64, device=device)
+
+
+def vae_eval_acc_reset(acc: Tensor, n_classes: int, latent_dim: int) -> Tensor:
+    _chk(acc, "acc", (vae_eval_acc_layout(n_classes, latent_dim)["words"],), torch.int64)
+    L.check(L.load().mg_vae_eval_acc_reset(_p(acc), int(n_classes), int(latent_dim), _stream()), "mg_vae_eval_acc_reset")
+    return acc
+
+
+def vae_eval_acc(x, recon, mu, logvar, labels, acc, row_i, row_d, counter, base, n_classes: int, tick=None):
+    """One evaluated VAE batch added to the pass's accumulator (mg_vae_eval_acc): x / recon (B, T, 4), mu / logvar (B, L),
+    labels (B,) int64 (-1 = a padding row), acc from vae_eval_acc_new(n_classes, L); row_i (dst_rows, 8) int32 and row_d
+    (dst_rows, 4) float64 receive the per-row numbers at split position (counter - base) * B + row; counter / base: int64
+    device scalars (1,).  tick: an int64 (1,) batch counter to advance (usually `counter` itself)."""
+    _chk(x, "x")
+    if x.dim() != 3:
+        raise ValueError("vae_eval_acc: x (B, T, 4) expected")
+    B, T, C = x.shape
+    if C != 4:
+        raise ValueError(f"vae_eval_acc: C = {C}: only the (T, 4) note-row format decodes into notes")
+    _chk(recon, "recon", (B, T, C))
+    _chk(mu, "mu")
+    if mu.dim() != 2 or mu.shape[0] != B or not 1 <= mu.shape[1] <= 1024:
+        raise ValueError(f"vae_eval_acc: mu (B, L) with L in 1..1024 expected, got {tuple(mu.shape)}")
+    Ld = mu.shape[1]
+    _chk(logvar, "logvar", (B, Ld))
+    _chk(labels, "labels", (B,), torch.int64)
+    if not (1 <= B <= 32767 and 1 <= T <= 1 << 20):
+        raise ValueError("vae_eval_acc: B must be in 1..32767 and T in 1..2^20")
+    if x.data_ptr() % 16 or recon.data_ptr() % 16:
+        raise ValueError("vae_eval_acc: x and recon must be 16-byte aligned")
+    K = int(n_classes)
+    _chk(acc, "acc", (vae_eval_acc_layout(K, Ld)["words"],), torch.int64)
+    _chk(row_i, "row_i", dtype=torch.int32)
+    if row_i.dim() != 2 or row_i.shape[0] < 1 or row_i.shape[1] != 8:
+        raise ValueError(f"vae_eval_acc: row_i (dst_rows, 8) expected, got {tuple(row_i.shape)}")
+    _chk(row_d, "row_d", (row_i.shape[0], 4), torch.float64)
+    _chk(counter, "counter", (1,), torch.int64)
+    _chk(base, "base", (1,), torch.int64)
+    if tick is not None:
+        _chk(tick, "tick", (1,), torch.int64)
+    lib = L.load()
+    work = workspace(lib.mg_vae_eval_acc_workspace_bytes(B, Ld), x.device, "vae_eval_acc")
+    L.check(lib.mg_vae_eval_acc(_p(x), _p(recon), B, T, C, _p(mu), _p(logvar), Ld, _p(labels), K, _p(acc), _p(row_i), _p(row_d),
+                                row_i.shape[0], _p(counter), _p(base), _p(work), work.numel(), _p(tick), _stream()),
+            "mg_vae_eval_acc")
+    return acc
+
+
 def wq_table(entries):
     """ctypes table for adam_flat(wq=...): entries = [(start, N, Cc, K, w_sn, w_sc, dst tensor), ...] (mg_wq_entry)."""
     if len(entries) > L.MAX_WQ_ENTRIES:
