@@ -738,6 +738,52 @@ int mg_vae_eval_acc(const float* x, const float* recon, int B, int T, int C, con
                     const uint64_t* counter, const uint64_t* base, void* work, size_t work_bytes, uint64_t* tick,
                     mg_stream_t stream);
 
+/* ---- held-out evaluation of a trained emotion classifier (melo_gan_amd.emotion_discriminator.evaluate; csrc/cls_metrics.hip) ----
+ * The classifier is the frozen judge of every number gan.evaluate reports, and the reference's own evaluation of it
+ * (src/emotion_discriminator/evaluate_ed.py) is a copy of the model file.  mg_cls_eval_acc adds ONE evaluated batch to a
+ * device-resident accumulator that lives for a whole pass.  Capturable; no host round trip.
+ *   logits          (B, K = n_classes) fp32;  clean_logits: NULL, or (B, K) fp32 of the same rows without augmentation
+ *   labels          (B) int64, the true class; a label outside [0, K) is a padding or unlabelled row: it counts nowhere and
+ *                   writes nothing
+ *   inv_temps       HOST pointer to n_temps = G fp64 inverse temperatures, copied into the launch's arguments (host and
+ *                   device then use the same values); inv_temperature scales the logits before everything else (1.0: plain)
+ *   B in 1..32767, K in 2..16, n_bins in 1..32, G in 1..64, every inverse temperature positive and finite; anything else, a
+ *   null pointer or a workspace smaller than mg_cls_eval_acc_workspace_bytes(B, G) returns -1 before a launch
+ * Per row, in fp64, without contraction, in this order:
+ *   z_k = (double)logit_k * inv_temperature;  pred = argmax z (lowest index on ties);  m = z_pred
+ *   rest = sum over k != pred, in class order, of exp(z_k - m);  s = 1 + rest;  p_pred = 1 / s, p_k = exp(z_k - m) / s
+ *   ce = -log p_y computed as log1p(rest) + (m - z_y): finite for any finite logits
+ *   brier = sum_k (p_k - [k = y])^2 in class order;  conf = p_pred;  margin = conf - max_{k != pred} p_k
+ *   bin = min(n_bins - 1, floor(conf * n_bins));  correct = pred == y
+ *   nll_g = the same ce with z_k * inv_temps[g] for z_k (m = z_pred * inv_temps[g])
+ *   flipped = clean_logits given and its argmax (same scaling and tie rule) differs from pred
+ * Accumulator: mg_cls_eval_acc_words(K, n_bins, G) = K (7 + K + 3 n_bins + G) 8-byte words, one block per TRUE class, zeroed
+ * by the caller:
+ *   int64  rows, correct, flipped, confusion[K] (by predicted class), bin_count[n_bins], bin_correct[n_bins]
+ *   double ce, brier, conf, margin, bin_conf[n_bins] (sum of conf of the bin's rows), nll_T[G]
+ * Per-row outputs at the split position p = (counter[0] - base[0]) * B + row (mg_scatter_rows_cursor's rule; rows with
+ * p >= dst_rows are dropped; the caller zeroes the arrays):
+ *   probs  [dst_rows][K] double;  row_i [dst_rows][4] int32: pred, bin, correct, flipped
+ *   row_d  [dst_rows][4] double: ce, conf, p_y, margin
+ * Launch shape: launch 1 has one wave per row; lane g computes nll_g, lane 0 the rest, and the row's partial goes to the row's
+ * own entry of `work`.  In launch 2 one lane owns one accumulator word of one class and adds the batch's rows of that class
+ * onto it one at a time, rows 0 .. B-1 in order.  No atomics: two runs, and an eager run and a graph replay, leave identical
+ * bits, and the accumulator does not depend on how the rows are cut into batches.  tick != NULL: tick[0] += 1 at the end of
+ * launch 2.
+ * mg_cls_auroc_pairs: the exact one-vs-rest Mann-Whitney counts of a finished pass from its stored probs (n, K) fp64 and
+ * labels (n) int64, 1 <= n <= 131072.  out [4][K] int64 (zeroed by the call): for every class k
+ *   wins[k] = #{(i, j): y_i = k, y_j valid and != k, p_ik > p_jk},  ties[k] likewise with ==,  n_pos[k] = #{y_i = k},
+ *   n_neg[k] = #{y_j valid and != k}
+ * A workgroup owns a tile of 256 rows i and walks tiles of 256 rows j through LDS; counts are summed inside the wave and the
+ * workgroup, then one integer atomicAdd per workgroup, array and class: integer addition does not depend on the order. */
+long mg_cls_eval_acc_words(int n_classes, int n_bins, int n_temps);
+size_t mg_cls_eval_acc_workspace_bytes(int B, int n_temps);
+int mg_cls_eval_acc(const float* logits, const float* clean_logits, int B, int n_classes, const int64_t* labels, int n_bins,
+                    const double* inv_temps, int n_temps, double inv_temperature, void* acc, double* probs, int32_t* row_i,
+                    double* row_d, long dst_rows, const uint64_t* counter, const uint64_t* base, void* work, size_t work_bytes,
+                    uint64_t* tick, mg_stream_t stream);
+int mg_cls_auroc_pairs(const double* probs, const int64_t* labels, long n, int n_classes, int64_t* out, mg_stream_t stream);
+
 /* ---- exact t-SNE of a feature set (melo_gan_amd.gan.tsne, melo_gan_amd.gan.evaluate --tsne; csrc/tsne.hip) ----
  * The reference's tsne.py asks whether the VAE latents cluster by emotion and hands the answer to scikit-learn; here the
  * affinities and the descent run on the device.  4 <= N <= 16384 (the dense P is 1 GiB there), everything fp32 unless said.

@@ -177,6 +177,11 @@ SIGNATURES = {
     "mg_vae_eval_acc_workspace_bytes": (sz, [i32, i32]),
     "mg_vae_eval_acc_reset": (i32, [vp, i32, i32, vp]),
     "mg_vae_eval_acc": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp, sz, vp, vp]),
+    "mg_cls_eval_acc_words": (i64, [i32, i32, i32]),
+    "mg_cls_eval_acc_workspace_bytes": (sz, [i32, i32]),
+    "mg_cls_eval_acc": (i32, [vp, vp, i32, i32, vp, i32, C.POINTER(C.c_double), i32, C.c_double, vp, vp, vp, vp, i64, vp, vp, vp, sz,
+                              vp, vp]),
+    "mg_cls_auroc_pairs": (i32, [vp, vp, i64, i32, vp, vp]),
     "mg_tsne_workspace_bytes": (sz, [i64]),
     "mg_tsne_affinities": (i32, [vp, i64, i32, f32, vp, vp, vp, sz, vp]),
     "mg_tsne_step": (i32, [vp, i64, vp, vp, vp, f32, f32, f32, vp, vp, vp, i64, vp, sz, vp]),

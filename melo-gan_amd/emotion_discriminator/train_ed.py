@@ -9,7 +9,10 @@ Data: the row-aligned arrays the GAN trainer already uses, `<splits_dir>/<stem o
 (kept resident in HBM); the reference's per-file manifest/.npz loader (ed_dataset.py) is out of scope.  Like the
 reference's loaders (no drop_last, ed_dataset.py:542-558) an epoch ends with the trailing partial batch, run by a second
 engine of that batch size over the same parameters (EdEngine.tail); metrics are sample-weighted (train_ed.py:75-82).
---synthetic N trains on N random rolls (smoke runs without the git-ignored dataset).
+--synthetic N trains on N random rolls (smoke runs without the git-ignored dataset).  --eval-test: after training, the best
+checkpoint is loaded into a fresh evaluator (emotion_discriminator.evaluate) and judged on the test split (the validation
+split when there is none); the report goes to <checkpoint_dir>/ed_eval.json.  The training itself is the same with or
+without the flag.
 
 input_mode 'notes' trains the convolutional encoder (EdEngine); 'latent' (the reference's default) trains the MLP on the
 (N, latent_dim) encoder latents that melo_gan_amd.ae.encode exports (EdLatentEngine: two launches per step).  The latents
@@ -204,7 +207,33 @@ def save_checkpoint(eng: EdEngine, cfg: dict, epoch: int, is_best: bool):
     return path
 
 
-def train(cfg: dict, synthetic: int = 0, use_graph: bool = True):
+def eval_best(cfg: dict, synthetic: int, val, device) -> dict:
+    """--eval-test: the best checkpoint in a fresh evaluator on the test split, else on `val` = (x, labels); writes and returns
+    the report."""
+    import json
+    from .evaluate import EdEvaluator
+    ckdir = cfg.get("checkpoint_dir", "data/models/ed")
+    path = os.path.join(ckdir, cfg.get("save_name", "ed_best.pth"))
+    (x, y), source = val, "val"
+    if not synthetic and cfg.get("test_split_csv"):
+        try:
+            x, y = (load_latent_split if cfg.get("input_mode", "latent") == "latent" else load_split)(cfg, "test", device)
+            source = "test"
+        except FileNotFoundError:
+            print("[eval-test] no test split arrays: evaluating the validation split")
+    ev = EdEvaluator(cfg, device, int(cfg.get("batch_size", 64)))
+    ev.load(path)
+    rep = ev.evaluate(x.contiguous(), y.contiguous())
+    rep.update(model=path, split=source)
+    out = os.path.join(ckdir, "ed_eval.json")
+    with open(out, "w") as f:
+        json.dump(rep, f, indent=1, allow_nan=False)
+    print(f"[eval-test] {source}: accuracy {rep['overall']['accuracy']}, macro_f1 {rep['overall']['macro_f1']}, "
+          f"ece {rep['overall']['ece']}, best T {rep['temperature']['best_T']} -> {out}")
+    return rep
+
+
+def train(cfg: dict, synthetic: int = 0, use_graph: bool = True, eval_test: bool = False):
     mode = cfg.get("input_mode", "latent")
     if mode not in ("latent", "notes"):
         raise ValueError("melo_gan_amd.emotion_discriminator.train_ed: input_mode must be 'latent' or 'notes'")
@@ -271,6 +300,8 @@ def train(cfg: dict, synthetic: int = 0, use_graph: bool = True):
             if epoch % cfg.get("save_freq", 5) == 0:
                 save_checkpoint(eng, cfg, epoch, False)
     print("Training Completed. Best epoch:", best_epoch, "Best metric:", best)
+    if eval_test and best_epoch:
+        eval_best(cfg, synthetic, (xv, yv), device)
     return eng, best
 
 
@@ -280,11 +311,12 @@ def main(argv=None):
     ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic rolls instead of the split arrays")
     ap.add_argument("--epochs", type=int, default=None, help="override num_epochs")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--eval-test", action="store_true", help="evaluate the best checkpoint on the test split afterwards")
     args = ap.parse_args(argv)
     cfg = C.load_config(args.config)
     if args.epochs is not None:
         cfg["num_epochs"] = args.epochs
-    train(cfg, args.synthetic, not args.no_graph)
+    train(cfg, args.synthetic, not args.no_graph, args.eval_test)
 
 
 if __name__ == "__main__":

@@ -2084,6 +2084,106 @@ def vae_eval_acc(x, recon, mu, logvar, labels, acc, row_i, row_d, counter, base,
     return acc
 
 
+CLS_MAX_CLASSES, CLS_MAX_BINS, CLS_MAX_TEMPS, CLS_MAX_PAIR_ROWS = 16, 32, 64, 131072
+CLS_INT_FIELDS = ("rows", "correct", "flipped", "confusion", "bin_count", "bin_correct")
+CLS_FIELDS = CLS_INT_FIELDS + ("ce", "brier", "conf", "margin", "bin_conf", "nll_T")
+
+
+def cls_eval_layout(n_classes: int, n_bins: int, n_temps: int) -> dict:
+    """The accumulator of cls_eval_acc (include/melo_gan_hip.h, mg_cls_eval_acc): name -> (offset in 8-byte words inside a
+    true class's block, shape), plus 'block' (7 + K + 3 n_bins + G words) and 'words' (K blocks).  CLS_INT_FIELDS are int64,
+    the rest fp64."""
+    K, nb, G = int(n_classes), int(n_bins), int(n_temps)
+    if not (2 <= K <= CLS_MAX_CLASSES and 1 <= nb <= CLS_MAX_BINS and 1 <= G <= CLS_MAX_TEMPS):
+        raise ValueError("cls_eval_acc: 2..16 classes, 1..32 bins and 1..64 inverse temperatures")
+    lay, off = {}, 0
+    for name, shape in (("rows", ()), ("correct", ()), ("flipped", ()), ("confusion", (K,)), ("bin_count", (nb,)),
+                        ("bin_correct", (nb,)), ("ce", ()), ("brier", ()), ("conf", ()), ("margin", ()), ("bin_conf", (nb,)),
+                        ("nll_T", (G,))):
+        lay[name] = (off, shape)
+        off += math.prod(shape)
+    lay["block"], lay["words"] = off, K * off
+    if lay["words"] != L.load().mg_cls_eval_acc_words(K, nb, G):
+        raise RuntimeError("cls_eval_layout disagrees with mg_cls_eval_acc_words")
+    return lay
+
+
+def cls_eval_views(acc: Tensor, n_classes: int, n_bins: int, n_temps: int) -> dict:
+    """Typed views of an accumulator (device or host int64 tensor of cls_eval_layout(...)['words'] words) by name, each
+    (K, *shape): what emotion_discriminator.metrics.report reads."""
+    lay = cls_eval_layout(n_classes, n_bins, n_temps)
+    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] \
+            or not acc.is_contiguous():
+        raise ValueError(f"cls_eval_acc: the accumulator is a contiguous int64 vector of {lay['words']} words")
+    blocks = acc.view(int(n_classes), lay["block"])
+    out = {}
+    for name in CLS_FIELDS:
+        off, shape = lay[name]
+        v = blocks[:, off:off + math.prod(shape)]
+        out[name] = (v if name in CLS_INT_FIELDS else v.view(torch.float64)).reshape(int(n_classes), *shape)
+    return out
+
+
+def cls_eval_acc_new(n_classes: int, n_bins: int, n_temps: int, device) -> Tensor:
+    """A fresh (zero) accumulator for cls_eval_acc."""
+    return torch.zeros(cls_eval_layout(n_classes, n_bins, n_temps)["words"], dtype=torch.int64, device=device)
+
+
+def cls_eval_acc(logits, labels, acc, probs, row_i, row_d, counter, base, n_bins: int, inv_temps, inv_temperature: float = 1.0,
+                 clean_logits=None, tick=None):
+    """One evaluated batch of the classifier added to the pass's accumulator (mg_cls_eval_acc): logits (B, K) fp32, labels (B,)
+    int64 (outside [0, K): a padding row), acc from cls_eval_acc_new(K, n_bins, len(inv_temps)); probs (dst_rows, K) float64,
+    row_i (dst_rows, 4) int32 and row_d (dst_rows, 4) float64 receive the per-row numbers at split position
+    (counter - base) * B + row.  inv_temps: the G host floats of the temperature grid; inv_temperature scales the logits first.
+    clean_logits (B, K): count the rows whose argmax differs from theirs.  tick: an int64 (1,) batch counter to advance."""
+    _chk(logits, "logits")
+    if logits.dim() != 2 or not 2 <= logits.shape[1] <= CLS_MAX_CLASSES or not 1 <= logits.shape[0] <= 32767:
+        raise ValueError(f"cls_eval_acc: logits (B in 1..32767, K in 2..16) expected, got {tuple(logits.shape)}")
+    B, K = logits.shape
+    _chk(labels, "labels", (B,), torch.int64)
+    if clean_logits is not None:
+        _chk(clean_logits, "clean_logits", (B, K))
+    temps = [float(t) for t in inv_temps]
+    G, nb = len(temps), int(n_bins)
+    if not 1 <= nb <= CLS_MAX_BINS:
+        raise ValueError(f"cls_eval_acc: n_bins = {n_bins}: 1..32")
+    if not 1 <= G <= CLS_MAX_TEMPS or not all(0.0 < t < 1e300 for t in temps + [float(inv_temperature)]):
+        raise ValueError("cls_eval_acc: 1..64 inverse temperatures, each (and inv_temperature) positive and finite")
+    _chk(acc, "acc", (cls_eval_layout(K, nb, G)["words"],), torch.int64)
+    _chk(probs, "probs", dtype=torch.float64)
+    if probs.dim() != 2 or probs.shape[0] < 1 or probs.shape[1] != K:
+        raise ValueError(f"cls_eval_acc: probs (dst_rows, {K}) expected, got {tuple(probs.shape)}")
+    _chk(row_i, "row_i", (probs.shape[0], 4), torch.int32)
+    _chk(row_d, "row_d", (probs.shape[0], 4), torch.float64)
+    _chk(counter, "counter", (1,), torch.int64)
+    _chk(base, "base", (1,), torch.int64)
+    if tick is not None:
+        _chk(tick, "tick", (1,), torch.int64)
+    lib = L.load()
+    work = workspace(lib.mg_cls_eval_acc_workspace_bytes(B, G), logits.device, "cls_eval_acc")
+    L.check(lib.mg_cls_eval_acc(_p(logits), _p(clean_logits), B, K, _p(labels), nb, (C.c_double * G)(*temps), G,
+                                float(inv_temperature), _p(acc), _p(probs), _p(row_i), _p(row_d), probs.shape[0], _p(counter),
+                                _p(base), _p(work), work.numel(), _p(tick), _stream()), "mg_cls_eval_acc")
+    return acc
+
+
+def cls_auroc_pairs(probs, labels, out=None):
+    """The one-vs-rest Mann-Whitney counts of stored probs (n, K) float64 and labels (n,) int64 (mg_cls_auroc_pairs): an
+    int64 (4, K) device tensor wins, ties, n_pos, n_neg.  Labels outside [0, K) take no part.  n <= 131072."""
+    _chk(probs, "probs", dtype=torch.float64)
+    if probs.dim() != 2 or not 2 <= probs.shape[1] <= CLS_MAX_CLASSES or probs.shape[0] < 1:
+        raise ValueError(f"cls_auroc_pairs: probs (n >= 1, K in 2..16) expected, got {tuple(probs.shape)}")
+    n, K = probs.shape
+    if n > CLS_MAX_PAIR_ROWS:
+        raise ValueError(f"cls_auroc_pairs: {n} rows: at most {CLS_MAX_PAIR_ROWS} (the pair count is quadratic)")
+    _chk(labels, "labels", (n,), torch.int64)
+    if out is None:
+        out = torch.zeros(4, K, dtype=torch.int64, device=probs.device)
+    _chk(out, "out", (4, K), torch.int64)
+    L.check(L.load().mg_cls_auroc_pairs(_p(probs), _p(labels), n, K, _p(out), _stream()), "mg_cls_auroc_pairs")
+    return out
+
+
 def wq_table(entries):
     """ctypes table for adam_flat(wq=...): entries = [(start, N, Cc, K, w_sn, w_sc, dst tensor), ...] (mg_wq_entry)."""
     if len(entries) > L.MAX_WQ_ENTRIES:
