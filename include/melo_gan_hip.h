@@ -287,9 +287,10 @@ int mg_conv_thin_route(const float* x, long xbs, int Cin, int N, int K, int stri
  *                   (forward: w_sn = Cin*K, w_sc = K; stride-1 data gradient: flip = 1, w_sn = K, w_sc = Cin*K).
  * mg_conv1d_s1_bf16: y[b,t,n] = EPI( sum_{k,c} x[b, t + k - (K-1)/2, c] * wb[k][n][c] ), K in {3,5}; x is bf16 or (x_f32)
  *                   fp32 converted on the way into LDS; y is bf16 or (y_f32) fp32.  Needs T % 128 == 0, Cin % 32 == 0,
- *                   N % 64 == 0 (mg_conv1d_s1_bf16_supported), dense 16-byte aligned tensors.
+ *                   N % 64 == 0 (mg_conv1d_s1_bf16_supported), dense 16-byte aligned tensors (x, wb, y, zout, gref: a
+ *                   misaligned one is refused before the launch).
  * mg_meanT_fwd_bf16 / mg_meanT_bwd_bf16: the temporal mean (ed_model.py:65) over a bf16 activation and its backward
- *                   fused with act'(gref) * gscale, writing a bf16 gradient. */
+ *                   fused with act'(gref) * gscale, writing a bf16 gradient (C % 8 == 0, dz / gref 16-byte aligned). */
 typedef struct mg_epilogue_bf16 {
     const float* scale;
     const float* shift;

@@ -345,6 +345,8 @@ extern "C" int mg_conv1d_s1_bf16(const void* x, int x_f32, const void* wb, void*
     ConvBP p{};
     p.x = x; p.w = (const __bf16*)wb; p.y = y; p.B = B; p.T = T; p.Cin = Cin; p.N = N;
     if (epi) p.e = *epi;
+    // zout / gref cross the LDS as 16-byte pieces like x and y
+    MG_CHECK_ARG(((((uintptr_t)p.e.zout) | ((uintptr_t)p.e.gref)) & 15) == 0, "mg_conv1d_s1_bf16: zout / gref must be 16-byte aligned");
     MG_CHECK_ARG(!(p.e.scale && !p.e.shift), "mg_conv1d_s1_bf16: scale without shift");
     MG_CHECK_ARG(!(p.e.accumulate && !y_f32), "mg_conv1d_s1_bf16: accumulate needs an fp32 output");
     return K == 3 ? launch_bf16<3>(p, x_f32, y_f32, (hipStream_t)stream) : launch_bf16<5>(p, x_f32, y_f32, (hipStream_t)stream);
@@ -361,6 +363,7 @@ extern "C" int mg_meanT_fwd_bf16(const void* a, float* h, int B, int T, int C, m
 extern "C" int mg_meanT_bwd_bf16(const float* dh, void* dz, const void* gref, int gact, const float* gscale, int B, int T, int C,
                                  mg_stream_t stream) {
     MG_CHECK_ARG(dh && dz && gref && B > 0 && T > 0 && C > 0 && C % 8 == 0, "mg_meanT_bwd_bf16: bad args (C %% 8 == 0)");
+    MG_CHECK_ARG(((((uintptr_t)dz) | ((uintptr_t)gref)) & 15) == 0, "mg_meanT_bwd_bf16: dz / gref must be 16-byte aligned");
     const long n8 = (long)B * T * C / 8;
     hipLaunchKernelGGL(meanT_bwd_bf16_kernel, dim3((unsigned)mg_cdiv(n8, 256)), dim3(256), 0, (hipStream_t)stream, dh, (__bf16*)dz,
                        (const __bf16*)gref, gact, gscale, n8, T, C);

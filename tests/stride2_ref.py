@@ -54,6 +54,19 @@ def gather(x, w):
     return _both(lambda a, b: torch.einsum("btck,nck->btn", _windows_s2(a), b), x, w)
 
 
+def _windows_s2k3(x):
+    """(B, T, C) -> (B, (T - 1) // 2 + 1, C, 3): window k of output t is x[2t + k - 1] (zeros outside)."""
+    B, T, C = x.shape
+    xp = torch.cat([x.new_zeros(B, 1, C), x, x.new_zeros(B, 1, C)], dim=1)
+    return xp.unfold(1, 3, 2)
+
+
+def gather3(x, w):
+    """y[b,t,n] = sum_{c,k} x[b, 2t+k-1, c] w[n,c,k]: Conv1d(k=3, s=2, p=1) forward with w (N, Cin, 3) -- no layer of the
+    models, but thin_in_kernel admits it (Cin <= 8).  Returns (ref, M) in fp64, (B, (T - 1) // 2 + 1, N)."""
+    return _both(lambda a, b: torch.einsum("btck,nck->btn", _windows_s2k3(a), b), x, w)
+
+
 def scatter(x, w, Tout):
     """ConvTranspose1d(k=5, s=2, p=2) forward with w (Cin, N, 5) and Tout = 2 Tin (output_padding 1) or 2 Tin - 1; also
     the Conv1d data gradient (w = the Conv1d's (Cout, Cin, 5) weight).  Returns (ref, M) in fp64, (B, Tout, N)."""
@@ -214,6 +227,9 @@ class Guarded:
 
     def check(self, what=""):
         head, tail = self.canvas[:self.pad], self.canvas[self.canvas.numel() - self.pad:]
+        # a bf16 (or any narrower) canvas holds the sentinel rounded to its dtype: compare with that value
+        sent = self.SENTINEL if self.canvas.dtype == torch.float32 else torch.tensor(self.SENTINEL, dtype=self.canvas.dtype,
+                                                                                     device=self.canvas.device)
         for nm, s in (("before", head), ("after", tail)):
-            bad = (s != self.SENTINEL).nonzero()
+            bad = (s != sent).nonzero()
             assert bad.numel() == 0, f"{what}: {bad.numel()} sentinel element(s) {nm} the output overwritten (first {int(bad[0])})"

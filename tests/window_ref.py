@@ -54,6 +54,21 @@ def gather_s1(x, w, K, flip=False):
     return _both(lambda a, b: torch.einsum("btck,nck->btn", _windows_s1(a, K), b), x, w)
 
 
+def thin(entry, x, w, K, stride, Tout):
+    """(ref, M) of the ops.py entry points csrc/conv_thin.hip serves (tests/thin_bf16_tables.py: ENTRIES), from the
+    references above and stride2_ref's -- no arithmetic of its own.  n = K * x.shape[2]."""
+    import stride2_ref as S
+    if entry == "fwd":
+        return gather_s1(x, w, K) if stride == 1 else (S.gather(x, w) if K == 5 else S.gather3(x, w))
+    if entry == "convT_dgrad":
+        return S.gather(x, w)
+    if entry == "dgrad1":
+        return gather_s1(x, w, K, flip=True)
+    if entry in ("convT_fwd", "dgrad2"):
+        return S.scatter(x, w, Tout)
+    raise ValueError(entry)
+
+
 def perm_index(N, perm_L, device="cpu"):
     """Weight row behind output column n' of mg_linear with perm_L: (n' % C) * L + n' // C, C = N / L (identity for perm_L <= 1)."""
     n = torch.arange(N, device=device)
