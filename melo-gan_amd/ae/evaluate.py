@@ -29,6 +29,7 @@ import torch
 from ..gan.config import load_config
 from ..gan.generate import EMOTIONS
 from ..gan.utils import emotion_to_index
+from ..eval_pass import Packed, ResidentPass, check_split
 from . import metrics as M
 from .encode import load_model
 from .engine import VaeEngine
@@ -65,14 +66,13 @@ class VaeEvaluator:
         eng = self.eng
         self.B, self.K = eng.B, int(n_classes)
         d = eng.dev
-        self.ctr = torch.zeros(1, dtype=torch.int64, device=d)      # batch cursor, advanced by mg_vae_eval_acc
-        self.base = torch.zeros(1, dtype=torch.int64, device=d)
+        self.split_pass = ResidentPass(self.B, d)
+        self.ctr, self.base = self.split_pass.ctr, self.split_pass.base           # batch cursor, advanced by mg_vae_eval_acc
         self.labels = torch.zeros(self.B, dtype=torch.int64, device=d)
         self.words = ops.vae_eval_acc_layout(self.K, eng.latent)["words"]
-        self.buf = self.acc = self.row_d = self.row_i = None         # one buffer, three views of it: one device -> host read
+        self.out = self.acc = self.row_d = self.row_i = None         # one packed buffer, three views of it
         self.mu = self.logvar = self.recon = None                    # split-position arrays of the last pass
         self.acc_host = self.rows = None
-        self._graphs, self._key, self._hold = {}, None, None
 
     def load(self, path: str):
         """The weights and BatchNorm buffers of train_ae's ae_best.pth / ae_final.pth (encode.load_model)."""
@@ -111,48 +111,26 @@ class VaeEvaluator:
         (the accumulator by name) and self.rows (the per-row numbers) are on the host."""
         from .. import ops
         eng, B = self.eng, self.B
-        if not isinstance(notes, torch.Tensor) or not notes.is_cuda or notes.dtype != torch.float32 or not notes.is_contiguous():
-            raise AeEvaluateError("evaluate: the split must be a contiguous fp32 array on the device")
-        if notes.dim() != 3 or tuple(notes.shape[1:]) != (eng.T, 4):
-            raise AeEvaluateError(f"evaluate: the split's notes have shape {tuple(notes.shape)}, the config implies "
-                                  f"(n, {eng.T}, 4)")
-        n = notes.shape[0]
-        if n < 1:
-            raise AeEvaluateError("evaluate: the split is empty")
-        if labels is not None and (not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.int64
-                                   or tuple(labels.shape) != (n,)):
-            raise AeEvaluateError(f"evaluate: labels must be an int64 device array of {n} entries")
+        n = check_split(AeEvaluateError, notes, (eng.T, 4), labels, "the split's notes have", labels_optional=True)
         if labels is not None and bool(((labels < 0) | (labels >= self.K)).any()):
             raise AeEvaluateError(f"evaluate: labels outside [0, {self.K})")
-        nb = (n + B - 1) // B
-        key = (notes.data_ptr(), None if labels is None else labels.data_ptr(), n, bool(keep_recon))
+
+        def build(split):
+            self.out = Packed([("acc", (self.words,), torch.int64), ("row_d", (n, 4), torch.float64), ("row_i", (n, 8), torch.int32)],
+                              eng.dev)
+            self.acc, self.row_d, self.row_i = self.out.dev.values()
+            self.mu, self.logvar = (torch.zeros(n, eng.latent, device=eng.dev) for _ in range(2))
+            self.recon = torch.zeros(n, eng.T, 4, device=eng.dev) if keep_recon else None
+            split.jobs = [(notes, eng.x), (split.labels, self.labels)]
+
         with torch.cuda.stream(eng.stream):
-            if self._key != key:
-                self.buf = torch.zeros(self.words + 4 * n + 4 * n, dtype=torch.int64, device=eng.dev)
-                self.acc = self.buf[:self.words]
-                self.row_d = self.buf[self.words:self.words + 4 * n].view(torch.float64).view(n, 4)
-                self.row_i = self.buf[self.words + 4 * n:].view(torch.int32).view(n, 8)
-                self.mu, self.logvar = (torch.zeros(n, eng.latent, device=eng.dev) for _ in range(2))
-                self.recon = torch.zeros(n, eng.T, 4, device=eng.dev) if keep_recon else None
-                # the labels padded to whole batches with -1: the staging clamps the notes' padding rows into the split
-                pad = torch.full((nb * B,), -1, dtype=torch.int64, device=eng.dev)
-                pad[:n] = 0 if labels is None else labels
-                order = torch.arange(nb * B, dtype=torch.int64, device=eng.dev)
-                jobs = [(notes, eng.x), (pad, self.labels)]
-                self._hold = (notes, labels, pad, order, jobs)
-                self._graphs, self._key = {}, key
-            _, _, _, order, jobs = self._hold
-            eng.eps.zero_()
-            self.buf.zero_()            # the empty accumulator (mg_vae_eval_acc_reset's zeros) and the per-row stashes
-            self.ctr.zero_()
-            for _ in range(nb):         # eager, then captured, then replayed: one graph per batch
-                ops.run_graphed(self._graphs, "batch", lambda: self._launches(jobs, order, nb * B, keep_recon))
-            host = self.buf.cpu()       # the pass's only device -> host read
-        views = {k: v.numpy() for k, v in ops.vae_eval_acc_views(host[:self.words], self.K, eng.latent).items()}
-        self.rows = {"row_d": host[self.words:self.words + 4 * n].view(torch.float64).view(n, 4).numpy(),
-                     "row_i": host[self.words + 4 * n:].view(torch.int32).view(n, 8).numpy()}
-        self.acc_host = views
-        rep = M.report(views, eng.T, eng.latent, names)
+            sp = self.split_pass.bind((notes, labels), (n, bool(keep_recon)), n, labels, build)
+            eng.eps.zero_()             # in front of a new graph's eager run too: a shared engine's eps is the trainer's
+            self.split_pass.run("batch", lambda: self._launches(sp.jobs, sp.order, sp.rows, keep_recon), self.out.buf.zero_)
+            host = self.out.host()      # the pass's only device -> host read
+        self.acc_host = {k: v.numpy() for k, v in ops.vae_eval_acc_views(host["acc"], self.K, eng.latent).items()}
+        self.rows = {"row_d": host["row_d"].numpy(), "row_i": host["row_i"].numpy()}
+        rep = M.report(self.acc_host, eng.T, eng.latent, names)
         rep["rows"], rep["batch"] = n, B
         if labels is None:
             del rep["per_class"]

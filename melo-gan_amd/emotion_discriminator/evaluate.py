@@ -31,6 +31,7 @@ import torch
 
 from ..gan.config import load_config
 from ..gan.generate import EMOTIONS
+from ..eval_pass import Packed, ResidentPass, check_split
 from . import metrics as M
 from .latent_engine import make_engine
 
@@ -85,16 +86,15 @@ class EdEvaluator:
         self.T_grid, self.inv_temps = M.temperature_grid()
         self.G = len(self.inv_temps)
         d = eng.dev
-        self.ctr = torch.zeros(1, dtype=torch.int64, device=d)       # batch cursor, advanced by mg_cls_eval_acc
-        self.base = torch.zeros(1, dtype=torch.int64, device=d)
+        self.split_pass = ResidentPass(self.B, d)
+        self.ctr, self.base = self.split_pass.ctr, self.split_pass.base      # batch cursor, advanced by mg_cls_eval_acc
         self.serial = torch.zeros(1, dtype=torch.int64, device=d)    # the augmentation's serial base of a robustness pass
         self.labels = torch.zeros(self.B, dtype=torch.int64, device=d)
         self.clean = torch.zeros(self.B, K, device=d)                # the clean pass's logits of the batch (robustness)
         self.words = ops.cls_eval_layout(K, self.n_bins, self.G)["words"]
-        self.buf = self.acc = self.probs = self.row_d = self.row_i = self.pair_out = None
+        self.out = self.acc = self.probs = self.row_d = self.row_i = self.pair_out = None      # one packed buffer, five views
         self.logits = self.aug_logits = None                         # split-position arrays of the last pass
         self.acc_host = self.rows = self.pairs = self.calibrated_host = self.labels_host = None
-        self._graphs, self._key, self._hold = {}, None, None
 
     # ---- weights --------------------------------------------------------------------------------------------
     def load(self, path: str):
@@ -146,50 +146,6 @@ class EdEvaluator:
         ops.cls_eval_acc(eng.logits, self.labels, self._aug_acc, self._aug_probs, self._aug_row_i, self._aug_row_d, self.ctr,
                          self.base, self.n_bins, self.inv_temps, clean_logits=self.clean, tick=self.ctr)
 
-    def _check_split(self, x, labels):
-        eng = self.eng
-        row = tuple(eng.x.shape[1:])
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
-            raise EdEvaluateError("evaluate: the split must be a contiguous fp32 array on the device")
-        if tuple(x.shape[1:]) != row or x.dim() != len(row) + 1:
-            raise EdEvaluateError(f"evaluate: the split has shape {tuple(x.shape)}, the config implies (n, "
-                                  f"{', '.join(map(str, row))})")
-        n = x.shape[0]
-        if n < 1:
-            raise EdEvaluateError("evaluate: the split is empty")
-        if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
-            raise EdEvaluateError(f"evaluate: labels must be an int64 device array of {n} entries")
-        return n
-
-    def _prepare(self, x, labels):
-        """The pass's buffers for this split (kept while the same arrays come back: the captured graphs hold their addresses)."""
-        eng, B, K = self.eng, self.B, self.K
-        n = x.shape[0]
-        nb = (n + B - 1) // B
-        key = (x.data_ptr(), labels.data_ptr(), n)
-        if self._key != key:
-            d = eng.dev
-            # one buffer, five views of it: accumulator, pair counts, probs, row_d, row_i -> one device -> host read
-            sizes = (self.words, 4 * K, n * K, 4 * n, 2 * n)
-            self.buf = torch.zeros(sum(sizes), dtype=torch.int64, device=d)
-            parts = torch.split(self.buf, sizes)
-            self.acc, self.pair_out = parts[0], parts[1].view(4, K)
-            self.probs = parts[2].view(torch.float64).view(n, K)
-            self.row_d = parts[3].view(torch.float64).view(n, 4)
-            self.row_i = parts[4].view(torch.int32).view(n, 4)
-            self._sizes = sizes
-            self._logits_pad = torch.zeros(nb * B, K, device=d)
-            self.logits = self._logits_pad[:n]
-            # the labels padded to whole batches with -1: the staging clamps the inputs' padding rows into the split
-            pad = torch.full((nb * B,), -1, dtype=torch.int64, device=d)
-            pad[:n] = labels
-            jobs = [(x, eng.x), (pad, self.labels)]
-            self._order = torch.arange(nb * B, dtype=torch.int64, device=d)
-            self._hold = (x, labels, pad, jobs, nb)
-            self._graphs, self._key = {}, key
-            self._aug_pad = None
-        return self._hold
-
     # ---- the pass ---------------------------------------------------------------------------------------------
     def evaluate(self, x: torch.Tensor, labels: torch.Tensor, calibrate_at: Optional[int] = None) -> dict:
         """One pass over a resident split x (n, max_notes, note_dim) or (n, latent_dim) in row order; returns
@@ -199,25 +155,29 @@ class EdEvaluator:
         self.acc_host (the accumulator by name), self.rows (the per-row records) and self.pairs are on the host."""
         from .. import ops
         eng, B, K = self.eng, self.B, self.K
-        n = self._check_split(x, labels)
+        n = check_split(EdEvaluateError, x, tuple(eng.x.shape[1:]), labels)
         if n > ops.CLS_MAX_PAIR_ROWS:
             raise EdEvaluateError(f"evaluate: {n} rows: the exact AUROC counts pairs of at most {ops.CLS_MAX_PAIR_ROWS} rows")
+
+        def build(split):
+            self.out = Packed([("acc", (self.words,), torch.int64), ("pairs", (4, K), torch.int64), ("probs", (n, K), torch.float64),
+                               ("row_d", (n, 4), torch.float64), ("row_i", (n, 4), torch.int32)], eng.dev)
+            self.acc, self.pair_out, self.probs, self.row_d, self.row_i = self.out.dev.values()
+            self._logits_pad = torch.zeros(split.rows, K, device=eng.dev)
+            self.logits = self._logits_pad[:n]
+            split.jobs = [(x, eng.x), (split.labels, self.labels)]
+            self._aug_pad = None
+
         with torch.cuda.stream(eng.stream):
-            _, _, pad, jobs, nb = self._prepare(x, labels)
-            self.buf.zero_()
-            self.ctr.zero_()
+            sp = self.split_pass.bind((x, labels), (n,), n, labels, build)
             self.base.zero_()
-            for _ in range(nb):         # eager, then captured, then replayed: one graph per batch
-                ops.run_graphed(self._graphs, "batch", lambda: self._batch(jobs, self._order, nb * B))
+            self.split_pass.run("batch", lambda: self._batch(sp.jobs, sp.order, sp.rows), self.out.buf.zero_)
             ops.cls_auroc_pairs(self.probs, labels, self.pair_out)
-            host = self.buf.cpu()       # the pass's only device -> host read
-        parts = torch.split(host, self._sizes)
-        self.acc_host = {k: v.numpy() for k, v in ops.cls_eval_views(parts[0], K, self.n_bins, self.G).items()}
-        self.pairs = parts[1].view(4, K).numpy()
-        self.rows = {"probs": parts[2].view(torch.float64).view(n, K).numpy(),
-                     "row_d": parts[3].view(torch.float64).view(n, 4).numpy(),
-                     "row_i": parts[4].view(torch.int32).view(n, 4).numpy()}
-        self.labels_host = pad[:n].cpu().numpy()
+            host = self.out.host()      # the pass's only device -> host read
+        self.acc_host = {k: v.numpy() for k, v in ops.cls_eval_views(host["acc"], K, self.n_bins, self.G).items()}
+        self.pairs = host["pairs"].numpy()
+        self.rows = {k: host[k].numpy() for k in ("probs", "row_d", "row_i")}
+        self.labels_host = sp.labels[:n].cpu().numpy()
         g = calibrate_at
         if g is None:
             total = self.acc_host["nll_T"].sum(axis=0)
@@ -232,13 +192,13 @@ class EdEvaluator:
         """The accumulator of the last pass's stored logits at temperature T_g: ops.cls_eval_acc over the stored logits, batch
         by batch in the pass's own cuts, with inv_temperature = 1 / T_g.  No forward pass."""
         from .. import ops
-        if self._key is None or self.acc_host is None:
+        if self.split_pass.key is None or self.acc_host is None:
             raise EdEvaluateError("rescored: no pass has run")
         if not 0 <= int(g) < self.G:
             raise EdEvaluateError(f"rescored: grid index {g} outside 0..{self.G - 1}")
         eng, B, K = self.eng, self.B, self.K
-        _, _, pad, _, nb = self._hold
-        n = self.logits.shape[0]
+        sp = self.split_pass.split
+        n, nb, pad = sp.n, sp.nb, sp.labels
         with torch.cuda.stream(eng.stream):
             acc = ops.cls_eval_acc_new(K, self.n_bins, self.G, eng.dev)
             probs = torch.zeros(n, K, dtype=torch.float64, device=eng.dev)
@@ -266,18 +226,18 @@ class EdEvaluator:
         unknown = sorted(set(params) - set(ops.AUG_ED_KEYS))
         if unknown:
             raise EdEvaluateError(f"robustness: unknown augmentation key(s) {unknown}; known: {list(ops.AUG_ED_KEYS)}")
-        n = self._check_split(x, labels)
+        n = check_split(EdEvaluateError, x, tuple(eng.x.shape[1:]), labels)
         if eng.C % 4 or x.data_ptr() % 16:
             raise EdEvaluateError("robustness: the augmentation moves 16-byte pieces: note_dim must be a multiple of 4")
-        if self._key != (x.data_ptr(), labels.data_ptr(), n) or self.acc_host is None:
+        if self.split_pass.key != self.split_pass.key_of((x, labels), n) or self.acc_host is None:
             self.evaluate(x, labels)                # the clean pass these are judged against
-        _, _, pad, _, nb = self._hold
+        sp = self.split_pass.split
         settings = [(k, {k: params.get(k, 0.0)}) for k in ops.AUG_ED_KEYS] + [("all", {k: params.get(k, 0.0) for k in ops.AUG_ED_KEYS})]
         out = {"repeats": int(repeats), "strengths": {k: float(params.get(k, 0.0)) for k in ops.AUG_ED_KEYS}, "passes": {}}
         with torch.cuda.stream(eng.stream):
             if self._aug_pad is None:
                 d = eng.dev
-                self._aug_pad = torch.zeros(nb * B, K, device=d)
+                self._aug_pad = torch.zeros(sp.rows, K, device=d)
                 self._aug_acc = ops.cls_eval_acc_new(K, self.n_bins, self.G, d)
                 self._aug_probs = torch.zeros(n, K, dtype=torch.float64, device=d)
                 self._aug_row_i = torch.zeros(n, 4, dtype=torch.int32, device=d)
@@ -288,13 +248,12 @@ class EdEvaluator:
                     aug = ops.augment_spec("ed", int(self.cfg.get("seed", 42)), **p)
                 except ValueError as e:
                     raise EdEvaluateError(f"robustness: {e}") from e
-                self._aug_acc.zero_()
+                # one graph per augmentation setting, kept across calls; the accumulator is zeroed behind a new one's eager run
                 gkey = "aug:" + name + ":" + ",".join(repr(float(v)) for v in p.values())
                 for rep in range(int(repeats)):
-                    self.ctr.zero_()
-                    self.serial.fill_((si * int(repeats) + rep + 1) * nb * B)
-                    for _ in range(nb):
-                        ops.run_graphed(self._graphs, gkey, lambda: self._aug_batch(x, pad, self._order, nb * B, aug))
+                    self.serial.fill_((si * int(repeats) + rep + 1) * sp.rows)
+                    self.split_pass.run(gkey, lambda: self._aug_batch(x, sp.labels, sp.order, sp.rows, aug),
+                                        None if rep else self._aug_acc.zero_)
                 host = self._aug_acc.cpu()
                 v = {k: a.numpy() for k, a in ops.cls_eval_views(host, K, self.n_bins, self.G).items()}
                 rows = int(v["rows"].sum())

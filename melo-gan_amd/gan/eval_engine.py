@@ -1,16 +1,17 @@
 """What the sampler (gan/generate.py) and the evaluator (gan/evaluate.py) share: one GanEngine of `batch` rows that only ever
-runs in eval mode, the loading of its weights, and the hipGraph of one batch that is replayed until its key changes."""
+runs in eval mode, the loading of its weights, and the cache (eval_pass.GraphCache) of the hipGraph of one batch, replayed
+until its key changes."""
 from __future__ import annotations
 
 import os
 from typing import Optional
 
+from ..eval_pass import GraphCache
 from . import config as C
 
 
 class EvalEngine:
     """Abstract: a subclass sets `error` (GenerateError or EvaluateError: what every check here raises) and _check_config."""
-    eager_once = False              # _graph_for: whether one eager run serves every later capture
 
     def __init__(self, cfg: dict, ed_cfg: Optional[dict], device, batch: int):
         from .engine import GanEngine
@@ -25,7 +26,7 @@ class EvalEngine:
             ed_cfg = dict(input_mode="latent", latent_dim=int(cfg["LATENT_DIM"]), mlp_hidden=[256, 128], n_classes=len(EMOTIONS))
         self.eng = GanEngine(cfg, ed_cfg, device, self.B)
         self.eng.init_weights(int(cfg.get("SEED", 42)))     # defines every parameter, the critic's unused ones included
-        self._graph, self._graph_key, self._warm = None, None, False
+        self.graphs = GraphCache()      # the hipGraph of one batch, replayed until what it froze changes
 
     def _check_config(self, cfg: dict, ed_cfg: Optional[dict]):
         """The subclass's checks of the normalised GAN config and of the ED config (None: no classifier); its module's
@@ -56,15 +57,3 @@ class EvalEngine:
         if not os.path.isfile(path):
             raise self.error(f"ED checkpoint {path} does not exist")
         load_ed_checkpoint(self.eng, path)
-
-    def _graph_for(self, key, launches):
-        """The graph of one batch: launches() captured when `key` (whatever the capture froze: launch arguments, buffers)
-        differs from the last capture's, after one eager launches() that allocates every workspace this set of launches
-        needs.  eager_once: the eager run of the first capture serves the later ones too."""
-        from .. import ops
-        if self._graph_key != key:
-            if not (self.eager_once and self._warm):
-                launches()
-                self._warm = True
-            self._graph, self._graph_key = ops.Graph.capture(launches), key
-        return self._graph

@@ -48,6 +48,7 @@ import torch
 from . import feature_metrics as FM
 from . import generate as G
 from . import music_metrics as MM
+from ..eval_pass import Packed, ResidentPass
 from .eval_engine import EvalEngine
 from .generate import EMOTIONS, GenerateError
 from .utils import check_labels, emotion_to_index
@@ -281,13 +282,13 @@ class Evaluator(EvalEngine):
         self.ed_real = self.has_ed and eng.ed_mode == "notes"
         d = eng.dev
         self.K = len(EMOTIONS)
-        self.ctr = torch.zeros(1, dtype=torch.int64, device=d)       # batch cursor, advanced by mg_eval_acc
-        self.base = torch.zeros(1, dtype=torch.int64, device=d)
+        self.split_pass = ResidentPass(self.B, d, self.graphs)
+        self.ctr, self.base = self.split_pass.ctr, self.split_pass.base      # batch cursor, advanced by mg_eval_acc
         self.acc = ops.eval_acc_new(self.K, eng.C, d)
         self.logits_real = torch.zeros(self.B, self.K, device=d)
         self.feat_real = self.feat_fake = self.feat_train = None      # (whole batches, notes_hidden) stashes in split row order
-        self.music_buf = self.note_acc = self.note_row_i = self.note_row_beats = None      # one buffer, three views of it
-        self._hold = self._labels_host = None
+        self.music_buf = self.note_acc = self.note_row_i = self.note_row_beats = None      # one Packed buffer, three views of it
+        self._labels_host = None
 
     def _check_config(self, cfg: dict, ed_cfg: Optional[dict]):
         check_feature_options(self.features, self.knn_k, ed_cfg)
@@ -392,17 +393,16 @@ class Evaluator(EvalEngine):
         counts = [int(i.numel()) for i in idx]
         Re = [R.index_select(0, i) if c else None for i, c in zip(idx, counts)]
         Fe = [F.index_select(0, i) if c else None for i, c in zip(idx, counts)]
-        # the layout of the result buffer: fp64 kernel sums first, then fp32 margins / distances
+        # the result buffer: the fp64 kernel sums, then the fp32 margins of every pair of sets that holds more than k rows
+        # (fake in real, real in fake: over all rows, then per emotion), then the nearest-training-row distances
         n_sums = 3 + 2 * K + K * K
-        n_f32 = 2 * sum(c for c in [n] + counts if c > k) + (2 * n if train is not None else 0)
-        buf = torch.zeros(8 * n_sums + 4 * n_f32, dtype=torch.uint8, device=dev)
-        ks, fl = buf[:8 * n_sums].view(torch.float64), buf[8 * n_sums:].view(torch.float32)
+        sets = [(tag, A, Bm) for tag, A, Bm in [("", F, R)] + [(str(e), Fe[e], Re[e]) for e in range(K)]
+                if A is not None and A.shape[0] > k]
+        out = Packed([("sums", (n_sums,), torch.float64)] +
+                     [(side + tag, (A.shape[0],), torch.float32) for tag, A, _ in sets for side in ("fr", "rf")] +
+                     ([("nn_fake", (n,), torch.float32), ("nn_real", (n,), torch.float32)] if train is not None else []), dev)
+        ks = out.dev["sums"]
         slot = iter(range(n_sums))
-        cut = [0]
-
-        def take(m):
-            cut[0] += m
-            return fl[cut[0] - m:cut[0]]
 
         def ksum(A, Bm, same):
             i = next(slot)
@@ -410,38 +410,27 @@ class Evaluator(EvalEngine):
                 ops.pair_ksum(A, Bm, ks[i:i + 1], exclude_diag=same)
             return i
 
-        def margins(A, Bm):
-            """(A's rows in Bm's manifold, Bm's rows in A's), or None when the sets hold at most k rows."""
-            m = A.shape[0] if A is not None else 0
-            if m <= k:
-                return None, None
-            out = []
-            for X, Y in ((A, Bm), (Bm, A)):          # Y's radii, then X against Y's manifold
-                nn = torch.empty(m, k, device=dev)
-                ops.pair_knn(Y, Y, nn, exclude_self=True)
-                out.append(ops.pair_margin(X, Y, nn[:, k - 1].contiguous(), take(m)))
-            return out
-
         s_xx, s_yy, s_xy = ksum(R, R, True), ksum(F, F, True), ksum(R, F, False)
         s_xx_e = [ksum(Re[e], Re[e], True) for e in range(K)]
         s_yy_e = [ksum(Fe[e], Fe[e], True) for e in range(K)]
         s_xy_ef = [[ksum(Re[e], Fe[f], False) for f in range(K)] for e in range(K)]
-        m_fr, m_rf = margins(F, R)
-        m_e = [margins(Fe[e], Re[e]) for e in range(K)]
-        nn_fake = nn_real = None
+        for tag, A, Bm in sets:             # A's rows in Bm's manifold ("fr"), Bm's rows in A's ("rf")
+            for side, X, Y in (("fr", A, Bm), ("rf", Bm, A)):          # Y's radii, then X against Y's manifold
+                nn = torch.empty(A.shape[0], k, device=dev)
+                ops.pair_knn(Y, Y, nn, exclude_self=True)
+                ops.pair_margin(X, Y, nn[:, k - 1].contiguous(), out.dev[side + tag])
         if train is not None:
-            nn_fake = ops.pair_knn(F, train, take(n).view(n, 1))
-            nn_real = ops.pair_knn(R, train, take(n).view(n, 1))
-        host = buf.cpu()                                   # every result of the pair kernels in one device -> host read
-        hk, hf = host[:8 * n_sums].view(torch.float64).numpy(), host[8 * n_sums:].view(torch.float32).numpy()
-        at = lambda v: None if v is None else hf[v.storage_offset() - fl.storage_offset():][:v.numel()]  # noqa: E731
+            ops.pair_knn(F, train, out.dev["nn_fake"].view(n, 1))
+            ops.pair_knn(R, train, out.dev["nn_real"].view(n, 1))
+        host = {name: v.numpy() for name, v in out.host().items()}      # every result of the pair kernels in one read
+        hk = host["sums"]
         sums = {"xx": hk[s_xx], "yy": hk[s_yy], "xy": hk[s_xy], "xx_e": [hk[i] for i in s_xx_e], "yy_e": [hk[i] for i in s_yy_e],
                 "xy_ef": [[hk[i] for i in row] for row in s_xy_ef]}
-        marg = {"fake_in_real": at(m_fr), "real_in_fake": at(m_rf), "fake_in_real_e": [at(m[0]) for m in m_e],
-                "real_in_fake_e": [at(m[1]) for m in m_e]}
+        marg = {"fake_in_real": host.get("fr"), "real_in_fake": host.get("rf"),
+                "fake_in_real_e": [host.get(f"fr{e}") for e in range(K)], "real_in_fake_e": [host.get(f"rf{e}") for e in range(K)]}
         block = FM.feature_block(R.shape[1], k, EMOTIONS, counts, sums, marg)
         if train is not None:
-            block["nn_train"] = FM.nn_summary(at(nn_fake), at(nn_real))
+            block["nn_train"] = FM.nn_summary(host["nn_fake"], host["nn_real"])
         return block
 
     def evaluate(self, dataset, seed: int, noise: Optional[torch.Tensor] = None, train_dataset=None) -> dict:
@@ -462,52 +451,47 @@ class Evaluator(EvalEngine):
                                   not noise.is_contiguous() or tuple(noise.shape) != (n, eng.noise_dim)):
             raise EvaluateError(f"evaluate: noise must be a contiguous fp32 device array of shape ({n}, {eng.noise_dim})")
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        nb = (n + B - 1) // B
-        key = (dataset.notes.data_ptr(), dataset.emot_idx.data_ptr(), n, seed, None if noise is None else noise.data_ptr(),
-               self.has_d, self.music)
+        def build(split):
+            if self.features:
+                self.feat_real = torch.zeros(split.rows, eng.ed_feat_dim, device=eng.dev)
+                self.feat_fake = torch.zeros(split.rows, eng.ed_feat_dim, device=eng.dev)
+            if self.music:      # accumulator | per-row fp64 sums | per-row int32 numbers: one device -> host read
+                self.music_buf = Packed([("acc", (ops.note_acc_layout(self.K)["words"],), torch.int64),
+                                         ("row_beats", (2, split.rows, 2), torch.float64),
+                                         ("row_i", (2, split.rows, 8), torch.int32)], eng.dev)
+                self.note_acc, self.note_row_beats, self.note_row_i = self.music_buf.dev.values()
+            split.jobs = [(dataset.notes, eng.real), (dataset.numeric, eng.numeric), (split.labels, eng.emot_idx)]
+            split.dataset = dataset         # held with the keyed arrays for as long as the key stands
+            if eng.latent_dim > 0:
+                split.jobs.append((dataset.latent, eng.latent))
+            if noise is not None:
+                split.jobs.append((noise, eng.noise))
+            # the grouping of the feature metrics and of the per-row note statistics
+            self._labels_host = dataset.emot_idx.cpu() if self.features or self.music else None
+
+        def reset():
+            ops.eval_acc_reset(self.acc, self.K, eng.C)
+            if self.music:
+                self.music_buf.buf.zero_()      # the empty accumulator (mg_note_acc_reset's zeros) and the per-row stashes
+
         train = None
         with torch.cuda.stream(eng.stream):
             if train_dataset is not None:
                 train = self._train_features(train_dataset)
-            if self._graph_key != key:
-                if self.features:
-                    self.feat_real = torch.zeros(nb * B, eng.ed_feat_dim, device=eng.dev)
-                    self.feat_fake = torch.zeros(nb * B, eng.ed_feat_dim, device=eng.dev)
-                if self.music:      # accumulator | per-row fp64 sums | per-row int32 numbers: one device -> host read
-                    words = ops.note_acc_layout(self.K)["words"]
-                    self.music_buf = torch.zeros(words + 2 * nb * B * 2 + 2 * nb * B * 4, dtype=torch.int64, device=eng.dev)
-                    self.note_acc = self.music_buf[:words]
-                    self.note_row_beats = self.music_buf[words:words + 4 * nb * B].view(torch.float64).view(2, nb * B, 2)
-                    self.note_row_i = self.music_buf[words + 4 * nb * B:].view(torch.int32).view(2, nb * B, 8)
-                # the labels padded to whole batches with -1: the staging clamps the other arrays' padding rows into the split
-                labels = torch.full((nb * B,), -1, dtype=torch.int64, device=eng.dev)
-                labels[:n] = dataset.emot_idx
-                order = torch.arange(nb * B, dtype=torch.int64, device=eng.dev)
-                jobs = [(dataset.notes, eng.real), (dataset.numeric, eng.numeric), (labels, eng.emot_idx)]
-                if eng.latent_dim > 0:
-                    jobs.append((dataset.latent, eng.latent))
-                if noise is not None:
-                    jobs.append((noise, eng.noise))
-                # every new key runs eagerly first: other jobs or a music / critic switch can need other workspaces
-                self._graph_for(key, lambda: self._launches(jobs, order, nb * B, n, seed, noise is None))
-                self._hold = (dataset, labels, order, noise)
-                # the grouping of the feature metrics and of the per-row note statistics
-                self._labels_host = dataset.emot_idx.cpu() if self.features or self.music else None
-            ops.eval_acc_reset(self.acc, self.K, eng.C)
-            if self.music:
-                self.music_buf.zero_()          # the empty accumulator (mg_note_acc_reset's zeros) and the per-row stashes
-            self.ctr.zero_()
-            for _ in range(nb):
-                self._graph.launch()
+            sp = self.split_pass.bind((dataset.notes, dataset.emot_idx, noise), (n, seed, self.has_d, self.music), n,
+                                      dataset.emot_idx, build)
+            self.split_pass.run("batch", lambda: self._launches(sp.jobs, sp.order, sp.rows, n, seed, noise is None), reset)
             acc = self.acc.cpu()                # the pass's only device -> host read (with the note statistics' buffer)
-            music_host = self.music_buf.cpu() if self.music else None
+            music_host = self.music_buf.host() if self.music else None
             block = self.feature_space(self._labels_host, n, train) if self.features else None
         raw = raw_from_acc(acc, self.K, eng.C)
         rep = build_report(raw, eng.T, seed, B, self.has_d, self.has_ed, self.ed_real)
         if block is not None:
             rep["feature_space"] = block
         if music_host is not None:
-            rep["music"] = self._music_block(music_host, n, nb)
+            raw = {k: v.numpy() for k, v in ops.note_acc_views(music_host["acc"], self.K).items()}
+            rows = {k: music_host[k].numpy()[:, :n] for k in ("row_i", "row_beats")}
+            rep["music"] = MM.music_block(raw, rows, self._labels_host.numpy(), EMOTIONS)
         return rep
 
     def tsne(self, n: int, stem: str, **params) -> dict:
@@ -530,15 +514,6 @@ class Evaluator(EvalEngine):
         return {"n": 2 * n, "dim": int(X.shape[1]), "rows": "real rows 0..n-1, then generated rows 0..n-1", "params": ts.params(),
                 "kl": ts.kl_, "trace_iters": ts.trace_iters, "kl_trace": ts.kl_trace.tolist(),
                 "files": {k: os.path.basename(v) for k, v in files.items()}}
-
-    def _music_block(self, host: torch.Tensor, n: int, nb: int) -> dict:
-        """The `music` block from the host copy of music_buf (the layout of evaluate())."""
-        from .. import ops
-        words, rows = ops.note_acc_layout(self.K)["words"], nb * self.B
-        raw = {k: v.numpy() for k, v in ops.note_acc_views(host[:words], self.K).items()}
-        beats = host[words:words + 4 * rows].view(torch.float64).view(2, rows, 2).numpy()
-        row_i = host[words + 4 * rows:].view(torch.int32).view(2, rows, 8).numpy()
-        return MM.music_block(raw, {"row_i": row_i[:, :n], "row_beats": beats[:, :n]}, self._labels_host.numpy(), EMOTIONS)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -125,7 +125,6 @@ class Samples:
 class Sampler(EvalEngine):
     """One GanEngine of `batch` rows in eval mode: E_num -> G, and the frozen emotion classifier when ed_cfg is given."""
     error = GenerateError
-    eager_once = True           # a new seed changes a launch argument only: the first eager run's workspaces serve
 
     def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH):
         super().__init__(cfg, ed_cfg, device, batch)
@@ -167,7 +166,9 @@ class Sampler(EvalEngine):
         pred = np.empty(M, np.int64) if self.has_ed else None
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         with torch.cuda.stream(eng.stream):
-            g = self._graph_for(seed, lambda: self._launches(seed))
+            if seed not in self.graphs:         # the seed is a launch argument the capture froze; one graph at a time
+                self.graphs.clear()
+            g = self.graphs.graph(seed, lambda: self._launches(seed))
             self.acc.zero_()
             for c0 in range(0, M, B):
                 chunk = keys[c0:c0 + B]

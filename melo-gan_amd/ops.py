@@ -8,6 +8,7 @@ state_dict layouts.  Nothing here falls back to PyTorch math.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import Optional
 
@@ -1662,53 +1663,123 @@ def emotion_score(logits, target, p_target, pred, acc):
             "mg_emotion_score")
 
 
+_WORD_ITEM = {torch.int64: 8, torch.float64: 8, torch.float32: 4, torch.int32: 4}       # bytes; 4-byte items pack two to a word
+
+
+class Layout:
+    """An int64 buffer cut into typed arrays by name: `blocks` are the leading block dimensions (() for none) and every block
+    holds `fields`, an ordered list of (name, shape, dtype in _WORD_ITEM), each from an 8-byte boundary.  self.off: name ->
+    offset in 8-byte words inside a block; self.block / self.words: the words of one block / of all."""
+    who, what = "Layout", "the buffer"          # the words in front of every message
+
+    def __init__(self, fields, blocks=()):
+        self.fields, self.blocks, self.off, off = [(n, tuple(s), d) for n, s, d in fields], tuple(blocks), {}, 0
+        for name, shape, dtype in self.fields:
+            self.off[name] = off
+            off += self._words(shape, dtype)
+        self.block, self.words = off, math.prod(self.blocks) * off
+
+    @staticmethod
+    def _words(shape, dtype):
+        return (math.prod(shape) * _WORD_ITEM[dtype] + 7) // 8
+
+    def new(self, device) -> Tensor:
+        return torch.zeros(self.words, dtype=torch.int64, device=device)
+
+    def views(self, buf: Tensor) -> dict:
+        """Typed views of a device or host buffer by name, each (*blocks, *shape)."""
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.int64 or buf.dim() != 1 or buf.numel() != self.words \
+                or not buf.is_contiguous():
+            raise ValueError(f"{self.who}: {self.what} is a contiguous int64 vector of {self.words} words")
+        blocks, out = buf.view(*self.blocks, -1), {}
+        for name, shape, dtype in self.fields:
+            v = blocks[..., self.off[name]:self.off[name] + self._words(shape, dtype)]
+            out[name] = (v if dtype == torch.int64 else v.view(dtype))[..., :math.prod(shape)].reshape(*self.blocks, *shape)
+        return out
+
+
+class _Acc(Layout):
+    """One accumulator of an evaluation pass (include/melo_gan_hip.h), described once: blocks () for eval_acc, (2 sides, K) for
+    the note statistics, (K,) for the VAE and the classifier.  self.lay: name -> (offset, shape), 'block' (only where there
+    are blocks) and 'words', which the library's words_fn(*args) confirms.  `who` is the family's name."""
+
+    def __init__(self, who, fields, blocks, words_fn, *args):
+        super().__init__(fields, blocks)
+        self.who, self.what = who, "the accumulator"
+        self.lay = {name: (self.off[name], shape) for name, shape, _ in self.fields}
+        self.lay.update({"block": self.block} if self.blocks else {}, words=self.words)
+        if self.words != getattr(L.load(), words_fn)(*args):
+            raise RuntimeError(f"{who}: the layout disagrees with {words_fn}")
+
+    def on_device(self, acc: Tensor) -> Tensor:
+        """What a launch asks of its accumulator."""
+        return _chk(acc, "acc", (self.words,), torch.int64)
+
+
+def _cursor_scalars(counter, base, tick=None):
+    """The int64 (1,) device scalars of a pass's cursor: counter, base, and the batch counter to advance."""
+    _chk(counter, "counter", (1,), torch.int64)
+    _chk(base, "base", (1,), torch.int64)
+    if tick is not None:
+        _chk(tick, "tick", (1,), torch.int64)
+
+
+def _note_rows(who, x, y, nx, ny):
+    """The two (B, T, 4) note-row batches of note_stats / vae_eval_acc: fp32, B in 1..32767, T in 1..2^20, 16-byte aligned."""
+    _chk(x, nx)
+    if x.dim() != 3:
+        raise ValueError(f"{who}: {nx} (B, T, 4) expected")
+    B, T, C = x.shape
+    if C != 4:
+        raise ValueError(f"{who}: C = {C}: only the (T, 4) note-row format decodes into notes")
+    _chk(y, ny, (B, T, C))
+    if not (1 <= B <= 32767 and 1 <= T <= 1 << 20):
+        raise ValueError(f"{who}: B must be in 1..32767 and T in 1..2^20")
+    if x.data_ptr() % 16 or y.data_ptr() % 16:
+        raise ValueError(f"{who}: {nx} and {ny} must be 16-byte aligned")
+    return B, T
+
+
+def _row_stash(who, row_i, wi, other, name, wo, lead=()):
+    """The per-row stashes of a pass: row_i (*lead, dst_rows, wi) int32 and `other` (*lead, dst_rows, wo) float64; returns
+    dst_rows."""
+    _chk(row_i, "row_i", dtype=torch.int32)
+    if row_i.dim() != len(lead) + 2 or tuple(row_i.shape[:-2]) != lead or row_i.shape[-2] < 1 or row_i.shape[-1] != wi:
+        raise ValueError(f"{who}: row_i ({', '.join(map(str, lead + ('dst_rows', wi)))}) expected, got {tuple(row_i.shape)}")
+    _chk(other, name, lead + (row_i.shape[-2], wo), torch.float64)
+    return row_i.shape[-2]
+
+
+@functools.lru_cache(maxsize=64)
+def _eval_acc(n_classes: int, C: int) -> _Acc:
+    K, C = int(n_classes), int(C)
+    if not (1 <= K <= 32 and 4 <= C <= 1024 and C % 4 == 0):
+        raise ValueError("eval_acc: 1..32 classes and C a multiple of 4 in 4..1024")
+    i, d, f = torch.int64, torch.float64, torch.float32
+    return _Acc("eval_acc", (("n", (K,), i), ("conf_fake", (K, K), i), ("conf_real", (K, K), i), ("d_sum", (2,), d),
+                             ("cls", (2, 2, K), d), ("nsum", (2, K, C), d), ("nsq", (2, K, C), d), ("nmin", (2, K, C), f),
+                             ("nmax", (2, K, C), f)), (), "mg_eval_acc_words", K, C)
+
+
 def eval_acc_layout(n_classes: int, C: int) -> dict:
     """The accumulator of eval_acc (include/melo_gan_hip.h, mg_eval_acc): name -> (offset in 8-byte words, shape), plus
     'words'.  The int64 and fp64 sections count in words; 'nmin' / 'nmax' are fp32, two to a word."""
-    K = int(n_classes)
-    if not (1 <= K <= 32 and 4 <= C <= 1024 and C % 4 == 0):
-        raise ValueError("eval_acc: 1..32 classes and C a multiple of 4 in 4..1024")
-    lay, off = {}, 0
-    for name, shape in (("n", (K,)), ("conf_fake", (K, K)), ("conf_real", (K, K)), ("d_sum", (2,)), ("cls", (2, 2, K)),
-                        ("nsum", (2, K, C)), ("nsq", (2, K, C))):
-        lay[name] = (off, shape)
-        n = 1
-        for s in shape:
-            n *= s
-        off += n
-    lay["nmin"], lay["nmax"] = (off, (2, K, C)), (off + K * C, (2, K, C))
-    lay["words"] = off + 2 * K * C
-    if lay["words"] != L.load().mg_eval_acc_words(K, C):
-        raise RuntimeError("eval_acc_layout disagrees with mg_eval_acc_words")
-    return lay
+    return dict(_eval_acc(n_classes, C).lay)
 
 
 def eval_acc_views(acc: Tensor, n_classes: int, C: int) -> dict:
     """Typed views of an accumulator (device or host int64 tensor of eval_acc_layout(...)['words'] words), by name."""
-    lay = eval_acc_layout(n_classes, C)
-    if acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] or not acc.is_contiguous():
-        raise ValueError(f"eval_acc: the accumulator is a contiguous int64 vector of {lay['words']} words")
-    out = {}
-    for name in ("n", "conf_fake", "conf_real"):
-        off, shape = lay[name]
-        out[name] = acc[off:off + math.prod(shape)].view(shape)
-    for name in ("d_sum", "cls", "nsum", "nsq"):
-        off, shape = lay[name]
-        out[name] = acc[off:off + math.prod(shape)].view(torch.float64).view(shape)
-    for name in ("nmin", "nmax"):
-        off, shape = lay[name]
-        out[name] = acc[off:off + math.prod(shape) // 2].view(torch.float32).view(shape)
-    return out
+    return _eval_acc(n_classes, C).views(acc)
 
 
 def eval_acc_new(n_classes: int, C: int, device) -> Tensor:
     """A fresh (reset) accumulator for eval_acc."""
-    acc = torch.zeros(eval_acc_layout(n_classes, C)["words"], dtype=torch.int64, device=device)
-    return eval_acc_reset(acc, n_classes, C)
+    return eval_acc_reset(_eval_acc(n_classes, C).new(device), n_classes, C)
 
 
 def eval_acc_reset(acc: Tensor, n_classes: int, C: int) -> Tensor:
-    _chk(acc, "acc", (eval_acc_layout(n_classes, C)["words"],), torch.int64)
+    """mg_eval_acc_reset: zeros, and the extremes' identities in 'nmin' / 'nmax'."""
+    _eval_acc(n_classes, C).on_device(acc)
     L.check(L.load().mg_eval_acc_reset(_p(acc), int(n_classes), int(C), _stream()), "mg_eval_acc_reset")
     return acc
 
@@ -1743,11 +1814,9 @@ def eval_acc(real, fake, emot_idx, d_real, d_fake, logits_fake, logits_real, acc
         raise ValueError("eval_acc: B must be in 1..65534")
     if real.data_ptr() % 16 or fake.data_ptr() % 16:
         raise ValueError("eval_acc: real and fake must be 16-byte aligned")
-    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1:
-        raise ValueError("eval_acc: acc is an int64 vector (eval_acc_new)")
     if K is None:
         raise ValueError("eval_acc: without logits, n_classes must be given")
-    _chk(acc, "acc", (eval_acc_layout(K, C)["words"],), torch.int64)
+    _eval_acc(K, C).on_device(acc)
     if tick is not None:
         _chk(tick, "tick", (1,), torch.int64)
     lib = L.load()
@@ -1764,8 +1833,7 @@ def eval_noise(noise, counter, base, n: int, seed: int):
     _chk(noise, "noise")
     if noise.dim() != 2 or not 0 < noise.shape[0] <= 65535:
         raise ValueError("eval_noise: noise (rows, noise_dim) with 1..65535 rows expected")
-    _chk(counter, "counter", (1,), torch.int64)
-    _chk(base, "base", (1,), torch.int64)
+    _cursor_scalars(counter, base)
     if int(n) < 1:
         raise ValueError("eval_noise: the split length must be positive")
     L.check(L.load().mg_eval_noise(_p(noise), noise.shape[0], noise.shape[1], _p(counter), _p(base), int(n),
@@ -1852,8 +1920,7 @@ def scatter_rows_cursor(src, dst, counter, base):
             or src.shape[1] < 1:
         raise ValueError(f"scatter_rows_cursor: src (1..65535 rows, width) and dst (dst_rows, width) expected, got "
                          f"{tuple(src.shape)} and {tuple(dst.shape)}")
-    _chk(counter, "counter", (1,), torch.int64)
-    _chk(base, "base", (1,), torch.int64)
+    _cursor_scalars(counter, base)
     L.check(L.load().mg_scatter_rows_cursor(_p(src), src.shape[0], src.shape[1], _p(dst), dst.shape[0], _p(counter), _p(base),
                                             _stream()), "mg_scatter_rows_cursor")
     return dst
@@ -1932,41 +1999,33 @@ NOTE_ACC_FIELDS = (("counters", (8,)), ("pitch", (128,)), ("velocity", (128,)), 
                    ("interval", (64,)), ("pctm", (12, 12)))
 
 
-def note_acc_layout(n_classes: int) -> dict:
-    """The accumulator of note_stats (include/melo_gan_hip.h, mg_note_stats): name -> (offset in int64 words inside a
-    [side][class] block, shape), plus 'block' (words of one block) and 'words' (2 * K blocks)."""
+@functools.lru_cache(maxsize=64)
+def _note_acc(n_classes: int) -> _Acc:
     K = int(n_classes)
     if not 1 <= K <= 32:
         raise ValueError("note_stats: 1..32 classes")
-    lay, off = {}, 0
-    for name, shape in NOTE_ACC_FIELDS:
-        lay[name] = (off, shape)
-        off += math.prod(shape)
-    lay["block"], lay["words"] = off, 2 * K * off
-    if lay["words"] != L.load().mg_note_acc_words(K):
-        raise RuntimeError("note_acc_layout disagrees with mg_note_acc_words")
-    return lay
+    return _Acc("note_stats", ((n, s, torch.int64) for n, s in NOTE_ACC_FIELDS), (2, K), "mg_note_acc_words", K)
+
+
+def note_acc_layout(n_classes: int) -> dict:
+    """The accumulator of note_stats (include/melo_gan_hip.h, mg_note_stats): name -> (offset in int64 words inside a
+    [side][class] block, shape), plus 'block' (words of one block) and 'words' (2 * K blocks)."""
+    return dict(_note_acc(n_classes).lay)
 
 
 def note_acc_views(acc: Tensor, n_classes: int) -> dict:
     """Views of an accumulator (device or host int64 tensor of note_acc_layout(...)['words'] words) by name, each
     (2 sides, K, *shape)."""
-    lay = note_acc_layout(n_classes)
-    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] \
-            or not acc.is_contiguous():
-        raise ValueError(f"note_stats: the accumulator is a contiguous int64 vector of {lay['words']} words")
-    blocks = acc.view(2, int(n_classes), lay["block"])
-    return {name: blocks[:, :, off:off + math.prod(shape)].reshape(2, int(n_classes), *shape)
-            for name, (off, shape) in ((n, lay[n]) for n, _ in NOTE_ACC_FIELDS)}
+    return _note_acc(n_classes).views(acc)
 
 
 def note_acc_new(n_classes: int, device) -> Tensor:
     """A fresh (zero) accumulator for note_stats."""
-    return torch.zeros(note_acc_layout(n_classes)["words"], dtype=torch.int64, device=device)
+    return _note_acc(n_classes).new(device)
 
 
 def note_acc_reset(acc: Tensor, n_classes: int) -> Tensor:
-    _chk(acc, "acc", (note_acc_layout(n_classes)["words"],), torch.int64)
+    _note_acc(n_classes).on_device(acc)
     L.check(L.load().mg_note_acc_reset(_p(acc), int(n_classes), _stream()), "mg_note_acc_reset")
     return acc
 
@@ -1976,70 +2035,46 @@ def note_stats(real, fake, emot_idx, acc, row_i, row_beats, counter, base, n_cla
     emot_idx (B,) int64 (-1 = a padding row), acc from note_acc_new(n_classes), row_i (2, dst_rows, 8) int32 and row_beats
     (2, dst_rows, 2) float64 receive the per-row numbers at split position (counter - base) * B + row; counter / base: int64
     device scalars (1,).  Goes in front of eval_acc, which advances the counter."""
-    _chk(real, "real")
-    if real.dim() != 3:
-        raise ValueError("note_stats: real (B, T, 4) expected")
-    B, T, C = real.shape
-    if C != 4:
-        raise ValueError(f"note_stats: C = {C}: only the (T, 4) note-row format decodes into notes")
-    _chk(fake, "fake", (B, T, C))
+    B, T = _note_rows("note_stats", real, fake, "real", "fake")
     _chk(emot_idx, "emot_idx", (B,), torch.int64)
-    if not (1 <= B <= 32767 and 1 <= T <= 1 << 20):
-        raise ValueError("note_stats: B must be in 1..32767 and T in 1..2^20")
-    if real.data_ptr() % 16 or fake.data_ptr() % 16:
-        raise ValueError("note_stats: real and fake must be 16-byte aligned")
     K = int(n_classes)
-    _chk(acc, "acc", (note_acc_layout(K)["words"],), torch.int64)
-    _chk(row_i, "row_i", dtype=torch.int32)
-    if row_i.dim() != 3 or row_i.shape[0] != 2 or row_i.shape[1] < 1 or row_i.shape[2] != 8:
-        raise ValueError(f"note_stats: row_i (2, dst_rows, 8) expected, got {tuple(row_i.shape)}")
-    _chk(row_beats, "row_beats", (2, row_i.shape[1], 2), torch.float64)
-    _chk(counter, "counter", (1,), torch.int64)
-    _chk(base, "base", (1,), torch.int64)
-    L.check(L.load().mg_note_stats(_p(real), _p(fake), B, T, C, _p(emot_idx), K, _p(acc), _p(row_i), _p(row_beats),
-                                   row_i.shape[1], _p(counter), _p(base), _stream()), "mg_note_stats")
+    _note_acc(K).on_device(acc)
+    dst_rows = _row_stash("note_stats", row_i, 8, row_beats, "row_beats", 2, lead=(2,))
+    _cursor_scalars(counter, base)
+    L.check(L.load().mg_note_stats(_p(real), _p(fake), B, T, 4, _p(emot_idx), K, _p(acc), _p(row_i), _p(row_beats), dst_rows,
+                                   _p(counter), _p(base), _stream()), "mg_note_stats")
     return acc
+
+
+@functools.lru_cache(maxsize=64)
+def _vae_eval_acc(n_classes: int, latent_dim: int) -> _Acc:
+    K, Ld = int(n_classes), int(latent_dim)
+    if not (1 <= K <= 32 and 1 <= Ld <= 1024):
+        raise ValueError("vae_eval_acc: 1..32 classes and a latent width in 1..1024")
+    d = torch.float64
+    return _Acc("vae_eval_acc", (("c", (16,), torch.int64), ("se", (4,), d), ("ae", (4,), d), ("beats_abs", (2,), d),
+                                 ("lat", (5, Ld), d)), (K,), "mg_vae_eval_acc_words", K, Ld)
 
 
 def vae_eval_acc_layout(n_classes: int, latent_dim: int) -> dict:
     """The accumulator of vae_eval_acc (include/melo_gan_hip.h, mg_vae_eval_acc): name -> (offset in 8-byte words inside a
     class's block, shape), plus 'block' (words of one block, 26 + 5 L) and 'words' (K blocks).  'c' is int64, the rest fp64."""
-    K, Ld = int(n_classes), int(latent_dim)
-    if not (1 <= K <= 32 and 1 <= Ld <= 1024):
-        raise ValueError("vae_eval_acc: 1..32 classes and a latent width in 1..1024")
-    lay, off = {}, 0
-    for name, shape in (("c", (16,)), ("se", (4,)), ("ae", (4,)), ("beats_abs", (2,)), ("lat", (5, Ld))):
-        lay[name] = (off, shape)
-        off += math.prod(shape)
-    lay["block"], lay["words"] = off, K * off
-    if lay["words"] != L.load().mg_vae_eval_acc_words(K, Ld):
-        raise RuntimeError("vae_eval_acc_layout disagrees with mg_vae_eval_acc_words")
-    return lay
+    return dict(_vae_eval_acc(n_classes, latent_dim).lay)
 
 
 def vae_eval_acc_views(acc: Tensor, n_classes: int, latent_dim: int) -> dict:
     """Typed views of an accumulator (device or host int64 tensor of vae_eval_acc_layout(...)['words'] words) by name, each
     (K, *shape): what ae.metrics.report reads."""
-    lay = vae_eval_acc_layout(n_classes, latent_dim)
-    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] \
-            or not acc.is_contiguous():
-        raise ValueError(f"vae_eval_acc: the accumulator is a contiguous int64 vector of {lay['words']} words")
-    blocks = acc.view(int(n_classes), lay["block"])
-    out = {}
-    for name in ("c", "se", "ae", "beats_abs", "lat"):
-        off, shape = lay[name]
-        v = blocks[:, off:off + math.prod(shape)]
-        out[name] = (v if name == "c" else v.view(torch.float64)).reshape(int(n_classes), *shape)
-    return out
+    return _vae_eval_acc(n_classes, latent_dim).views(acc)
 
 
 def vae_eval_acc_new(n_classes: int, latent_dim: int, device) -> Tensor:
     """A fresh (zero) accumulator for vae_eval_acc."""
-    return torch.zeros(vae_eval_acc_layout(n_classes, latent_dim)["words"], dtype=torch.int64, device=device)
+    return _vae_eval_acc(n_classes, latent_dim).new(device)
 
 
 def vae_eval_acc_reset(acc: Tensor, n_classes: int, latent_dim: int) -> Tensor:
-    _chk(acc, "acc", (vae_eval_acc_layout(n_classes, latent_dim)["words"],), torch.int64)
+    _vae_eval_acc(n_classes, latent_dim).on_device(acc)
     L.check(L.load().mg_vae_eval_acc_reset(_p(acc), int(n_classes), int(latent_dim), _stream()), "mg_vae_eval_acc_reset")
     return acc
 
@@ -2049,37 +2084,21 @@ def vae_eval_acc(x, recon, mu, logvar, labels, acc, row_i, row_d, counter, base,
     labels (B,) int64 (-1 = a padding row), acc from vae_eval_acc_new(n_classes, L); row_i (dst_rows, 8) int32 and row_d
     (dst_rows, 4) float64 receive the per-row numbers at split position (counter - base) * B + row; counter / base: int64
     device scalars (1,).  tick: an int64 (1,) batch counter to advance (usually `counter` itself)."""
-    _chk(x, "x")
-    if x.dim() != 3:
-        raise ValueError("vae_eval_acc: x (B, T, 4) expected")
-    B, T, C = x.shape
-    if C != 4:
-        raise ValueError(f"vae_eval_acc: C = {C}: only the (T, 4) note-row format decodes into notes")
-    _chk(recon, "recon", (B, T, C))
+    B, T = _note_rows("vae_eval_acc", x, recon, "x", "recon")
     _chk(mu, "mu")
     if mu.dim() != 2 or mu.shape[0] != B or not 1 <= mu.shape[1] <= 1024:
         raise ValueError(f"vae_eval_acc: mu (B, L) with L in 1..1024 expected, got {tuple(mu.shape)}")
     Ld = mu.shape[1]
     _chk(logvar, "logvar", (B, Ld))
     _chk(labels, "labels", (B,), torch.int64)
-    if not (1 <= B <= 32767 and 1 <= T <= 1 << 20):
-        raise ValueError("vae_eval_acc: B must be in 1..32767 and T in 1..2^20")
-    if x.data_ptr() % 16 or recon.data_ptr() % 16:
-        raise ValueError("vae_eval_acc: x and recon must be 16-byte aligned")
     K = int(n_classes)
-    _chk(acc, "acc", (vae_eval_acc_layout(K, Ld)["words"],), torch.int64)
-    _chk(row_i, "row_i", dtype=torch.int32)
-    if row_i.dim() != 2 or row_i.shape[0] < 1 or row_i.shape[1] != 8:
-        raise ValueError(f"vae_eval_acc: row_i (dst_rows, 8) expected, got {tuple(row_i.shape)}")
-    _chk(row_d, "row_d", (row_i.shape[0], 4), torch.float64)
-    _chk(counter, "counter", (1,), torch.int64)
-    _chk(base, "base", (1,), torch.int64)
-    if tick is not None:
-        _chk(tick, "tick", (1,), torch.int64)
+    _vae_eval_acc(K, Ld).on_device(acc)
+    dst_rows = _row_stash("vae_eval_acc", row_i, 8, row_d, "row_d", 4)
+    _cursor_scalars(counter, base, tick)
     lib = L.load()
     work = workspace(lib.mg_vae_eval_acc_workspace_bytes(B, Ld), x.device, "vae_eval_acc")
-    L.check(lib.mg_vae_eval_acc(_p(x), _p(recon), B, T, C, _p(mu), _p(logvar), Ld, _p(labels), K, _p(acc), _p(row_i), _p(row_d),
-                                row_i.shape[0], _p(counter), _p(base), _p(work), work.numel(), _p(tick), _stream()),
+    L.check(lib.mg_vae_eval_acc(_p(x), _p(recon), B, T, 4, _p(mu), _p(logvar), Ld, _p(labels), K, _p(acc), _p(row_i), _p(row_d),
+                                dst_rows, _p(counter), _p(base), _p(work), work.numel(), _p(tick), _stream()),
             "mg_vae_eval_acc")
     return acc
 
@@ -2089,44 +2108,32 @@ CLS_INT_FIELDS = ("rows", "correct", "flipped", "confusion", "bin_count", "bin_c
 CLS_FIELDS = CLS_INT_FIELDS + ("ce", "brier", "conf", "margin", "bin_conf", "nll_T")
 
 
+@functools.lru_cache(maxsize=64)
+def _cls_eval_acc(n_classes: int, n_bins: int, n_temps: int) -> _Acc:
+    K, nb, G = int(n_classes), int(n_bins), int(n_temps)
+    if not (2 <= K <= CLS_MAX_CLASSES and 1 <= nb <= CLS_MAX_BINS and 1 <= G <= CLS_MAX_TEMPS):
+        raise ValueError("cls_eval_acc: 2..16 classes, 1..32 bins and 1..64 inverse temperatures")
+    shapes = {"confusion": (K,), "bin_count": (nb,), "bin_correct": (nb,), "bin_conf": (nb,), "nll_T": (G,)}     # the rest: scalars
+    return _Acc("cls_eval_acc", ((n, shapes.get(n, ()), torch.int64 if n in CLS_INT_FIELDS else torch.float64) for n in CLS_FIELDS),
+                (K,), "mg_cls_eval_acc_words", K, nb, G)
+
+
 def cls_eval_layout(n_classes: int, n_bins: int, n_temps: int) -> dict:
     """The accumulator of cls_eval_acc (include/melo_gan_hip.h, mg_cls_eval_acc): name -> (offset in 8-byte words inside a
     true class's block, shape), plus 'block' (7 + K + 3 n_bins + G words) and 'words' (K blocks).  CLS_INT_FIELDS are int64,
     the rest fp64."""
-    K, nb, G = int(n_classes), int(n_bins), int(n_temps)
-    if not (2 <= K <= CLS_MAX_CLASSES and 1 <= nb <= CLS_MAX_BINS and 1 <= G <= CLS_MAX_TEMPS):
-        raise ValueError("cls_eval_acc: 2..16 classes, 1..32 bins and 1..64 inverse temperatures")
-    lay, off = {}, 0
-    for name, shape in (("rows", ()), ("correct", ()), ("flipped", ()), ("confusion", (K,)), ("bin_count", (nb,)),
-                        ("bin_correct", (nb,)), ("ce", ()), ("brier", ()), ("conf", ()), ("margin", ()), ("bin_conf", (nb,)),
-                        ("nll_T", (G,))):
-        lay[name] = (off, shape)
-        off += math.prod(shape)
-    lay["block"], lay["words"] = off, K * off
-    if lay["words"] != L.load().mg_cls_eval_acc_words(K, nb, G):
-        raise RuntimeError("cls_eval_layout disagrees with mg_cls_eval_acc_words")
-    return lay
+    return dict(_cls_eval_acc(n_classes, n_bins, n_temps).lay)
 
 
 def cls_eval_views(acc: Tensor, n_classes: int, n_bins: int, n_temps: int) -> dict:
     """Typed views of an accumulator (device or host int64 tensor of cls_eval_layout(...)['words'] words) by name, each
     (K, *shape): what emotion_discriminator.metrics.report reads."""
-    lay = cls_eval_layout(n_classes, n_bins, n_temps)
-    if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or acc.dim() != 1 or acc.numel() != lay["words"] \
-            or not acc.is_contiguous():
-        raise ValueError(f"cls_eval_acc: the accumulator is a contiguous int64 vector of {lay['words']} words")
-    blocks = acc.view(int(n_classes), lay["block"])
-    out = {}
-    for name in CLS_FIELDS:
-        off, shape = lay[name]
-        v = blocks[:, off:off + math.prod(shape)]
-        out[name] = (v if name in CLS_INT_FIELDS else v.view(torch.float64)).reshape(int(n_classes), *shape)
-    return out
+    return _cls_eval_acc(n_classes, n_bins, n_temps).views(acc)
 
 
 def cls_eval_acc_new(n_classes: int, n_bins: int, n_temps: int, device) -> Tensor:
     """A fresh (zero) accumulator for cls_eval_acc."""
-    return torch.zeros(cls_eval_layout(n_classes, n_bins, n_temps)["words"], dtype=torch.int64, device=device)
+    return _cls_eval_acc(n_classes, n_bins, n_temps).new(device)
 
 
 def cls_eval_acc(logits, labels, acc, probs, row_i, row_d, counter, base, n_bins: int, inv_temps, inv_temperature: float = 1.0,
@@ -2149,16 +2156,13 @@ def cls_eval_acc(logits, labels, acc, probs, row_i, row_d, counter, base, n_bins
         raise ValueError(f"cls_eval_acc: n_bins = {n_bins}: 1..32")
     if not 1 <= G <= CLS_MAX_TEMPS or not all(0.0 < t < 1e300 for t in temps + [float(inv_temperature)]):
         raise ValueError("cls_eval_acc: 1..64 inverse temperatures, each (and inv_temperature) positive and finite")
-    _chk(acc, "acc", (cls_eval_layout(K, nb, G)["words"],), torch.int64)
+    _cls_eval_acc(K, nb, G).on_device(acc)
     _chk(probs, "probs", dtype=torch.float64)
     if probs.dim() != 2 or probs.shape[0] < 1 or probs.shape[1] != K:
         raise ValueError(f"cls_eval_acc: probs (dst_rows, {K}) expected, got {tuple(probs.shape)}")
     _chk(row_i, "row_i", (probs.shape[0], 4), torch.int32)
     _chk(row_d, "row_d", (probs.shape[0], 4), torch.float64)
-    _chk(counter, "counter", (1,), torch.int64)
-    _chk(base, "base", (1,), torch.int64)
-    if tick is not None:
-        _chk(tick, "tick", (1,), torch.int64)
+    _cursor_scalars(counter, base, tick)
     lib = L.load()
     work = workspace(lib.mg_cls_eval_acc_workspace_bytes(B, G), logits.device, "cls_eval_acc")
     L.check(lib.mg_cls_eval_acc(_p(logits), _p(clean_logits), B, K, _p(labels), nb, (C.c_double * G)(*temps), G,

@@ -141,30 +141,35 @@ def test_run_graphed_goes_eager_then_captures_then_replays():
         assert graphs["j"] == "warm"
 
 
-def test_eval_engine_graph_cache_rules(monkeypatch):
-    """EvalEngine._graph_for with a stand-in for ops.Graph.capture: the Sampler runs eagerly once in its life and re-captures
-    on a new seed; the Evaluator runs eagerly in front of every capture, a returning key included; neither touches a graph
-    whose key holds.  A capture that raises leaves the old key: the next call captures again."""
+def test_graph_cache_rules(monkeypatch):
+    """eval_pass.GraphCache (under the Sampler and the three evaluators) with a stand-in for ops.Graph.capture: a key seen
+    for the first time runs eagerly once in front of its capture; a key that holds is not touched, a returning one included;
+    clear() forgets every graph.  A capture that raises stores nothing: the keys before it stand, the next call captures
+    again."""
     from melo_gan_amd import ops
-    from melo_gan_amd.gan.evaluate import Evaluator
-    from melo_gan_amd.gan.generate import Sampler
+    from melo_gan_amd.eval_pass import GraphCache
     log = []
     monkeypatch.setattr(ops.Graph, "capture", staticmethod(lambda fn: (log.append("capture"), fn(), object())[-1]))
-    for cls, want in ((Sampler, ["launch", "capture", "launch", "capture", "launch", "capture", "launch"]),
-                      (Evaluator, ["launch", "capture", "launch", "launch", "capture", "launch", "launch", "capture", "launch"])):
-        e = object.__new__(cls)                 # the cache alone: no engine, no device
-        e._graph, e._graph_key, e._warm = None, None, False
-        del log[:]
-        launches = lambda: log.append("launch")  # noqa: E731
-        g1 = e._graph_for(1, launches)
-        assert e._graph_for(1, launches) is g1
-        g2 = e._graph_for(2, launches)
-        assert g2 is not g1 and e._graph_for(2, launches) is g2
-        assert e._graph_for(1, launches) not in (g1, g2)
-        assert log == want, (cls.__name__, log)
+    c = GraphCache()
+    launches = lambda: log.append("launch")  # noqa: E731
+    g1 = c.graph(1, launches)
+    assert c.graph(1, launches) is g1
+    g2 = c.graph(2, launches)
+    assert g2 is not g1 and c.graph(2, launches) is g2
+    assert c.graph(1, launches) is g1 and 1 in c and 2 in c and 3 not in c
+    assert log == ["launch", "capture", "launch", "launch", "capture", "launch"], log
 
-        def fail():
-            raise RuntimeError("capture failed")
-        with pytest.raises(RuntimeError):
-            e._graph_for(3, fail)
-        assert e._graph_key == 1
+    def fail():
+        raise RuntimeError("capture failed")
+    with pytest.raises(RuntimeError):
+        c.graph(3, fail)
+    assert 3 not in c and c.graph(1, launches) is g1 and c.graph(2, launches) is g2
+    del log[:]
+    monkeypatch.setattr(ops.Graph, "capture", staticmethod(lambda fn: (_ for _ in ()).throw(RuntimeError("locked"))))
+    with pytest.raises(RuntimeError):
+        c.graph(3, launches)                      # the eager run passed, the capture itself refused
+    assert log == ["launch"] and 3 not in c and c.graph(1, launches) is g1
+    monkeypatch.setattr(ops.Graph, "capture", staticmethod(lambda fn: (log.append("capture"), fn(), object())[-1]))
+    c.clear()
+    assert 1 not in c and c.graph(1, launches) not in (g1, g2)
+    assert log == ["launch", "launch", "capture", "launch"], log

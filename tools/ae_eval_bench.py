@@ -22,7 +22,7 @@ import torch  # noqa: E402
 import melo_gan_amd  # noqa: E402,F401
 from melo_gan_amd import ops  # noqa: E402
 from melo_gan_amd.ae.evaluate import VaeEvaluator  # noqa: E402
-from _timeit import timeit  # noqa: E402
+from _timeit import alternate, timeit  # noqa: E402
 
 HBM_ACHIEVABLE = 6.3e12
 PASSES = 60          # timed window: 60 passes of 16 batches = 960 replays
@@ -44,27 +44,12 @@ def main():
     rep = ev.evaluate(notes, labels)                    # every buffer and workspace exists from here on
     assert rep["rows"] == n
     eng = ev.eng
-    _, _, _, order, jobs = ev._hold
-    nb = (n + B - 1) // B
-    times = {"with": [], "without": []}
+    sp = ev.split_pass.split
+    nb = sp.nb
     with torch.cuda.stream(eng.stream):
-        graphs = {name: ops.Graph.capture(lambda m=m: ev._launches(jobs, order, nb * B, False, metrics=m))
+        graphs = {name: ops.Graph.capture(lambda m=m: ev._launches(sp.jobs, sp.order, sp.rows, False, metrics=m))
                   for name, m in (("with", True), ("without", False))}
-        for _ in range(args.repeats):
-            for name, gr in graphs.items():
-                ev.ctr.zero_()
-                for _ in range(16):
-                    gr.launch()
-                torch.cuda.synchronize()
-                e0, e1 = ops.Event(), ops.Event()
-                e0.record()
-                for _ in range(PASSES):
-                    ev.ctr.zero_()
-                    for _ in range(16):
-                        gr.launch()
-                e1.record()
-                torch.cuda.synchronize()
-                times[name].append(e0.elapsed_ms(e1) / (16 * PASSES) * 1e3)
+        times = alternate(graphs, ev.ctr.zero_, args.repeats, PASSES)
         print(f"B={B} T={T} L={L}: replayed evaluation batch, us", flush=True)
         for name, ts in times.items():
             print(f"  {name:8s} metrics  {' '.join(f'{t:8.2f}' for t in ts)}   median {med(ts):8.2f}", flush=True)

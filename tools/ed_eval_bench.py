@@ -43,7 +43,8 @@ def main():
     rep = ev.evaluate(x, y)                             # every buffer and workspace exists from here on
     assert rep["rows"] == n
     eng = ev.eng
-    _, _, _, jobs, nb = ev._hold
+    sp = ev.split_pass.split
+    nb = sp.nb
 
     def timed(fn):
         ts = []
@@ -58,7 +59,7 @@ def main():
         return ts
 
     with torch.cuda.stream(eng.stream):
-        graphs = {name: ops.Graph.capture(lambda m=m: ev._batch(jobs, ev._order, nb * B, metrics=m))
+        graphs = {name: ops.Graph.capture(lambda m=m: ev._batch(sp.jobs, sp.order, sp.rows, metrics=m))
                   for name, m in (("with", True), ("without", False))}
 
         def a_pass(gr):

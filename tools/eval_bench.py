@@ -31,7 +31,7 @@ from melo_gan_amd import ops  # noqa: E402
 from melo_gan_amd.gan import evaluate as EV  # noqa: E402
 from melo_gan_amd.gan.config import default_ed_cfg, default_gan_cfg  # noqa: E402
 from melo_gan_amd.gan.dataset import GANDataset  # noqa: E402
-from _timeit import timeit  # noqa: E402
+from _timeit import alternate, timeit  # noqa: E402
 
 HBM_ACHIEVABLE = 6.3e12
 PASSES = 60          # timed window: 60 passes of 16 batches = 960 replays, a few tenths of a second
@@ -75,33 +75,13 @@ def batch_graphs(ev, ds, n, variants):
     """One captured evaluation batch per variant: name -> a function that sets the evaluator up for that variant's capture and
     returns the `metrics` argument of _launches."""
     eng = ev.eng
-    _, labels, order, _ = ev._hold
-    jobs = [(ds.notes, eng.real), (ds.numeric, eng.numeric), (labels, eng.emot_idx), (ds.latent, eng.latent)]
+    sp = ev.split_pass.split
+    jobs = [(ds.notes, eng.real), (ds.numeric, eng.numeric), (sp.labels, eng.emot_idx), (ds.latent, eng.latent)]
     graphs = {}
     for name, prepare in variants:
         metrics = prepare()
-        graphs[name] = ops.Graph.capture(lambda: ev._launches(jobs, order, n, n, 1, True, metrics=metrics))
+        graphs[name] = ops.Graph.capture(lambda: ev._launches(jobs, sp.order, n, n, 1, True, metrics=metrics))
     return graphs
-
-
-def time_graphs(ev, graphs, repeats):
-    times = {k: [] for k in graphs}
-    for _ in range(repeats):
-        for name, g in graphs.items():
-            ev.ctr.zero_()
-            for _ in range(16):
-                g.launch()
-            torch.cuda.synchronize()
-            e0, e1 = ops.Event(), ops.Event()
-            e0.record()
-            for _ in range(PASSES):
-                ev.ctr.zero_()
-                for _ in range(16):
-                    g.launch()
-            e1.record()
-            torch.cuda.synchronize()
-            times[name].append(e0.elapsed_ms(e1) / (16 * PASSES) * 1e3)
-    return times
 
 
 def music_leg(repeats, med):
@@ -124,7 +104,7 @@ def music_leg(repeats, med):
     with torch.cuda.stream(eng.stream):
         graphs = batch_graphs(ev, ds, n, (("with", variant(True)), ("without", variant(False))))
         ev.music = True
-        times = time_graphs(ev, graphs, repeats)
+        times = alternate(graphs, ev.ctr.zero_, repeats, PASSES)
     print(f"music: B={B} T={T} C={C}: replayed evaluation batch, us", flush=True)
     for name, ts in times.items():
         print(f"  {name:8s} note_stats  {' '.join(f'{t:8.2f}' for t in ts)}   median {med(ts):8.2f}", flush=True)
@@ -169,7 +149,7 @@ def main():
         eng = ev.eng
         with torch.cuda.stream(eng.stream):
             graphs = batch_graphs(ev, ds, n, (("with", lambda: True), ("without", lambda: False)))
-            times = time_graphs(ev, graphs, args.repeats)
+            times = alternate(graphs, ev.ctr.zero_, args.repeats, PASSES)
         print(f"{tag}: B={B} T={T} C={C}: replayed evaluation batch, us", flush=True)
         for name, ts in times.items():
             print(f"  {name:8s} metrics  {' '.join(f'{t:8.2f}' for t in ts)}   median {med(ts):8.2f}", flush=True)
