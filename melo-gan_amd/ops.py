@@ -665,6 +665,8 @@ def _sn_jobs(layers, bwd):
     arr = (L.SnJob * len(layers))()
     for a, ly in zip(arr, layers):
         w, we, u, v, sg = ly["w_orig"], ly["w_eff"], ly["u"], ly["v"], ly["sigma"]
+        if not isinstance(w, torch.Tensor) or w.dim() < 1 or w.numel() == 0:
+            raise ValueError("spectral_norm: w_orig must be a non-empty (out, ...) tensor")
         rows = w.shape[0]
         cols = w.numel() // rows
         _chk(w, "w_orig")
