@@ -840,6 +840,17 @@ int mg_adam_flat(float* p, const float* g, float* m, float* v, long n,
                  float lr, float beta1, float beta2, float eps, float weight_decay,
                  double* state, float grad_scale, const float* gs_dev, int state_ticked, uint64_t* rng_step,
                  const mg_wq_entry* table, int n_table, mg_stream_t stream);
+/* ---- exponential moving average of a flat parameter buffer (csrc/ema.hip): the rider behind the generator's mg_adam_flat ----
+ * Per element, in fp64, every operation rounded on its own (no contraction):
+ *     shadow[i] = shadow[i] + (1.0 - d) * ((double)p[i] - shadow[i])
+ * d is computed on the device: t = adam_state[0] - 1 - step_offset (adam_state: mg_adam_flat's `state`, already advanced by the
+ * update in front of this launch and only read here; step_offset: the step count at which averaging began, so t = averaged
+ * updates before this one); d = ramp ? min(decay, (1 + t) / (10 + t)) : decay, an IEEE fp64 divide.  Only `shadow` is written:
+ * one launch, hipGraph-replayable with constant arguments.  -1 before any launch for n < 1, decay outside [0, 1) or a null
+ * pointer; non-finite parameters propagate into the shadow.  n need not be a multiple of 4; 16-byte aligned p and shadow take
+ * the vector path. */
+int mg_ema_flat(const float* p, double* shadow, long n, double decay, int ramp, const double* adam_state, double step_offset,
+                mg_stream_t stream);
 /* out[0] = sqrt(sum g^2) ; out[1] = min(1, max_norm/(norm+1e-6))  (clip_grad_norm_, train_ae.py:121) */
 int mg_grad_norm_clip(const float* g, long n, float max_norm, float* out, void* work, size_t work_bytes,
                       mg_stream_t stream);

@@ -186,6 +186,7 @@ SIGNATURES = {
     "mg_tsne_affinities": (i32, [vp, i64, i32, f32, vp, vp, vp, sz, vp]),
     "mg_tsne_step": (i32, [vp, i64, vp, vp, vp, f32, f32, f32, vp, vp, vp, i64, vp, sz, vp]),
     "mg_adam_flat": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, f32, vp, i32, vp, vp, i32, vp]),
+    "mg_ema_flat": (i32, [vp, vp, i64, C.c_double, i32, vp, C.c_double, vp]),
     "mg_mlp_cls_fwd_bwd": (i32, [C.POINTER(MlpCls), i32, vp, vp, vp, vp, i64, vp, i64, vp, i32, i32, i32, f32, C.c_uint64, vp, vp, f32, f32,
                                  vp, vp, vp, vp]),
     "mg_mlp_cls_wgrad_update": (i32, [C.POINTER(MlpCls), i32, vp, vp, C.POINTER(i64), C.POINTER(i64), i64, vp, vp, vp, vp, i32, f32, f32,

@@ -206,6 +206,8 @@ class DataParallel:
         import torch
         keep = [e.D.data, e.D.grad, e.D.m, e.D.v, e.D.state, e.GE.data, e.GE.grad, e.GE.m, e.GE.v, e.GE.state, e.rng_step]
         keep += list(e.Gbuf.values())
+        if getattr(e, "ema", None) is not None:
+            keep.append(e.ema)          # the dry steps' generator updates move the shadow too
         saved = [t.clone() for t in keep]
         nbt, ticked = e.num_batches_tracked, (e.D.ticked, e.GE.ticked)
         dry, self._dry = self._dry, True

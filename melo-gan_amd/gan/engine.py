@@ -36,6 +36,7 @@ import torch
 from .. import ops
 from ..ops import ACT_GELU, ACT_LRELU, ACT_RELU
 from ..emotion_discriminator.layers import tail_bwd, tail_fwd
+from .ema import ema_config
 
 Tensor = torch.Tensor
 BN_EPS, BN_MOM, P_DROP = 1e-5, 0.1, 0.2
@@ -178,6 +179,7 @@ class GanEngine:
         if ed_dtype not in ("fp32", "bf16"):
             raise ValueError(f"ed_dtype={ed_dtype!r}: expected 'fp32' or 'bf16'")
         self.ed_dtype = ed_dtype
+        self.ema_decay, self.ema_ramp = ema_config(cfg)       # EMA_DECAY / EMA_RAMP: validated before anything is allocated
         self.cfg, self.ed_cfg = dict(cfg), dict(ed_cfg)
         self.dev = torch.device(device)
         B = self.B = int(batch_size or cfg.get("BATCH_SIZE", 32))
@@ -218,6 +220,11 @@ class GanEngine:
                      "decoder.deconv.4.running_mean": torch.zeros(64, device=d),
                      "decoder.deconv.4.running_var": torch.ones(64, device=d)}
         self.num_batches_tracked = 0
+        self.bn_mom = BN_MOM        # momentum of G's train-mode BatchNorm launches (eval_engine.recalibrate_bn passes 1 / (j + 1))
+        # EMA_DECAY > 0: an fp64 shadow of the flat G + E_num buffer, updated by one launch behind every generator update
+        # (g_update); off -- the default -- nothing is allocated and no launch is added
+        self.ema = torch.zeros(self.GE.n, dtype=torch.float64, device=d) if self.ema_decay > 0.0 else None
+        self.ema_offset = 0.0       # the generator's Adam step count where averaging began (ema_reset)
         self.ed_scale = [torch.empty(co, device=d) for (_, co, _) in self.ed_chans]
         self.ed_shift = [torch.empty(co, device=d) for (_, co, _) in self.ed_chans]
         # the frozen ED's conv weights re-laid once as (Cin, Cout, K): its forward then takes the window GEMM's CNK
@@ -504,6 +511,7 @@ class GanEngine:
         for k in self.EDbuf:
             self.EDbuf[k].copy_(BED[k])
         self.params_changed()
+        self.ema_reset()
 
     def init_weights(self, seed: int = 42):
         """weights_init (src/gan/utils.py:37-45): N(0, 0.02) on every Conv*/Linear* weight of E_num, G, D,
@@ -528,6 +536,41 @@ class GanEngine:
                 bound = 1.0 / math.sqrt(fan_in)
                 self.ED.p[k].copy_((torch.rand(s, generator=g) * 2 - 1) * bound)
         self.params_changed()
+        self.ema_reset()
+
+    # -------------------------------------------------------------------------------------
+    # the averaged generator (EMA_DECAY > 0)
+    # -------------------------------------------------------------------------------------
+    def ema_reset(self, shadow: Optional[Tensor] = None, offset: Optional[float] = None):
+        """Start averaging here: the shadow becomes the current parameters and the ramp counts from the generator's current
+        Adam step -- after init_weights / load_state (which call this) or a resume without an `ema` block.  shadow / offset: the
+        resumed values of a checkpoint's `ema` block instead.  Call between steps, never inside one; a no-op with EMA_DECAY 0."""
+        if self.ema is None:
+            return
+        if shadow is None:
+            self.ema.copy_(self.GE.data[:self.GE.n])          # fp32 -> fp64, exact
+        else:
+            if shadow.numel() != self.GE.n:
+                raise ValueError(f"ema_reset: the shadow holds {shadow.numel()} values, the generator + encoder {self.GE.n}")
+            self.ema.copy_(shadow.reshape(-1).to(torch.float64))
+        offset = float(self.GE.state[0].item() if offset is None else offset)
+        if offset != self.ema_offset and getattr(self, "_graphs", None):
+            if self.capture_locked:
+                raise RuntimeError("ema_reset: after DataParallel.prepare() -- the captured generator update holds the offset")
+            self._graphs.clear()            # the offset is a launch argument the captured generator updates froze
+        self.ema_offset = offset
+
+    def ema_state_dicts(self):
+        """{'G', 'E_num'}: the averaged parameters as float64 CPU tensors under the state-dict keys (no BatchNorm buffers: the
+        raw weights' running statistics are not the averaged weights' -- eval_engine.recalibrate_bn)."""
+        if self.ema is None:
+            raise RuntimeError("ema_state_dicts: averaging is off (EMA_DECAY = 0)")
+        host = self.ema.cpu()
+        G, E = OrderedDict(), OrderedDict()
+        for k, shape in self.GE.spec.items():
+            o, n = self.GE.offsets[k]
+            (G if k.startswith("G.") else E)[k[2:]] = host[o:o + n].view(shape).clone()
+        return {"G": G, "E_num": E}
 
     def state_dicts(self):
         """{'G','E_num','D','ED'} -> reference-format state_dicts (CPU)."""
@@ -785,10 +828,10 @@ class GanEngine:
             if parts is not None:
                 ops.bn_train_fwd_parts(parts[0], parts[1], groups, z, a, P(name + ".weight"), P(name + ".bias"),
                                        self.Gbuf[name + ".running_mean"], self.Gbuf[name + ".running_var"], mean, invstd,
-                                       ACT_RELU, BN_MOM, BN_EPS)
+                                       ACT_RELU, self.bn_mom, BN_EPS)
                 return
             ops.bn_train_fwd(z, a, P(name + ".weight"), P(name + ".bias"), self.Gbuf[name + ".running_mean"],
-                             self.Gbuf[name + ".running_var"], mean, invstd, ACT_RELU, BN_MOM, BN_EPS, groups=groups)
+                             self.Gbuf[name + ".running_var"], mean, invstd, ACT_RELU, self.bn_mom, BN_EPS, groups=groups)
         else:
             ops.bn_eval_fwd(z, a, P(name + ".weight"), P(name + ".bias"), self.Gbuf[name + ".running_mean"],
                             self.Gbuf[name + ".running_var"], ACT_RELU, BN_EPS)
@@ -1391,6 +1434,8 @@ class GanEngine:
             self.coll.reduce_g(self)        # C3
             self._p2_pending = self._a_p0_gathered = False
         self._adam(self.GE, self.lr_g)
+        if self.ema is not None:            # reads the updated parameters and the advanced Adam state; writes the shadow only
+            ops.ema_flat(self.GE.data, self.ema, self.GE.n, self.ema_decay, self.ema_ramp, self.GE.state, self.ema_offset)
         self._stamp(6)
 
     # -------------------------------------------------------------------------------------

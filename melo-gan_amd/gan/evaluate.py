@@ -9,6 +9,11 @@ ed_model.py):
         [--ckpt <CHECKPOINT_DIR>/gan_final.pth | gan_epochNNNN.pth] [--split <VAL_SPLIT>] [--feats <ENCODER_FEATS_VAL>] \
         [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--seed <SEED>] [--batch 64] \
         [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3] [--tsne]] [--memorisation] [--music-metrics]
+        [--ema]
+
+--ema evaluates the averaged generator in the `ema` block of a full checkpoint (EMA_DECAY, gan/ema.py) with that checkpoint's
+critic -- the critic has no average; the noise is keyed by (seed, split row), so the same checkpoint and seed with and without
+--ema is a paired comparison.  eval.json records "weights": "ema" | "raw".
 
 One pass over the split in row order.  Per batch ONE replayed hipGraph: stage the batch by a device-side cursor -> noise
 (mg_eval_noise: Philox keyed by (seed, split row), so the report does not depend on the batch size) -> E_num -> G (eval:
@@ -543,6 +548,7 @@ def parse_args(argv=None):
     ap.add_argument("--tsne", action="store_true",
                     help="also embed the real and the generated features jointly by exact t-SNE and write <out stem>_tsne.npy / "
                          ".svg (needs --feature-metrics)")
+    ap.add_argument("--ema", action="store_true", help="evaluate the averaged weights in a full checkpoint's 'ema' block")
     return ap.parse_args(argv)
 
 
@@ -565,6 +571,7 @@ class Plan:
     train_arrays: Optional[tuple] = None
     music: bool = False
     tsne: bool = False
+    ema: bool = False
 
 
 def plan(args) -> Plan:
@@ -590,6 +597,10 @@ def plan(args) -> Plan:
     check_music_options(music, cfg, args.batch)
     ckpt = G.load_checkpoint(ckpt_path, err=EvaluateError)
     has_critic = check_checkpoint(ckpt, cfg, ckpt_path)
+    ema = bool(getattr(args, "ema", False))
+    if ema:
+        from .eval_engine import ema_checkpoint
+        G.check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, EvaluateError), cfg, ckpt_path, err=EvaluateError)
     ed_cfg = None
     if args.ed_config is not None:
         ed_cfg = G._read_config(args.ed_config, "ED config", EvaluateError)
@@ -612,7 +623,7 @@ def plan(args) -> Plan:
     out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/gan/logs"), "eval.json")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
     return Plan(cfg, ed_cfg, ckpt_path, ckpt, has_critic, args.ed_ckpt, arrays, int(args.synthetic), seed, args.batch, out,
-                features, knn_k, memorisation, train_arrays, music, tsne)
+                features, knn_k, memorisation, train_arrays, music, tsne, ema)
 
 
 def main(argv=None) -> int:
@@ -637,13 +648,13 @@ def main(argv=None) -> int:
                                          int(cfg.get("SEED", 42)), "cuda") if p.synthetic else
                     GANDataset(*p.train_arrays, int(cfg["LATENT_DIM"]), "cuda", resident=True))
     ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch, features=p.features, knn_k=p.knn_k, music=p.music)
-    ev.load_generator(p.ckpt)
+    weights = ev.load_generator(p.ckpt, ema=p.ema)
     if p.has_critic:
         ev.load_critic(p.ckpt)
     if p.ed_cfg is not None:
         ev.load_ed(p.ed_ckpt)
     rep = ev.evaluate(ds, p.seed, train_dataset=train_ds)
-    rep["checkpoint"], rep["ed_checkpoint"] = p.ckpt_path, p.ed_ckpt
+    rep["checkpoint"], rep["ed_checkpoint"], rep["weights"] = p.ckpt_path, p.ed_ckpt, weights
     os.makedirs(os.path.dirname(os.path.abspath(p.out)), exist_ok=True)
     if p.tsne:
         rep["tsne"] = ev.tsne(rep["n"], os.path.splitext(p.out)[0], seed=p.seed)

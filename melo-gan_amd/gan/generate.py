@@ -6,8 +6,10 @@ hold; its only generation code left is the Flask route, app.py:53-65,92-119):
     python -m melo_gan_amd.gan.generate --config config/gan_config.yaml \
         [--ckpt <CHECKPOINT_DIR>/gan_final.pth] [--emotion happy|sad|angry|calm|all] \
         [--samples <N_SAMPLES_PER_EMOTION>] [--out <SAMPLE_DIR>] [--seed <SEED>] [--batch 64] \
-        [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth]
+        [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--ema]
 
+--ema samples from the averaged generator in the `ema` block of a full gan_epochNNNN.pth (trained with EMA_DECAY > 0;
+gan_final_ema.pth is an ordinary checkpoint and needs no flag); summary.json records "weights": "ema" | "raw".
 writes <out>/test_<emotion>_<k>.mid for k = 1..N (the reference's file names) with app.py's scale and tempo per emotion,
 and <out>/summary.json with the frozen emotion classifier's verdict on every sample when one is given.
 
@@ -207,6 +209,7 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=DEFAULT_BATCH, help="rows per replayed chunk")
     ap.add_argument("--ed_config", type=str, default=None, help="ED config of the classifier that scores the samples")
     ap.add_argument("--ed_ckpt", type=str, default=None, help="ED checkpoint (ed_best.pth)")
+    ap.add_argument("--ema", action="store_true", help="sample from the averaged weights in a full checkpoint's 'ema' block")
     return ap.parse_args(argv)
 
 
@@ -222,6 +225,7 @@ class Plan:
     out: str
     seed: int
     batch: int
+    ema: bool = False
 
 
 def _read_config(path: str, what: str, err=GenerateError) -> dict:
@@ -260,7 +264,12 @@ def plan(args) -> Plan:
     if int(cfg["NOTE_DIM"]) != 4:
         raise GenerateError(f"NOTE_DIM = {cfg['NOTE_DIM']}: the MIDI writer reads (pitch, velocity, duration, step) rows")
     ckpt = load_checkpoint(ckpt_path)
-    check_generator_checkpoint(ckpt, cfg, ckpt_path)
+    ema = bool(getattr(args, "ema", False))
+    if ema:
+        from .eval_engine import ema_checkpoint
+        check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, GenerateError), cfg, ckpt_path)
+    else:
+        check_generator_checkpoint(ckpt, cfg, ckpt_path)
     ed_cfg = None
     if args.ed_config is not None:
         ed_cfg = _read_config(args.ed_config, "ED config")
@@ -269,7 +278,7 @@ def plan(args) -> Plan:
             raise GenerateError(f"ED checkpoint {args.ed_ckpt} does not exist")
     out = args.out or cfg.get("SAMPLE_DIR", "experiments/gan/samples")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
-    return Plan(cfg, ed_cfg, ckpt_path, ckpt, args.ed_ckpt, emotions, samples, out, seed, args.batch)
+    return Plan(cfg, ed_cfg, ckpt_path, ckpt, args.ed_ckpt, emotions, samples, out, seed, args.batch, ema)
 
 
 def midi_name(emotion: str, k: int) -> str:
@@ -287,7 +296,7 @@ def write_outputs(p: Plan, res: Samples) -> dict:
         files.append({"file": midi_name(e, k), "emotion": e, "k": k,
                       "ed_pred": None if res.pred is None else EMOTIONS[int(res.pred[i])],
                       "ed_p_target": None if res.p_target is None else float(res.p_target[i])})
-    summary = {"checkpoint": p.ckpt_path, "ed_checkpoint": p.ed_ckpt, "seed": p.seed, "samples": p.samples,
+    summary = {"checkpoint": p.ckpt_path, "weights": "ema" if p.ema else "raw", "ed_checkpoint": p.ed_ckpt, "seed": p.seed, "samples": p.samples,
                "batch": p.batch, "emotions": p.emotions, "per_emotion": res.summary, "files": files}
     with open(os.path.join(p.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
@@ -304,7 +313,7 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
     sampler = Sampler(p.cfg, p.ed_cfg, "cuda", p.batch)
-    sampler.load_generator(p.ckpt)
+    sampler.load_generator(p.ckpt, ema=p.ema)
     if p.ed_cfg is not None:
         sampler.load_ed(p.ed_ckpt)
     res = sampler.sample(p.emotions, p.samples, p.seed)

@@ -12,7 +12,9 @@ per-epoch scalars are accumulated on the device and read back once per epoch (th
 three times per batch, train_gan.py:205,250-251).  Extra flags (--synthetic, --epochs, --no-graph) exist
 for smoke runs without the (git-ignored) dataset.  --eval-every N (not in the reference, which never looks at held-out data
 while it trains) evaluates the current weights on VAL_SPLIT every N epochs (gan/evaluate.py) and logs Val/W_dist,
-Val/ED_Acc_Fake, Val/ED_CE_Fake and Val/ED_Acc_Real; it changes nothing the training step reads.
+Val/ED_Acc_Fake, Val/ED_CE_Fake and Val/ED_Acc_Real; it changes nothing the training step reads.  EMA_DECAY d in (0, 1) (gan/ema.py; off by
+default) keeps an exponential moving average of G and E_num behind every generator update: full checkpoints gain an `ema` key,
+gan_final_ema.pth holds the averaged generator as an ordinary {G, E_num} file, and --eval-every also logs ValEMA/*.
 
 Data parallel (not in the reference, which is single-GPU): launched under torch.distributed.run
 (`--nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`) every rank holds a replica, takes every N-th batch of the
@@ -23,6 +25,8 @@ import argparse
 import json
 import os
 import time
+
+from collections import OrderedDict
 
 import torch
 
@@ -100,15 +104,42 @@ def spectral_norm_weight(sd: dict, key: str):
     return None
 
 
-def save_checkpoint(eng: GanEngine, path: str, epoch=None, full=True):
-    """train_gan.py:267-282: {'epoch','G','D','E_num','opt_G','opt_D'} every SAVE_FREQ epochs; final {'G','E_num'}."""
+def save_checkpoint(eng: GanEngine, path: str, epoch=None, full=True, ema=None):
+    """train_gan.py:267-282: {'epoch','G','D','E_num','opt_G','opt_D'} every SAVE_FREQ epochs; final {'G','E_num'}.  ema: the
+    block of ema_block() -- one more key, 'ema', of a full checkpoint (the reference's loaders index by key and ignore it)."""
     sd = eng.state_dicts()
     if not full:
         torch.save({"G": sd["G"], "E_num": sd["E_num"]}, path)
         return
     betas = tuple(eng.betas)
-    torch.save({"epoch": epoch, "G": sd["G"], "D": sd["D"], "E_num": sd["E_num"],
-                "opt_G": adam_state_dict(eng.GE, eng.lr_g, betas), "opt_D": adam_state_dict(eng.D, eng.lr_d, betas)}, path)
+    ck = {"epoch": epoch, "G": sd["G"], "D": sd["D"], "E_num": sd["E_num"],
+          "opt_G": adam_state_dict(eng.GE, eng.lr_g, betas), "opt_D": adam_state_dict(eng.D, eng.lr_d, betas)}
+    if ema is not None:
+        ck["ema"] = ema
+    torch.save(ck, path)
+
+
+def ema_block(eng: GanEngine, calib) -> dict:
+    """The `ema` key of a full checkpoint: decay, ramp, offset; 'G' under G's state-dict keys -- the parameters float64 from the
+    shadow, the BatchNorm buffers float32 from `calib` (an EvalEngine that holds the averaged weights, after recalibrate_bn),
+    num_batches_tracked int64 -- and 'E_num', float64."""
+    sd = eng.ema_state_dicts()
+    G = OrderedDict()
+    for k, v in sd["G"].items():
+        G[k] = v
+        if k in ("decoder.deconv.1.bias", "decoder.deconv.4.bias"):     # BN buffers follow weight/bias
+            base = k[:-len("bias")]
+            G[base + "running_mean"] = calib.eng.Gbuf[base + "running_mean"].cpu().clone()
+            G[base + "running_var"] = calib.eng.Gbuf[base + "running_var"].cpu().clone()
+            G[base + "num_batches_tracked"] = torch.tensor(calib.eng.num_batches_tracked, dtype=torch.int64)
+    return {"decay": float(eng.ema_decay), "ramp": bool(eng.ema_ramp), "offset": float(eng.ema_offset), "G": G, "E_num": sd["E_num"]}
+
+
+def save_ema_final(block: dict, path: str):
+    """gan_final_ema.pth: gan_final.pth's keys with the averaged parameters rounded to float32 and the recalibrated buffers --
+    an ordinary generator checkpoint (the reference's app.py loads it as it is)."""
+    f32 = lambda sd: OrderedDict((k, v.float() if v.is_floating_point() else v) for k, v in sd.items())  # noqa: E731
+    torch.save({"G": f32(block["G"]), "E_num": f32(block["E_num"])}, path)
 
 
 def adam_state_dict(fp, lr: float, betas, eps: float = 1e-8, weight_decay: float = 0.0) -> dict:
@@ -158,6 +189,21 @@ def load_adam_state_dict(fp, sd: dict):
     fp.state[0], fp.state[1], fp.state[2] = step, float(b1) ** step, float(b2) ** step
 
 
+def _replay_beta_powers(fp, betas):
+    """The running beta powers exactly as the update kernels hold them after fp.state[0] steps: a product in fp64, one factor
+    per step, of the betas rounded to fp32 (they are float launch arguments).  load_adam_state_dict's closed form differs from
+    it in the last bits (beta2 = 0.9 is not an fp32 number), enough to move single weights of a resumed run by an ulp."""
+    step = int(fp.state[0].item())
+    if step < 1:
+        return
+    b1, b2 = (torch.tensor(float(b), dtype=torch.float32).item() for b in betas)
+    p1 = p2 = 1.0
+    for _ in range(step):
+        p1 *= b1
+        p2 *= b2
+    fp.state[1], fp.state[2] = p1, p2
+
+
 def load_generator_state(eng: GanEngine, ck: dict):
     """G (with its BatchNorm running statistics) and E_num of a checkpoint dict -- gan_final.pth or gan_epochNNNN.pth, of
     this trainer or the reference's.  The caller runs eng.params_changed() once everything is loaded."""
@@ -180,7 +226,27 @@ def resume_checkpoint(eng: GanEngine, path: str) -> int:
         eng.num_batches_tracked = int(nbt[0])
     load_adam_state_dict(eng.GE, ck["opt_G"])
     load_adam_state_dict(eng.D, ck["opt_D"])
+    for fp in (eng.GE, eng.D):
+        _replay_beta_powers(fp, eng.betas)
     eng.params_changed()
+    blk = ck.get("ema")
+    if eng.ema is None:
+        if blk is not None:
+            print(f"[WARN] {path} holds averaged weights ('ema') but EMA_DECAY is 0: the block is ignored and averaging stays off")
+    elif blk is None:
+        eng.ema_reset()         # averaging starts here: the shadow is the resumed weights, the ramp counts from this step
+    else:
+        if float(blk["decay"]) != eng.ema_decay or bool(blk["ramp"]) != eng.ema_ramp:
+            print(f"[WARN] {path}: averaged with EMA_DECAY {blk['decay']} / EMA_RAMP {blk['ramp']}, continuing with "
+                  f"{eng.ema_decay} / {eng.ema_ramp}")
+        shadow = torch.zeros(eng.GE.n, dtype=torch.float64)
+        for k, shape in eng.GE.spec.items():
+            src = blk["G" if k.startswith("G.") else "E_num"][k[2:]]
+            if tuple(src.shape) != tuple(shape):
+                raise ValueError(f"{path}: ema.{k}: shape {tuple(src.shape)} != {tuple(shape)}")
+            o, n = eng.GE.offsets[k]
+            shadow[o:o + n] = src.reshape(-1).to(torch.float64)
+        eng.ema_reset(shadow, float(blk["offset"]))     # its BatchNorm buffers are recomputed at the next save, never resumed
     return int(ck.get("epoch") or 0)
 
 
@@ -224,13 +290,29 @@ def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: 
     dp = DataParallel(eng, world, dist)
     dp.broadcast_params()
     eng.seed(cfg.get("SEED", 42) + rank)            # rank-offset Philox key: every shard draws its own noise
+    ema_on = eng.ema is not None
+    if ema_on and world > 1 and not resume:
+        eng.ema_reset()             # the shadow of the broadcast parameters: every rank keeps its own, and they stay identical
+    if ema_on:
+        log(f"[INFO] Averaging the generator: EMA_DECAY {eng.ema_decay}, ramp {'on' if eng.ema_ramp else 'off'}, from "
+            f"generator step {int(eng.ema_offset)}")
     writer = _scalar_writer(cfg.get("LOG_DIR", "experiments/gan/logs")) if rank == 0 else None
     os.makedirs(cfg.get("CHECKPOINT_DIR", "experiments/gan/checkpoints"), exist_ok=True)
     os.makedirs(cfg.get("SAMPLE_DIR", "experiments/gan/samples"), exist_ok=True)
     critic_iters = cfg.get("CRITIC_ITERS", 5)
     sums = torch.zeros(3, device=device)        # sum loss_d, sum g_adv, sum g_emo (device-side accumulation)
     shuffle_gen = torch.Generator().manual_seed(cfg.get("SEED", 42))
+    if resume:
+        # continue the two random streams where the checkpointed run left them, so that the resumed epochs are the ones an
+        # uninterrupted run would have trained: the Philox step counter (advanced once per batch, by the critic's update) and
+        # the shuffle generator (one permutation per epoch)
+        eng.rng_step.fill_(int(eng.D.state[0].item()))
+        for _ in range(start_epoch):
+            torch.randperm(len(ds), generator=shuffle_gen)
     evaluator = val_ds = None
+    if ema_on and rank == 0:        # holds the averaged weights while their BatchNorm statistics are recomputed (save, ValEMA)
+        from .evaluate import Evaluator
+        evaluator = Evaluator(cfg, ed_cfg, device, B)
     if eval_every > 0 and rank == 0:
         from .evaluate import Evaluator
         if synthetic:
@@ -239,8 +321,19 @@ def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: 
         else:
             val_ds = GANDataset.from_split(cfg, cfg["VAL_SPLIT"], cfg.get("ENCODER_FEATS_VAL"), device, resident=True)
         log(f"Validation set size: {len(val_ds)} (evaluated every {eval_every} epoch(s))")
-        evaluator = Evaluator(cfg, ed_cfg, device, B)
+        evaluator = evaluator or Evaluator(cfg, ed_cfg, device, B)
     log("Starting WGAN-GP Training with Emotion Guidance...")
+
+    def val_scalars(rep):
+        return {"W_dist": rep["critic"]["w_dist"], "ED_Acc_Fake": rep["ed_fake"]["accuracy"], "ED_CE_Fake": rep["ed_fake"]["ce"],
+                "ED_Acc_Real": rep["ed_real"]["accuracy"] if rep["ed_real"] else None}
+
+    def averaged():
+        """The evaluator holding the averaged weights with their own BatchNorm statistics (over the training split)."""
+        from .eval_engine import recalibrate_bn
+        evaluator.copy_ema_from(eng)
+        recalibrate_bn(evaluator, ds, cfg.get("SEED", 42))
+        return evaluator
 
     def epoch_batches():
         """Per batch of this rank's share of the epoch: stage it (or, for a bound resident split, nothing: the step's first
@@ -284,19 +377,28 @@ def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: 
             writer.add_scalar("Loss/Critic", s[0] / steps, epoch)
             writer.add_scalar("Loss/Generator_Adv", s[1] / g_steps, epoch)
             writer.add_scalar("Loss/Generator_Emo", s[2] / g_steps, epoch)
-            if evaluator is not None and epoch % eval_every == 0:
+            if val_ds is not None and epoch % eval_every == 0:
                 evaluator.copy_from(eng)        # device-to-device, behind this stream's work; the engine is only read
                 rep = evaluator.evaluate(val_ds, cfg.get("SEED", 42))
-                val = {"Val/W_dist": rep["critic"]["w_dist"], "Val/ED_Acc_Fake": rep["ed_fake"]["accuracy"],
-                       "Val/ED_CE_Fake": rep["ed_fake"]["ce"],
-                       "Val/ED_Acc_Real": rep["ed_real"]["accuracy"] if rep["ed_real"] else None}
+                val = {"Val/" + t: v for t, v in val_scalars(rep).items()}
                 for tag, v in val.items():
                     if v is not None:
                         writer.add_scalar(tag, v, epoch)
                 log(f"Epoch {epoch}/{cfg['EPOCHS']} | validation ({rep['n']} rows) | " +
                     " | ".join(f"{t[4:]}: {v:.4f}" for t, v in val.items() if v is not None))
+                if ema_on:      # the same pass, seed and critic under the averaged generator: a paired second line
+                    rep = averaged().evaluate(val_ds, cfg.get("SEED", 42))
+                    val = {"ValEMA/" + t: v for t, v in val_scalars(rep).items()}
+                    for tag, v in val.items():
+                        if v is not None:
+                            writer.add_scalar(tag, v, epoch)
+                    log(f"Epoch {epoch}/{cfg['EPOCHS']} | validation, averaged weights | " +
+                        " | ".join(f"{t[7:]}: {v:.4f}" for t, v in val.items() if v is not None))
             if epoch % cfg.get("SAVE_FREQ", 5) == 0:
-                save_checkpoint(eng, os.path.join(cfg["CHECKPOINT_DIR"], f"gan_epoch{epoch:04d}.pth"), epoch, full=True)
+                save_checkpoint(eng, os.path.join(cfg["CHECKPOINT_DIR"], f"gan_epoch{epoch:04d}.pth"), epoch, full=True,
+                                ema=ema_block(eng, averaged()) if ema_on else None)
+        if rank == 0 and ema_on:
+            save_ema_final(ema_block(eng, averaged()), os.path.join(cfg["CHECKPOINT_DIR"], "gan_final_ema.pth"))
     if rank == 0:
         save_checkpoint(eng, os.path.join(cfg["CHECKPOINT_DIR"], "gan_final.pth"), full=False)
         writer.close()

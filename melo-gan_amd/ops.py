@@ -2222,6 +2222,22 @@ def adam_flat(p, g, m, v, state, lr, beta1, beta2, eps=1e-8, weight_decay=0.0, g
                                   n_table, _stream()), "mg_adam_flat")
 
 
+def ema_flat(p, shadow, n: int, decay: float, ramp: bool, adam_state, step_offset: float = 0.0):
+    """shadow[:n] += (1 - d) * (p[:n] - shadow[:n]) in fp64 (mg_ema_flat; gan/ema.py restates it): p fp32 with at least n
+    elements, shadow fp64 with at least n, adam_state the optimiser's (4,) fp64 state, already advanced by the update this
+    launch follows.  d = decay, or under `ramp` min(decay, (1 + t) / (10 + t)) with t = adam_state[0] - 1 - step_offset."""
+    _chk(p, "p")
+    _chk(shadow, "shadow", dtype=torch.float64)
+    _chk(adam_state, "adam_state", (4,), torch.float64)
+    if p.dim() != 1 or shadow.dim() != 1 or not 1 <= int(n) <= min(p.numel(), shadow.numel()):
+        raise ValueError("ema_flat: flat p and shadow holding at least n >= 1 elements expected")
+    if not 0.0 <= float(decay) < 1.0:
+        raise ValueError(f"ema_flat: decay = {decay}: must be in [0, 1)")
+    L.check(L.load().mg_ema_flat(_p(p), _p(shadow), int(n), float(decay), 1 if ramp else 0, _p(adam_state), float(step_offset),
+                                 _stream()), "mg_ema_flat")
+    return shadow
+
+
 def grad_norm_clip(g, max_norm, out):
     _chk(g, "g")
     _chk(out, "out")
