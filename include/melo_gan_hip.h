@@ -569,6 +569,57 @@ int mg_gen_inputs(const int32_t* emotion, const int32_t* sample, int rows, float
 int mg_emotion_score(const float* logits, int rows, int n_classes, const int32_t* target, float* p_target, int32_t* pred,
                      double* acc, mg_stream_t stream);
 
+/* ---- rendering note lists to audio (csrc/render.hip; melo_gan_amd.audio, melo_gan_amd.render, generate --wav) ----
+ * The reference stops at the .mid file; hearing one takes a synthesiser from outside.  mg_render_notes is an additive
+ * synthesiser with an integer phase accumulator: F files in ONE launch, a lane per output sample.
+ *   per note (device):  onset, release  int32 sample indices, file-local, release > onset
+ *                       inc             uint32, the fundamental's phase increment per sample in units of 2^-32 turns
+ *                       gain            fp32
+ *   per file (device):  note_ptr[F+1]   int64 CSR offsets into the note arrays; WITHIN A FILE THE NOTES ARE SORTED BY ONSET
+ *                                       (ascending; the kernel bounds its candidate search by it and does not check)
+ *                       pcm_ptr[F+1]    int64 offsets of the file's samples in pcm; every element of [pcm_ptr[f], pcm_ptr[f+1])
+ *                                       is written, 0 where nothing sounds and for a file without notes
+ *                       n_begin[F]      int32 file-local index of the first sample rendered: 0 = the file from its start,
+ *                                       otherwise a window  pcm[pcm_ptr[f] + j] = y[n_begin[f] + j]
+ *                       max_len[F]      int32 >= release - onset + release_len of every note of the file
+ *   host:               max_samples     >= pcm_ptr[f+1] - pcm_ptr[f] of every file (sizes the grid), 1 .. 2^31 - 1
+ *                       voice           the instrument, read before the call returns (see mg_voice)
+ *                       peak            NULL, or F floats: mg_pcm_peak of what this launch wrote, in the same launch
+ * For the file-local sample n a note is live while onset <= n < release + release_len; with k = n - onset, kr = max(n - release, 0)
+ *   y[n] = sum over live notes i in array order, over partials h ascending, skipped when (uint64)mult[h] * inc[i] >= 2^31 (Nyquist)
+ *            gain[i] * min((k + 1) / attack, 1) * exp(-kr / (fs * release_tau)) * weight[h] * exp(-decay[h] * k / fs) * sin(2 pi x)
+ *   x    = ((((uint32)(mult[h] * inc[i])) * (uint32)k mod 2^32) >> 8) * 2^-24          (exact in fp32)
+ * The terms are evaluated in fp32 (one expf for both envelopes, sinpif on the exact x) and added in fp32 in exactly that order by
+ * the lane that owns n, every operation rounded on its own.  A sample is therefore a function of its file's notes and of n alone:
+ * windows, batches, batch positions, eager launches and graph replays agree bit for bit.  Against the fp64 evaluation each
+ * sample lies within (32 + 2 A + M) 2^-24 S (S = sum of |amplitude| of its M terms, A = its largest envelope exponent):
+ * tests/render_ref.py, tests/test_render_gpu.py.
+ * mg_pcm_peak: peak[f] = max |pcm| over the file, taken as the integer maximum of the absolute values' bit patterns: exact, and
+ *   independent of the order (0 for an empty file; a NaN sample yields a NaN peak).
+ * mg_pcm_quantise: q = (int16) clamp(rint(pcm * s_f), -32767, 32767), s_f = (target * 32767.0f) / peak[f] in fp32, IEEE divide,
+ *   s_f = 0 where peak[f] == 0; q is laid out as pcm.
+ * All three are capturable (the peak is zeroed by a memset node in front of the kernel), use no floating-point atomics and return
+ * -1 before any launch for: a null pointer (peak of mg_render_notes excepted); F outside 1..65535; max_samples < 1; n_partials
+ * outside 1..16; attack < 1; release_len < 0; fs, release_tau or a used decay[h] not finite or not positive (decay may be 0); a used
+ * weight[h] not finite; target outside (0, 1]. */
+#define MG_VOICE_MAX_PARTIALS 16
+typedef struct mg_voice {
+    int n_partials;                           /* 1..16; entries past it are ignored */
+    uint32_t mult[MG_VOICE_MAX_PARTIALS];     /* partial h sounds at mult[h] times the fundamental */
+    float weight[MG_VOICE_MAX_PARTIALS];
+    float decay[MG_VOICE_MAX_PARTIALS];       /* 1/s, from the onset on */
+    int attack;                               /* samples of the linear ramp, >= 1 */
+    float release_tau;                        /* s, time constant after the release */
+    int release_len;                          /* samples a note sounds after its release, >= 0 */
+    float fs;                                 /* sample rate, Hz */
+} mg_voice;
+int mg_render_notes(const int32_t* onset, const int32_t* release, const uint32_t* inc, const float* gain, const int64_t* note_ptr,
+                    const int64_t* pcm_ptr, const int32_t* n_begin, const int32_t* max_len, int F, long max_samples,
+                    const mg_voice* voice, float* pcm, float* peak /* may be NULL */, mg_stream_t stream);
+int mg_pcm_peak(const float* pcm, const int64_t* pcm_ptr, int F, long max_samples, float* peak, mg_stream_t stream);
+int mg_pcm_quantise(const float* pcm, const int64_t* pcm_ptr, const float* peak, int F, long max_samples, float target, int16_t* q,
+                    mg_stream_t stream);
+
 /* ---- held-out evaluation of a trained GAN (melo_gan_amd.gan.evaluate) ----
  * The reference judges a generator with host scripts over files: src/gan/analyze_midi.py:28-45 (mean / min / max of pitch,
  * mean velocity of written .mid files, per emotion), src/gan/diagnose.py:53-80 (per-column range, mean and standard deviation

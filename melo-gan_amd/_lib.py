@@ -85,6 +85,13 @@ MAX_WQ_ENTRIES = 8
 
 MLP_MAX_HIDDEN, MLP_MAX_DIM, MLP_MAX_CLASSES = 4, 512, 32
 
+VOICE_MAX_PARTIALS = 16
+
+
+class Voice(C.Structure):
+    _fields_ = [("n_partials", i32), ("mult", C.c_uint32 * VOICE_MAX_PARTIALS), ("weight", f32 * VOICE_MAX_PARTIALS),
+                ("decay", f32 * VOICE_MAX_PARTIALS), ("attack", i32), ("release_tau", f32), ("release_len", i32), ("fs", f32)]
+
 
 class MlpCls(C.Structure):
     _fields_ = [("n_hidden", i32), ("in_dim", i32), ("width", i32 * MLP_MAX_HIDDEN), ("n_classes", i32),
@@ -160,6 +167,9 @@ SIGNATURES = {
     "mg_rng_fill": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, f32, C.c_uint64, vp, vp, vp, f32, f32, vp, i32, i32, vp, i64, vp, vp]),
     "mg_gen_inputs": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, f32, vp, i32, C.c_uint64, vp]),
     "mg_emotion_score": (i32, [vp, i32, i32, vp, vp, vp, vp, vp]),
+    "mg_render_notes": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, C.POINTER(Voice), vp, vp, vp]),
+    "mg_pcm_peak": (i32, [vp, vp, i32, i64, vp, vp]),
+    "mg_pcm_quantise": (i32, [vp, vp, vp, i32, i64, f32, vp, vp]),
     "mg_eval_acc_words": (i64, [i32, i32]),
     "mg_eval_acc_workspace_bytes": (sz, [i32, i32, i32]),
     "mg_eval_acc_reset": (i32, [vp, i32, i32, vp]),

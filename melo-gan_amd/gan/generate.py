@@ -7,11 +7,17 @@ hold; its only generation code left is the Flask route, app.py:53-65,92-119):
         [--ckpt <CHECKPOINT_DIR>/gan_final.pth] [--emotion happy|sad|angry|calm|all] \
         [--samples <N_SAMPLES_PER_EMOTION>] [--out <SAMPLE_DIR>] [--seed <SEED>] [--batch 64] \
         [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--ema]
+        [--wav [--wav-fs 44100] [--voice piano|organ|sine]]
 
 --ema samples from the averaged generator in the `ema` block of a full gan_epochNNNN.pth (trained with EMA_DECAY > 0;
 gan_final_ema.pth is an ordinary checkpoint and needs no flag); summary.json records "weights": "ema" | "raw".
 writes <out>/test_<emotion>_<k>.mid for k = 1..N (the reference's file names) with app.py's scale and tempo per emotion,
 and <out>/summary.json with the frozen emotion classifier's verdict on every sample when one is given.
+
+--wav also writes test_<emotion>_<k>.wav beside every .mid: the note list that goes into the .mid (midi.notes_from_roll with the
+emotion's scale and tempo), rendered on the device by melo_gan_amd.audio.Renderer at --wav-fs Hz with --voice, peak -1 dB full
+scale.  Each files[] entry of summary.json then gains "wav", "seconds" and "truncated", and the top level a "wav" block {fs,
+voice, peak_db}; without --wav the summary has neither.
 
 The inputs follow app.py: noise ~ N(0,1), numeric = the emotion's base vector + 0.15 * N(0,1), latent = 0.  mg_gen_inputs
 draws them on the device from a Philox counter per (emotion, sample), so a sample does not depend on what else is
@@ -43,6 +49,8 @@ JITTER = 0.15
 # app.py:109-110: (scale, bpm) per emotion; root key C, piano
 STYLE = {"happy": ("major", 140), "sad": ("minor", 70), "angry": ("minor", 160), "calm": ("major", 90)}
 DEFAULT_BATCH = 64
+WAV_PEAK_DB = -1.0
+WAV_MAX_SECONDS = 3600.0      # where --wav would cut a sample: 512 steps of at most 4 beats at 60 bpm stay below it
 
 
 class GenerateError(ValueError):
@@ -210,6 +218,9 @@ def parse_args(argv=None):
     ap.add_argument("--ed_config", type=str, default=None, help="ED config of the classifier that scores the samples")
     ap.add_argument("--ed_ckpt", type=str, default=None, help="ED checkpoint (ed_best.pth)")
     ap.add_argument("--ema", action="store_true", help="sample from the averaged weights in a full checkpoint's 'ema' block")
+    ap.add_argument("--wav", action="store_true", help="also render every sample to test_<emotion>_<k>.wav")
+    ap.add_argument("--wav-fs", type=int, default=44100, help="sample rate of the .wav files in Hz")
+    ap.add_argument("--voice", type=str, default="piano", help="the renderer's voice: piano, organ or sine")
     return ap.parse_args(argv)
 
 
@@ -226,6 +237,7 @@ class Plan:
     seed: int
     batch: int
     ema: bool = False
+    wav: Optional[dict] = None          # --wav: {"fs", "voice", "peak_db"}
 
 
 def _read_config(path: str, what: str, err=GenerateError) -> dict:
@@ -278,11 +290,35 @@ def plan(args) -> Plan:
             raise GenerateError(f"ED checkpoint {args.ed_ckpt} does not exist")
     out = args.out or cfg.get("SAMPLE_DIR", "experiments/gan/samples")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
-    return Plan(cfg, ed_cfg, ckpt_path, ckpt, args.ed_ckpt, emotions, samples, out, seed, args.batch, ema)
+    wav = None
+    if getattr(args, "wav", False):
+        from .. import audio
+        wav = {"fs": args.wav_fs, "voice": args.voice, "peak_db": WAV_PEAK_DB}
+        try:
+            audio.check_settings(wav["fs"], wav["voice"], wav["peak_db"], WAV_MAX_SECONDS)
+        except audio.AudioError as e:
+            raise GenerateError(f"--wav: {e}") from e
+    return Plan(cfg, ed_cfg, ckpt_path, ckpt, args.ed_ckpt, emotions, samples, out, seed, args.batch, ema, wav)
 
 
 def midi_name(emotion: str, k: int) -> str:
     return f"test_{emotion}_{k}.mid"
+
+
+def wav_name(emotion: str, k: int) -> str:
+    return f"test_{emotion}_{k}.wav"
+
+
+def write_wavs(p: Plan, res: Samples, files: List[dict]) -> None:
+    """--wav: every sample's note list -- the one save_piano_roll_to_midi writes -- through one Renderer; files[i] gains wav,
+    seconds and truncated."""
+    from .. import audio, midi
+    lists = [midi.notes_from_roll(res.notes[i], bpm=STYLE[e][1], scale=STYLE[e][0], root_key=0)[0] for i, e in enumerate(res.emotion)]
+    r = audio.Renderer("cuda", p.wav["fs"], p.wav["voice"], p.wav["peak_db"], WAV_MAX_SECONDS)
+    for f, pcm, rep in zip(files, r.render(lists), r.report):
+        f["wav"] = wav_name(f["emotion"], f["k"])
+        f["seconds"], f["truncated"] = rep.seconds, rep.truncated
+        audio.write_wav(os.path.join(p.out, f["wav"]), pcm, p.wav["fs"])
 
 
 def write_outputs(p: Plan, res: Samples) -> dict:
@@ -298,6 +334,9 @@ def write_outputs(p: Plan, res: Samples) -> dict:
                       "ed_p_target": None if res.p_target is None else float(res.p_target[i])})
     summary = {"checkpoint": p.ckpt_path, "weights": "ema" if p.ema else "raw", "ed_checkpoint": p.ed_ckpt, "seed": p.seed, "samples": p.samples,
                "batch": p.batch, "emotions": p.emotions, "per_emotion": res.summary, "files": files}
+    if p.wav is not None:
+        write_wavs(p, res, files)
+        summary["wav"] = dict(p.wav)
     with open(os.path.join(p.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     return summary
@@ -322,7 +361,7 @@ def main(argv=None) -> int:
     print(f"{'emotion':<8} {'n':>4} {'ed_accuracy':>12} {'ed_mean_p_target':>17}")
     for e, s in res.summary.items():
         print(f"{e:<8} {s['n']:>4} {fmt(s['ed_accuracy'], '.3f'):>12} {fmt(s['ed_mean_p_target'], '.4f'):>17}")
-    print(f"wrote {len(res.emotion)} MIDI files and summary.json to {p.out}")
+    print(f"wrote {len(res.emotion)} MIDI files{' and WAV files' if p.wav is not None else ''} and summary.json to {p.out}")
     return 0
 
 

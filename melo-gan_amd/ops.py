@@ -1665,6 +1665,71 @@ def emotion_score(logits, target, p_target, pred, acc):
             "mg_emotion_score")
 
 
+def voice_struct(mult, weight, decay, attack: int, release_tau: float, release_len: int, fs: float) -> L.Voice:
+    """mg_voice from a partial table (equally long sequences of multipliers, weights and decay rates in 1/s) and the envelope:
+    attack and release_len in samples, release_tau in seconds.  Only the table's length is checked here; the values are
+    mg_render_notes' to refuse."""
+    n = len(mult)
+    if len(weight) != n or len(decay) != n:
+        raise ValueError(f"voice: {n} multipliers, {len(weight)} weights, {len(decay)} decay rates")
+    if n > L.VOICE_MAX_PARTIALS:
+        raise ValueError(f"voice: {n} partials, at most {L.VOICE_MAX_PARTIALS}")
+    v = L.Voice()
+    v.n_partials, v.attack, v.release_tau, v.release_len, v.fs = n, int(attack), float(release_tau), int(release_len), float(fs)
+    for h in range(n):
+        v.mult[h], v.weight[h], v.decay[h] = int(mult[h]), float(weight[h]), float(decay[h])
+    return v
+
+
+def _pcm_files(who, pcm_ptr, n_elems, max_samples):
+    _chk(pcm_ptr, "pcm_ptr", dtype=torch.int64)
+    F = pcm_ptr.numel() - 1
+    if pcm_ptr.dim() != 1 or F < 1:
+        raise ValueError(f"{who}: pcm_ptr holds F + 1 >= 2 offsets")
+    if not 1 <= int(max_samples) <= max(1, n_elems):
+        raise ValueError(f"{who}: max_samples = {max_samples}: the longest file's length, within the {n_elems} samples of pcm")
+    return F
+
+
+def render_notes(onset, release, inc, gain, note_ptr, pcm_ptr, n_begin, max_len, max_samples: int, voice: L.Voice, pcm, peak=None):
+    """mg_render_notes: the files' notes (CSR note_ptr into onset / release / inc int32 and gain fp32, inc holding the uint32
+    phase increment's bits; sorted by onset within a file) rendered into pcm[pcm_ptr[f] : pcm_ptr[f + 1]] from the file-local
+    sample n_begin[f] on.  max_samples: the longest file's sample count.  The offsets live on the device and are not read
+    here: they must lie inside the arrays.  peak (F,) fp32: max |pcm| per file from the same launch."""
+    _chk(onset, "onset", dtype=torch.int32)
+    N = onset.numel()
+    _chk(release, "release", (N,), torch.int32)
+    _chk(inc, "inc", (N,), torch.int32)
+    _chk(gain, "gain", (N,))
+    _chk(pcm, "pcm")
+    F = _pcm_files("render_notes", pcm_ptr, pcm.numel(), max_samples)
+    _chk(note_ptr, "note_ptr", (F + 1,), torch.int64)
+    _chk(n_begin, "n_begin", (F,), torch.int32)
+    _chk(max_len, "max_len", (F,), torch.int32)
+    if peak is not None:
+        _chk(peak, "peak", (F,))
+    L.check(L.load().mg_render_notes(_p(onset), _p(release), _p(inc), _p(gain), _p(note_ptr), _p(pcm_ptr), _p(n_begin), _p(max_len), F,
+                                     int(max_samples), C.byref(voice), _p(pcm), _p(peak), _stream()), "mg_render_notes")
+
+
+def pcm_peak(pcm, pcm_ptr, max_samples: int, peak):
+    """peak[f] = max |pcm[pcm_ptr[f] : pcm_ptr[f + 1]]| (mg_pcm_peak), exact."""
+    _chk(pcm, "pcm")
+    F = _pcm_files("pcm_peak", pcm_ptr, pcm.numel(), max_samples)
+    _chk(peak, "peak", (F,))
+    L.check(L.load().mg_pcm_peak(_p(pcm), _p(pcm_ptr), F, int(max_samples), _p(peak), _stream()), "mg_pcm_peak")
+
+
+def pcm_quantise(pcm, pcm_ptr, peak, max_samples: int, target: float, q):
+    """q = int16 clamp(rint(pcm * (target * 32767 / peak[f])), +-32767) (mg_pcm_quantise); q int16, laid out as pcm."""
+    _chk(pcm, "pcm")
+    F = _pcm_files("pcm_quantise", pcm_ptr, pcm.numel(), max_samples)
+    _chk(peak, "peak", (F,))
+    _chk(q, "q", tuple(pcm.shape), torch.int16)
+    L.check(L.load().mg_pcm_quantise(_p(pcm), _p(pcm_ptr), _p(peak), F, int(max_samples), float(target), _p(q), _stream()),
+            "mg_pcm_quantise")
+
+
 _WORD_ITEM = {torch.int64: 8, torch.float64: 8, torch.float32: 4, torch.int32: 4}       # bytes; 4-byte items pack two to a word
 
 
