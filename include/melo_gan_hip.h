@@ -569,6 +569,43 @@ int mg_gen_inputs(const int32_t* emotion, const int32_t* sample, int rows, float
 int mg_emotion_score(const float* logits, int rows, int n_classes, const int32_t* target, float* p_target, int32_t* pred,
                      double* acc, mg_stream_t stream);
 
+/* ---- blends and transitions between emotions (melo_gan_amd.gan.morph; csrc/small_kernels.hip, csrc/morph_metrics.hip) ----
+ * mg_gen_inputs_mix: mg_gen_inputs' three outputs for rows that mix.  Row r carries weights[r, 0:n_emotions] (fp32), two keys
+ *   key_a[r] = (emotion, sample) and key_b[r] = (emotion, sample) (int32 pairs) and t[r] (fp32 in [0, 1]):
+ *     base[c]  = sum_e weights[r, e] * table[e, c]    fp32, class order, every product and sum rounded on its own: a
+ *                                                     one-hot row gives table[e] exactly
+ *     draw(k)  = what mg_gen_inputs draws for the key k = (emotion, sample): the same Philox counter words, key and
+ *                Box-Muller; (za, va) = the noise and the jitter normals of key_a, (zb, vb) those of key_b
+ *     t == 0 or key_a == key_b:  noise = za, numeric = base + jitter * va   (key_b is not drawn)
+ *     t == 1:                    noise = zb, numeric = base + jitter * vb
+ *     otherwise, spherically:    theta = acos(clamp(za.zb / (|za| |zb|), -1, 1)),  ca = sin((1 - t) theta) / sin(theta),
+ *                                cb = sin(t theta) / sin(theta)   (sin(theta) < 2^-20 or not a number: ca = 1 - t, cb = t),
+ *                                all in fp64 from fp64 sums of the widened draws (per-lane partials in element order, a fixed
+ *                                butterfly over the 64 lanes), ca and cb rounded to fp32;
+ *                                noise = ca * za + cb * zb,  numeric = base + jitter * (ca * va + cb * vb), the mixes with
+ *                                every product and sum rounded on its own.  The jitter takes the noise's coefficients.
+ *   `base + jitter * v` is ONE fused multiply-add, as mg_gen_inputs evaluates it: an exact row with one-hot weights equals
+ *   mg_gen_inputs' row for that key bit for bit.  latent = 0.  A row whose key_a emotion lies outside [0, n_emotions) is
+ *   padding: zeros (its weights are not read).  One 64-lane block per row, no atomics; a row depends on its own descriptors
+ *   and the seed alone.  n_emotions 1..32. */
+int mg_gen_inputs_mix(const float* weights, const int32_t* key_a, const int32_t* key_b, const float* t, int rows, float* noise,
+                      int noise_dim, float* numeric, int num_dim, const float* table, int n_emotions, float jitter, float* latent,
+                      int latent_dim, uint64_t seed, mg_stream_t stream);
+/* Reductions over paths: x and logits hold P paths of S1 consecutive rows each (path-major).
+ * mg_path_d2: out[p, s] (fp64, (P, S1)) = sum_j (x[p, s + 1, j] - x[p, s, j])^2 for s < S1 - 1, and out[p, S1 - 1] the same sum
+ *   between step S1 - 1 and step 0 (the endpoint distance; 0 when S1 = 1).  x (P * S1, D) fp32; every element is widened to
+ *   fp64 before the subtraction; identical rows give exactly 0.  One 256-lane workgroup per (p, s); 16-byte loads when
+ *   D % 4 == 0 and x is 16-byte aligned, element-wise otherwise; per-lane sums in element order, a fixed butterfly over the
+ *   wave, a fixed tree over the four waves.  D <= 2^30.
+ * mg_path_probs: probs (P * S1, K) fp64 = the softmax of the fp32 logits evaluated in fp64 with the row maximum (the lowest
+ *   index on ties) taken out and its own term not computed (mg_cls_eval_acc's rule); then acc (G, S1, K + 1) fp64:
+ *   acc[g, s, k] = sum of probs[p, s, k] over the paths with group[p] == g, p = 0 .. P-1 in order, one lane per word;
+ *   acc[g, s, K] = the number of those paths.  group int32 (P,); a group outside [0, G) is skipped.  K 2..32.
+ * Both: no atomics of any kind; eager runs, reruns and graph replays leave identical bits. */
+int mg_path_d2(const float* x, int P, int S1, int D, double* out, mg_stream_t stream);
+int mg_path_probs(const float* logits, const int32_t* group, int P, int S1, int n_classes, int n_groups, double* probs,
+                  double* acc, mg_stream_t stream);
+
 /* ---- rendering note lists to audio (csrc/render.hip; melo_gan_amd.audio, melo_gan_amd.render, generate --wav) ----
  * The reference stops at the .mid file; hearing one takes a synthesiser from outside.  mg_render_notes is an additive
  * synthesiser with an integer phase accumulator: F files in ONE launch, a lane per output sample.

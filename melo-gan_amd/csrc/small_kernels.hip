@@ -1008,6 +1008,86 @@ __global__ __launch_bounds__(64) void gen_inputs_kernel(const int* __restrict__ 
     for (int j = threadIdx.x; j < latent_dim; j += blockDim.x) latent[(long)r * latent_dim + j] = 0.f;
 }
 
+// ---------------- mixed rows: blends and transitions between emotions (gan/morph.py) ----------------
+// gen_inputs_kernel's draw for the key (e, k): element block qb of input `which` (0 noise, 1 jitter).
+__device__ __forceinline__ void gen_draw(int qb, unsigned which, int e, int k, unsigned long long seed, float (&v)[4]) {
+    unsigned c[4] = {(unsigned)qb, GEN_TAG | which, (unsigned)e, (unsigned)k};
+    philox4(c, (unsigned)seed, (unsigned)(seed >> 32));
+    box_muller4(c, v);
+}
+
+// gen_inputs_kernel's three outputs for rows that mix (include/melo_gan_hip.h, mg_gen_inputs_mix), one block per row.  Row r
+// carries weights[r, :] over the table, two keys (emotion, sample) and t: its base vector is sum_e w_e table[e] (class order,
+// every product and sum rounded on its own, so a one-hot row gives the table's row exactly), its noise and jitter normals
+// are those of key_a (t == 0 or key_a == key_b: key_b is not drawn), those of key_b (t == 1), or the spherical
+// interpolation of the two noise vectors, whose two coefficients also mix the jitter normals.  The angle is computed in
+// fp64: per-lane partial sums in element order, a fixed butterfly over the 64 lanes (every lane ends with the same bits).
+// numeric = fma(jitter, v, base): what gen_inputs_kernel's `base + jitter * v` compiles to, so that an exact row equals
+// that kernel's bit for bit (tests/test_morph_gpu.py pins the two to each other).
+__global__ __launch_bounds__(64) void gen_inputs_mix_kernel(const float* __restrict__ weights, const int* __restrict__ key_a,
+                                                            const int* __restrict__ key_b, const float* __restrict__ t,
+                                                            float* __restrict__ noise, int noise_dim, float* __restrict__ numeric,
+                                                            int num_dim, const float* __restrict__ table, int n_emotions,
+                                                            float jitter, float* __restrict__ latent, int latent_dim,
+                                                            unsigned long long seed) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int ea = key_a[2 * r], ka = key_a[2 * r + 1], eb = key_b[2 * r], kb = key_b[2 * r + 1];
+    const float tr = t[r];
+    const bool pad = ea < 0 || ea >= n_emotions;
+    const bool only_a = pad || tr == 0.f || (ea == eb && ka == kb), only_b = !only_a && tr == 1.f;
+    const int nb_noise = (noise_dim + 3) >> 2, nb_num = (num_dim + 3) >> 2;
+    float ca = 1.f, cb = 0.f;
+    if (!only_a && !only_b) {
+        double dot = 0.0, na = 0.0, nb = 0.0;
+        for (int q = lane; q < nb_noise; q += 64) {
+            float za[4], zb[4];
+            gen_draw(q, 0u, ea, ka, seed, za);
+            gen_draw(q, 0u, eb, kb, seed, zb);
+            for (int j = 0; j < 4; ++j)
+                if (4 * q + j < noise_dim) {
+                    const double a = (double)za[j], b = (double)zb[j];
+                    dot = dot + a * b;
+                    na = na + a * a;
+                    nb = nb + b * b;
+                }
+        }
+        for (int m = 1; m < 64; m <<= 1) {
+            dot = dot + __shfl_xor(dot, m, 64);
+            na = na + __shfl_xor(na, m, 64);
+            nb = nb + __shfl_xor(nb, m, 64);
+        }
+        const double theta = acos(fmin(fmax(dot / (sqrt(na) * sqrt(nb)), -1.0), 1.0));     // a NaN quotient: theta = pi
+        const double s = sin(theta), td = (double)tr;
+        double da = 1.0 - td, db = td;              // (anti)parallel vectors: the chord
+        if (s >= 0x1p-20) {
+            da = sin((1.0 - td) * theta) / s;
+            db = sin(td * theta) / s;
+        }
+        ca = (float)da;
+        cb = (float)db;
+    }
+    for (int q = lane; q < nb_noise + nb_num; q += 64) {
+        const unsigned which = q < nb_noise ? 0u : 1u;
+        const int qb = which ? q - nb_noise : q;
+        float va[4] = {0.f, 0.f, 0.f, 0.f}, vb[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!only_b) gen_draw(qb, which, ea, ka, seed, va);
+        if (!only_a) gen_draw(qb, which, eb, kb, seed, vb);
+        for (int j = 0; j < 4; ++j) {
+            const int col = 4 * qb + j;
+            const float v = only_a ? va[j] : only_b ? vb[j] : ca * va[j] + cb * vb[j];
+            if (which == 0 && col < noise_dim) noise[(long)r * noise_dim + col] = pad ? 0.f : v;
+            if (which == 1 && col < num_dim) {
+                float base = 0.f;
+                if (!pad)
+                    for (int e = 0; e < n_emotions; ++e) base = base + weights[(long)r * n_emotions + e] * table[(long)e * num_dim + col];
+                numeric[(long)r * num_dim + col] = pad ? 0.f : __builtin_fmaf(jitter, v, base);
+            }
+        }
+    }
+    for (int j = lane; j < latent_dim; j += 64) latent[(long)r * latent_dim + j] = 0.f;
+}
+
 // The classifier's verdict on a chunk (one block: a fixed summation order, so reruns and replays add bit-identical sums).
 // Per row: p_target = softmax(logits)[target] in fp32 with the row maximum subtracted first (torch.softmax), pred = the
 // first index of the maximum (torch.argmax; NaN counts as the maximum).  Per class c: acc[3c .. 3c+2] += {rows with target
@@ -1859,6 +1939,20 @@ int mg_gen_inputs(const int32_t* emotion, const int32_t* sample, int rows, float
     hipLaunchKernelGGL(gen_inputs_kernel, dim3((unsigned)rows), dim3(64), 0, ST, (const int*)emotion, (const int*)sample, noise,
                        noise_dim, numeric, num_dim, table, n_emotions, jitter, latent, latent_dim, (unsigned long long)seed);
     MG_CHECK_LAUNCH("gen_inputs");
+    return MG_OK;
+}
+
+int mg_gen_inputs_mix(const float* weights, const int32_t* key_a, const int32_t* key_b, const float* t, int rows, float* noise,
+                      int noise_dim, float* numeric, int num_dim, const float* table, int n_emotions, float jitter, float* latent,
+                      int latent_dim, uint64_t seed, mg_stream_t stream) {
+    MG_CHECK_ARG(weights && key_a && key_b && t && noise && numeric && table,
+                 "mg_gen_inputs_mix: null weights / key_a / key_b / t / noise / numeric / table");
+    MG_CHECK_ARG(rows > 0 && noise_dim > 0 && num_dim > 0, "mg_gen_inputs_mix: rows, noise_dim and num_dim must be positive");
+    MG_CHECK_ARG(n_emotions >= 1 && n_emotions <= 32, "mg_gen_inputs_mix: n_emotions = %d: 1..32", n_emotions);
+    MG_CHECK_ARG(latent_dim >= 0 && (latent || latent_dim == 0), "mg_gen_inputs_mix: latent is needed unless latent_dim is 0");
+    hipLaunchKernelGGL(gen_inputs_mix_kernel, dim3((unsigned)rows), dim3(64), 0, ST, weights, (const int*)key_a, (const int*)key_b, t,
+                       noise, noise_dim, numeric, num_dim, table, n_emotions, jitter, latent, latent_dim, (unsigned long long)seed);
+    MG_CHECK_LAUNCH("gen_inputs_mix");
     return MG_OK;
 }
 

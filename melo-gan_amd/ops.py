@@ -1665,6 +1665,75 @@ def emotion_score(logits, target, p_target, pred, acc):
             "mg_emotion_score")
 
 
+PATH_MAX_CLASSES = 32
+
+
+def gen_inputs_mix(weights, key_a, key_b, t, noise, numeric, table, jitter, latent, seed):
+    """The generator's inputs for one chunk of mixed rows (mg_gen_inputs_mix): row r has weights[r] over the table's rows
+    (rows, n_emotions), the keys key_a[r], key_b[r] = (emotion, sample) (int32 (rows, 2); key_a's emotion -1 = a padding row,
+    written with zeros) and t (rows,) in [0, 1]; the outputs are gen_inputs'."""
+    _chk(table, "table")
+    if table.dim() != 2 or not 1 <= table.shape[0] <= 32:
+        raise ValueError("gen_inputs_mix: table (n_emotions in 1..32, D) expected")
+    _chk(weights, "weights")
+    if weights.dim() != 2 or weights.shape[0] < 1 or weights.shape[1] != table.shape[0]:
+        raise ValueError(f"gen_inputs_mix: weights (rows >= 1, {table.shape[0]}) expected, got {tuple(weights.shape)}")
+    rows = weights.shape[0]
+    _chk(key_a, "key_a", (rows, 2), torch.int32)
+    _chk(key_b, "key_b", (rows, 2), torch.int32)
+    _chk(t, "t", (rows,))
+    _chk(noise, "noise")
+    if noise.dim() != 2 or noise.shape[0] != rows or noise.shape[1] < 1 or table.shape[1] < 1:
+        raise ValueError("gen_inputs_mix: noise (rows, noise_dim >= 1) and a table of D >= 1 columns expected")
+    _chk(numeric, "numeric", (rows, table.shape[1]))
+    latent_dim = 0
+    if latent is not None:
+        _chk(latent, "latent")
+        if latent.dim() != 2 or latent.shape[0] != rows:
+            raise ValueError("gen_inputs_mix: latent (rows, latent_dim) expected")
+        latent_dim = latent.shape[1]
+    L.check(L.load().mg_gen_inputs_mix(_p(weights), _p(key_a), _p(key_b), _p(t), rows, _p(noise), noise.shape[1], _p(numeric),
+                                       table.shape[1], _p(table), table.shape[0], float(jitter), _p(latent), latent_dim,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "mg_gen_inputs_mix")
+
+
+def path_d2(x, P: int, S1: int, out=None):
+    """The squared step lengths of P paths of S1 consecutive rows of x (P * S1, D) fp32 (mg_path_d2): out (P, S1) fp64, entry
+    S1 - 1 of a path = its squared endpoint distance."""
+    _chk(x, "x")
+    P, S1 = int(P), int(S1)
+    if x.dim() != 2 or P < 1 or S1 < 1 or x.shape[0] != P * S1 or x.shape[1] < 1:
+        raise ValueError(f"path_d2: x ({P} * {S1}, D >= 1) expected, got {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(P, S1, dtype=torch.float64, device=x.device)
+    _chk(out, "out", (P, S1), torch.float64)
+    L.check(L.load().mg_path_d2(_p(x), P, S1, x.shape[1], _p(out), _stream()), "mg_path_d2")
+    return out
+
+
+def path_probs(logits, group, S1: int, n_groups: int, probs=None, acc=None):
+    """The classifier along P paths of S1 consecutive rows (mg_path_probs): logits (P * S1, K) fp32, group (P,) int32 -> probs
+    (P * S1, K) fp64, the softmax, and acc (n_groups, S1, K + 1) fp64, its sums over each group's paths and their count.
+    Returns (probs, acc)."""
+    _chk(logits, "logits")
+    S1, G = int(S1), int(n_groups)
+    if logits.dim() != 2 or not 2 <= logits.shape[1] <= PATH_MAX_CLASSES or S1 < 1 or G < 1 or logits.shape[0] < 1 or \
+            logits.shape[0] % S1:
+        raise ValueError(f"path_probs: logits (P * {S1}, K in 2..{PATH_MAX_CLASSES}) and n_groups >= 1 expected, got "
+                         f"{tuple(logits.shape)}, n_groups = {G}")
+    rows, K = logits.shape
+    P = rows // S1
+    _chk(group, "group", (P,), torch.int32)
+    if probs is None:
+        probs = torch.empty(rows, K, dtype=torch.float64, device=logits.device)
+    if acc is None:
+        acc = torch.empty(G, S1, K + 1, dtype=torch.float64, device=logits.device)
+    _chk(probs, "probs", (rows, K), torch.float64)
+    _chk(acc, "acc", (G, S1, K + 1), torch.float64)
+    L.check(L.load().mg_path_probs(_p(logits), _p(group), P, S1, K, G, _p(probs), _p(acc), _stream()), "mg_path_probs")
+    return probs, acc
+
+
 def voice_struct(mult, weight, decay, attack: int, release_tau: float, release_len: int, fs: float) -> L.Voice:
     """mg_voice from a partial table (equally long sequences of multipliers, weights and decay rates in 1/s) and the envelope:
     attack and release_len in samples, release_tau in seconds.  Only the table's length is checked here; the values are
