@@ -606,6 +606,46 @@ int mg_path_d2(const float* x, int P, int S1, int D, double* out, mg_stream_t st
 int mg_path_probs(const float* logits, const int32_t* group, int P, int S1, int n_classes, int n_groups, double* probs,
                   double* acc, mg_stream_t stream);
 
+/* ---- edits in the VAE's latent space (melo_gan_amd.ae.edit; csrc/latent_edit.hip) ----
+ * mg_latent_rows: the decoder's input z (rows, L) fp32 for `rows` edited latents.  mu, logvar (n_src, L) fp32 are the encoded
+ *   source pieces, dirs (n_dir, L) fp32 direction vectors (NULL when n_dir is 0; mu and logvar may be NULL when n_src is 0).
+ *   Row r carries kind[r] (int32: 0 padding, 1 prior, 2 posterior), src_a[r], src_b[r] (int32 rows of mu), t[r] (fp32), dir[r]
+ *   (int32 row of dirs, < 0: none), alpha[r], sigma[r] (fp32) and key[r] = (piece, sample) (an int32 pair), all on the device:
+ *     kind 0:  z = 0; nothing else of the row is used
+ *     kind 1:  base = 0, s = 1 (src_a, src_b and t are not used)
+ *     kind 2:  base = mu[a]                          when t == 0 or a == b  (mu[b] is not read)
+ *              base = mu[b]                          when t == 1
+ *              base = (1 - t) mu[a] + t mu[b]        otherwise, interp 0
+ *              base = ca mu[a] + cb mu[b]            otherwise, interp 1: theta = acos(clamp(mu[a].mu[b] / (|mu[a]| |mu[b]|),
+ *                                                    -1, 1)), ca = sin((1 - t) theta) / sin(theta), cb = sin(t theta) /
+ *                                                    sin(theta) (sin(theta) < 2^-20 or not a number: ca = 1 - t, cb = t), from
+ *                                                    fp64 sums of the widened elements: lane u of 64 adds the element blocks
+ *                                                    q = u, u + 64, .. (elements 4q .. 4q + 3) in element order, then a fixed
+ *                                                    butterfly over the lanes; ca and cb stay fp64
+ *              s = exp(0.5 logvar[a])
+ *     z = base + alpha * dirs[dir] + (sigma * s) * n,  added in this order
+ *   n ~ N(0,1): Philox4x32-10 keyed by `seed`, counter = (element block, a tag of this kernel's own, piece, sample), Box-Muller
+ *   as mg_gen_inputs applies it: a row's normals depend on its key and the seed alone, not on its position, the other rows or
+ *   their number.  Everything is evaluated in fp64 from the widened fp32 inputs, every product and sum rounded on its own, with
+ *   ONE rounding to fp32 at the store.  A term whose coefficient is exactly 0 is not evaluated (alpha == 0 or dir < 0: dirs is
+ *   not read; sigma == 0: nothing is drawn and logvar is not read), so a posterior row with t in {0, 1}, alpha = 0 and
+ *   sigma = 0 is mu[a] or mu[b] bit for bit, and a prior row with sigma = 1 and no direction is n itself.
+ * mg_latent_cycle: what decode -> re-encode keeps of each edit.  z, mu2 (rows, L) fp32: the edited latents and the posterior
+ *   means of their re-encoded decodings; kind, src_a, dir as above.  out (rows, 6) fp64, with m = mu[src_a] (0 for a prior row)
+ *   and d = dirs[dir]:
+ *     out[r] = { |z - m|^2, |mu2 - z|^2, |mu2 - m|^2, (mu2 - m).d, (z - m).d, d.d }      the last three 0 when dir < 0
+ *   and six zeros for a padding row.  Every element is widened to fp64 before the subtraction (identical inputs give exactly
+ *   0); lane u of 64 adds the elements u, u + 64, .. in that order, then a fixed butterfly over the wave.
+ * Both: one 64-lane workgroup per row; no atomics; capturable; eager runs, reruns and graph replays leave identical bits.
+ *   L 1..1024; rows >= 0 (0: nothing is launched); n_src, n_dir >= 0.  The descriptors lie on the device, so the entry points
+ *   cannot see them: a row of kind 1 or 2 whose src_a / src_b (kind 2) lies outside [0, n_src), whose dir >= n_dir, or whose
+ *   kind is none of 0, 1, 2 reads neither mu, logvar nor dirs and is written as NaN. */
+int mg_latent_rows(const float* mu, const float* logvar, int n_src, const float* dirs, int n_dir, const int32_t* kind,
+                   const int32_t* src_a, const int32_t* src_b, const float* t, const int32_t* dir, const float* alpha,
+                   const float* sigma, const int32_t* key, int rows, int L, int interp, uint64_t seed, float* z, mg_stream_t stream);
+int mg_latent_cycle(const float* z, const float* mu2, const float* mu, int n_src, const float* dirs, int n_dir, const int32_t* kind,
+                    const int32_t* src_a, const int32_t* dir, int rows, int L, double* out, mg_stream_t stream);
+
 /* ---- rendering note lists to audio (csrc/render.hip; melo_gan_amd.audio, melo_gan_amd.render, generate --wav) ----
  * The reference stops at the .mid file; hearing one takes a synthesiser from outside.  mg_render_notes is an additive
  * synthesiser with an integer phase accumulator: F files in ONE launch, a lane per output sample.

@@ -170,6 +170,8 @@ SIGNATURES = {
     "mg_gen_inputs_mix": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, f32, vp, i32, C.c_uint64, vp]),
     "mg_path_d2": (i32, [vp, i32, i32, i32, vp, vp]),
     "mg_path_probs": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "mg_latent_rows": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_uint64, vp, vp]),
+    "mg_latent_cycle": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
     "mg_render_notes": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, C.POINTER(Voice), vp, vp, vp]),
     "mg_pcm_peak": (i32, [vp, vp, i32, i64, vp, vp]),
     "mg_pcm_quantise": (i32, [vp, vp, vp, i32, i64, f32, vp, vp]),

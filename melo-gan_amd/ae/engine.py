@@ -131,6 +131,14 @@ class VaeEngine:
 
     # ---------------------------------------------------------------------------------------------
     def forward(self, train: bool = True):
+        self.encode(train)
+        ops.reparam_fwd(self.mu, self.lv, self.eps, self.zl)
+        self.decode(train)
+        if train:
+            self.num_batches_tracked += 1
+
+    def encode(self, train: bool = True):
+        """x -> mu, lv: the encoder and the two heads."""
         p = self.P.p
         a = self.x
         for j, (i, ci, co) in enumerate(ENC):
@@ -148,7 +156,10 @@ class VaeEngine:
         ops.linear_fwd(self.flat, p["encoder._linear.1.weight"], self.h, bias=p["encoder._linear.1.bias"], act=ACT_RELU)
         ops.linear_fwd(self.h, p["fc_mu.weight"], self.mu, bias=p["fc_mu.bias"])
         ops.linear_fwd(self.h, p["fc_log_var.weight"], self.lv, bias=p["fc_log_var.bias"])
-        ops.reparam_fwd(self.mu, self.lv, self.eps, self.zl)
+
+    def decode(self, train: bool = True):
+        """zl -> recon: the decoder on whatever latent zl holds (forward's own, or one written from outside: ae/edit.py)."""
+        p = self.P.p
         ops.linear_fwd(self.zl, p["decoder.pre.0.weight"], self.p0, bias=p["decoder.pre.0.bias"], act=ACT_RELU)
         ops.linear_fwd(self.p0, p["decoder.pre.2.weight"], self.p2, bias=p["decoder.pre.2.bias"], act=ACT_RELU)
         ops.transpose_bcl_blc(self.p2.view(self.B, 128, self.red), self.y0)
@@ -166,8 +177,6 @@ class VaeEngine:
                 ops.bn_eval_fwd(self.dz_[j], self.da_[j], p[nm + ".weight"], p[nm + ".bias"], self.buf[nm + ".running_mean"],
                                 self.buf[nm + ".running_var"], ACT_RELU, BN_EPS)
             a = self.da_[j]
-        if train:
-            self.num_batches_tracked += 1
 
     def backward(self, beta: float):
         p, g, B = self.P.p, self.P.g, self.B

@@ -244,6 +244,12 @@ __device__ __forceinline__ void philox4(unsigned (&c)[4], unsigned k0, unsigned 
     }
 }
 __device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// four N(0,1) draws from one Philox output block (Box-Muller on the pairs (c0, c1) and (c2, c3))
+__device__ __forceinline__ void box_muller4(const unsigned (&c)[4], float (&v)[4]) {
+    const float r0 = sqrtf(-2.f * logf(u01(c[0]))), r1 = sqrtf(-2.f * logf(u01(c[2])));
+    const float t0 = 6.28318530717958647692f * u01(c[1]), t1 = 6.28318530717958647692f * u01(c[3]);
+    v[0] = r0 * cosf(t0); v[1] = r0 * sinf(t0); v[2] = r1 * cosf(t1); v[3] = r1 * sinf(t1);
+}
 
 // The 160 KiB dynamic-LDS opt-in of the tile kernels, made once per (kernel, device): the attribute belongs to the
 // kernel's code object on ONE device, so a process that drives several devices sets it on each.  `done` is the caller's

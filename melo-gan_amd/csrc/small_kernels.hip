@@ -882,12 +882,7 @@ __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __rest
 // step lo, step hi); the step counter lives in device memory and is advanced by the kernel itself so a
 // captured hipGraph draws fresh numbers on every replay.
 // philox4 / u01: csrc/common.h (csrc/mlp_train.hip draws its dropout masks from the same streams)
-// four N(0,1) draws from one Philox output block (Box-Muller on the pairs (c0, c1) and (c2, c3))
-__device__ __forceinline__ void box_muller4(const unsigned (&c)[4], float (&v)[4]) {
-    const float r0 = sqrtf(-2.f * logf(u01(c[0]))), r1 = sqrtf(-2.f * logf(u01(c[2])));
-    const float t0 = 6.28318530717958647692f * u01(c[1]), t1 = 6.28318530717958647692f * u01(c[3]);
-    v[0] = r0 * cosf(t0); v[1] = r0 * sinf(t0); v[2] = r1 * cosf(t1); v[3] = r1 * sinf(t1);
-}
+// box_muller4: csrc/common.h too (csrc/latent_edit.hip draws its normals through it)
 
 struct RngJob { float* dst; long n; int kind; float p0; };   // kind 0: N(0,1); 1: U(0,1); 2: keep-mask*(1/(1-p0))
 struct RngJobs { RngJob j[4]; int njobs; };

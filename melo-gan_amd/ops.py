@@ -1734,6 +1734,71 @@ def path_probs(logits, group, S1: int, n_groups: int, probs=None, acc=None):
     return probs, acc
 
 
+LATENT_MAX_DIM = 1024
+
+
+def _latent_sources(who, mu, dirs, L):
+    """The (n_src, L) / (n_dir, L) arrays of the latent kernels, either of which may be None: returns (n_src, n_dir)."""
+    n = []
+    for t, nm in ((mu, "mu"), (dirs, "dirs")):
+        if t is not None:
+            _chk(t, f"{who}: {nm}")
+            if t.dim() != 2 or t.shape[1] != L:
+                raise ValueError(f"{who}: {nm} (n, {L}) expected, got {tuple(t.shape)}")
+        n.append(0 if t is None else t.shape[0])
+    return n
+
+
+def latent_rows(mu, logvar, dirs, kind, src_a, src_b, t, dir, alpha, sigma, key, z, interp=0, seed=0):
+    """The decoder's input for a chunk of edited latents (mg_latent_rows): z (rows, L) = base + alpha * dirs[dir] + sigma * s *
+    N(0,1) per row, with kind (rows,) int32 0 padding (zeros) / 1 prior (base 0, s 1) / 2 posterior (base between mu[src_a] and
+    mu[src_b] at t, s = exp(logvar[src_a] / 2)); dir < 0 = no direction; key (rows, 2) int32 = (piece, sample) names the row's
+    normals.  mu, logvar (n_src, L) and dirs (n_dir, L) may be None (no such rows).  interp: 0 lerp, 1 slerp.  The descriptors
+    stay on the device; a row that points outside mu or dirs comes back as NaN."""
+    _chk(z, "z")
+    if z.dim() != 2 or not 1 <= z.shape[1] <= LATENT_MAX_DIM:
+        raise ValueError(f"latent_rows: z (rows, L in 1..{LATENT_MAX_DIM}) expected, got {tuple(z.shape)}")
+    rows, Ld = z.shape
+    n_src, n_dir = _latent_sources("latent_rows", mu, dirs, Ld)
+    if mu is not None:
+        _chk(logvar, "logvar", tuple(mu.shape))
+    for v, nm in ((kind, "kind"), (src_a, "src_a"), (src_b, "src_b"), (dir, "dir")):
+        _chk(v, nm, (rows,), torch.int32)
+    for v, nm in ((t, "t"), (alpha, "alpha"), (sigma, "sigma")):
+        _chk(v, nm, (rows,))
+    _chk(key, "key", (rows, 2), torch.int32)
+    if int(interp) not in (0, 1):
+        raise ValueError(f"latent_rows: interp = {interp}: 0 (lerp) or 1 (slerp)")
+    if rows == 0:
+        return z
+    L.check(L.load().mg_latent_rows(_p(mu), _p(logvar), n_src, _p(dirs), n_dir, _p(kind), _p(src_a), _p(src_b), _p(t), _p(dir),
+                                    _p(alpha), _p(sigma), _p(key), rows, Ld, int(interp), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(z),
+                                    _stream()), "mg_latent_rows")
+    return z
+
+
+def latent_cycle(z, mu2, mu, dirs, kind, src_a, dir, out=None):
+    """What decode -> re-encode keeps of each edit (mg_latent_cycle): z, mu2 (rows, L) fp32 -> out (rows, 6) fp64 = |z - m|^2,
+    |mu2 - z|^2, |mu2 - m|^2, (mu2 - m).d, (z - m).d, d.d with m = mu[src_a] (0 for a prior row) and d = dirs[dir] (the last three
+    0 when dir < 0); zeros for a padding row."""
+    _chk(z, "z")
+    if z.dim() != 2 or not 1 <= z.shape[1] <= LATENT_MAX_DIM:
+        raise ValueError(f"latent_cycle: z (rows, L in 1..{LATENT_MAX_DIM}) expected, got {tuple(z.shape)}")
+    rows, Ld = z.shape
+    _chk(mu2, "mu2", (rows, Ld))
+    n_src, n_dir = _latent_sources("latent_cycle", mu, dirs, Ld)
+    for v, nm in ((kind, "kind"), (src_a, "src_a"), (dir, "dir")):
+        _chk(v, nm, (rows,), torch.int32)
+    if out is None:
+        out = torch.empty(rows, 6, dtype=torch.float64, device=z.device)
+    _chk(out, "out", (rows, 6), torch.float64)
+    if rows == 0:
+        return out
+    L.check(L.load().mg_latent_cycle(_p(z), _p(mu2), _p(mu), n_src, _p(dirs), n_dir, _p(kind), _p(src_a), _p(dir), rows, Ld, _p(out),
+                                     _stream()), "mg_latent_cycle")
+    return out
+
+
 def voice_struct(mult, weight, decay, attack: int, release_tau: float, release_len: int, fs: float) -> L.Voice:
     """mg_voice from a partial table (equally long sequences of multipliers, weights and decay rates in 1/s) and the envelope:
     attack and release_len in samples, release_tau in seconds.  Only the table's length is checked here; the values are
