@@ -27,7 +27,7 @@ reconstruction, which the note-level change and the classifier's `before` are me
 
 Writes (unless --no-files) prior_<k>.mid, vary_r<row>_<k>.mid, path_r<a>_r<b>_s<ss>.mid (--join: also path_r<a>_r<b>.mid, the
 first 64 notes of every step one after the other) or shift_r<row>_<emotion>_<j>.mid through midi.save_piano_roll_to_midi; --shift
-decodes with the target emotion's scale and tempo (generate.STYLE), the other modes with --scale / --bpm.  <out>/edit.json holds
+decodes with the target emotion's scale and tempo (pieces.STYLE), the other modes with --scale / --bpm.  <out>/edit.json holds
 per output row its descriptors, latent_step = |z - mu_a|, cycle_error = |mu2 - z|, for shifts requested = (z - mu_a).d / d.d and
 realised = (mu2 - mu_a).d / d.d, the note-level change against the source's own reconstruction and, with a classifier, its
 verdict before and after; and one summary block of their means (per strength for --shift).  Every check raises AeEditError; the
@@ -38,14 +38,13 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import sys
 from dataclasses import dataclass
 from typing import List, Optional
 
 import numpy as np
 import torch
 
-from ..gan.generate import EMOTIONS, STYLE, WAV_MAX_SECONDS, WAV_PEAK_DB
+from ..pieces import EMOTIONS, STYLE, add_wav_arguments, joined_notes, plan_wav, require_device, run_tool, write_pieces
 from . import latent_edit as LE
 
 DEFAULT_BATCH = 64
@@ -82,8 +81,7 @@ class LatentEditor:
     def __init__(self, cfg: dict, device="cuda", batch: int = DEFAULT_BATCH):
         from ..eval_pass import GraphCache
         from .engine import VaeEngine
-        if not torch.cuda.is_available():
-            raise AeEditError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+        require_device(AeEditError)
         if int(batch) < 1 or int(batch) > 32767:
             raise AeEditError(f"batch = {batch}: must be in 1..32767")
         check_ae_config(cfg)
@@ -329,9 +327,7 @@ def parse_args(argv=None):
     ap.add_argument("--join", action="store_true", help="--from / --to: also write the steps one after the other as one piece")
     ap.add_argument("--ed_config", type=str, default=None, help="ED config of the classifier that scores the rows")
     ap.add_argument("--ed_ckpt", type=str, default=None, help="ED checkpoint (ed_best.pth)")
-    ap.add_argument("--wav", action="store_true", help="also render every .mid to a .wav")
-    ap.add_argument("--wav-fs", type=int, default=44100)
-    ap.add_argument("--voice", type=str, default="piano")
+    add_wav_arguments(ap, help_wav="also render every .mid to a .wav", help_fs=None, help_voice=None)
     ap.add_argument("--no-files", action="store_true", help="write edit.json only")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N random rows and labels, untrained weights")
     return ap.parse_args(argv)
@@ -442,8 +438,7 @@ def plan(args) -> Plan:
     if mode == "path" and args.interp not in LE.INTERP:
         raise AeEditError(f"--interp {args.interp!r}: expected one of {', '.join(LE.INTERP)}")
     files = not args.no_files
-    if (args.join or args.wav) and not files:
-        raise AeEditError("--no-files writes edit.json only: it cannot go with --join or --wav")
+    wav = plan_wav(args, AeEditError, files, args.join, "edit.json")
     if args.join and mode != "path":
         raise AeEditError("--join joins the steps of a path: it needs --from ROW --to ROW")
     if args.scale not in midi.SCALES:
@@ -532,14 +527,6 @@ def plan(args) -> Plan:
         ed_cfg = load_config(args.ed_config)
         if not os.path.isfile(args.ed_ckpt):
             raise AeEditError(f"ED checkpoint {args.ed_ckpt} does not exist")
-    wav = None
-    if args.wav:
-        from .. import audio
-        wav = {"fs": args.wav_fs, "voice": args.voice, "peak_db": WAV_PEAK_DB}
-        try:
-            audio.check_settings(wav["fs"], wav["voice"], wav["peak_db"], WAV_MAX_SECONDS)
-        except audio.AudioError as e:
-            raise AeEditError(f"--wav: {e}") from e
     out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/ae"), "ae_edit")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
     return Plan(cfg, ed_cfg, args.model, args.ed_ckpt, mode, rows, notes, labels, source, c_notes, c_labels, c_source, target, out,
@@ -560,32 +547,14 @@ def file_name(p: Plan, r: int) -> str:
 
 def write_files(p: Plan, res: EditResult) -> List[dict]:
     """The .mid (and --wav: .wav) files of a run; returns edit.json's files[] entries, one per output row first."""
-    from .. import midi
-    os.makedirs(p.out, exist_ok=True)
     scale, bpm = (STYLE[EMOTIONS[p.target]][0], float(STYLE[EMOTIONS[p.target]][1])) if p.mode == "shift" else (p.scale, p.bpm)
-    files, lists = [], []
-    for r in range(res.R):
-        name = file_name(p, r)
-        midi.save_piano_roll_to_midi(res.recon[r], os.path.join(p.out, name), bpm=bpm, scale=scale, root_key=0,
-                                     instrument_name="Acoustic Grand Piano")
-        files.append({"file": name, "row": r, "bpm": bpm, "scale": scale})
-        lists.append(midi.notes_from_roll(res.recon[r], bpm=bpm, scale=scale, root_key=0)[0])
+    todo = [({"file": file_name(p, r), "row": r, "bpm": bpm, "scale": scale}, (res.recon[r], scale, bpm)) for r in range(res.R)]
     if p.join:
-        from ..gan.morph import joined_notes
         a, b = p.rows.sources[int(p.rows.src_a[0])], p.rows.sources[int(p.rows.src_b[0])]
         n = min(JOIN_NOTES, res.recon.shape[1])
-        notes = joined_notes(list(res.recon[:res.R]), [(scale, bpm)] * res.R, n)
-        midi.write_smf(os.path.join(p.out, f"path_r{a}_r{b}.mid"), notes, 120.0, 0)
-        files.append({"file": f"path_r{a}_r{b}.mid", "joined": True, "join_notes": n})
-        lists.append(notes)
-    if p.wav is not None:
-        from .. import audio
-        r = audio.Renderer("cuda", p.wav["fs"], p.wav["voice"], p.wav["peak_db"], WAV_MAX_SECONDS)
-        for f, pcm, rep in zip(files, r.render(lists), r.report):
-            f["wav"] = f["file"][:-4] + ".wav"
-            f["seconds"], f["truncated"] = rep.seconds, rep.truncated
-            audio.write_wav(os.path.join(p.out, f["wav"]), pcm, p.wav["fs"])
-    return files
+        todo.append(({"file": f"path_r{a}_r{b}.mid", "joined": True, "join_notes": n},
+                     joined_notes(list(res.recon[:res.R]), [(scale, bpm)] * res.R, n)))
+    return write_pieces(p.out, todo, p.wav)
 
 
 def build_report(p: Plan, res: EditResult, files: List[dict], counts=None) -> dict:
@@ -612,9 +581,8 @@ def build_report(p: Plan, res: EditResult, files: List[dict], counts=None) -> di
 
 
 def run(p: Plan) -> dict:
-    if not torch.cuda.is_available():
-        raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
-    ed = LatentEditor(p.cfg, "cuda", p.batch)
+    require_device()
+    ed =LatentEditor(p.cfg, "cuda", p.batch)
     if p.synthetic:
         ed.eng.init_weights(0)
     else:
@@ -655,13 +623,7 @@ def run(p: Plan) -> dict:
 
 
 def main(argv=None) -> int:
-    args = parse_args(argv)
-    try:
-        run(plan(args))
-    except AeEditError as e:
-        print(f"ae.edit: error: {e}", file=sys.stderr)
-        return 2
-    return 0
+    return run_tool("ae.edit", AeEditError, plan, run, parse_args(argv), catch_run=True)
 
 
 if __name__ == "__main__":

@@ -27,8 +27,8 @@ import numpy as np
 import torch
 
 from ..gan.config import load_config
-from ..gan.generate import EMOTIONS
 from ..gan.utils import emotion_to_index
+from ..pieces import EMOTIONS, require_device
 from ..eval_pass import Packed, ResidentPass, check_split
 from . import metrics as M
 from .encode import load_model
@@ -50,8 +50,7 @@ class VaeEvaluator:
     def __init__(self, cfg: dict, device="cuda", batch: int = DEFAULT_BATCH, share: Optional[VaeEngine] = None,
                  n_classes: int = len(EMOTIONS)):
         from .. import ops
-        if not torch.cuda.is_available():
-            raise AeEvaluateError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+        require_device(AeEvaluateError)
         if int(batch) < 1 or int(batch) > 32767:
             raise AeEvaluateError(f"batch = {batch}: must be in 1..32767")
         for k in ("MAX_NOTES", "LATENT_DIM"):
@@ -166,8 +165,7 @@ def parse_args(argv=None):
 
 def run(args) -> dict:
     from ..midi import save_recon_midi
-    if not torch.cuda.is_available():
-        raise AeEvaluateError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+    require_device(AeEvaluateError)
     if not os.path.isfile(args.config):
         raise AeEvaluateError(f"config {args.config} does not exist")
     cfg = load_config(args.config)

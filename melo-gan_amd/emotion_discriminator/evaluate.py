@@ -30,8 +30,8 @@ import numpy as np
 import torch
 
 from ..gan.config import load_config
-from ..gan.generate import EMOTIONS
 from ..eval_pass import Packed, ResidentPass, check_split
+from ..pieces import EMOTIONS, require_device
 from . import metrics as M
 from .latent_engine import make_engine
 
@@ -67,8 +67,7 @@ class EdEvaluator:
 
     def __init__(self, cfg: dict, device="cuda", batch: int = DEFAULT_BATCH, n_bins: int = M.N_BINS):
         from .. import ops
-        if not torch.cuda.is_available():
-            raise EdEvaluateError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+        require_device(EdEvaluateError)
         if int(batch) < 1 or int(batch) > 32767:
             raise EdEvaluateError(f"batch = {batch}: must be in 1..32767")
         if not 1 <= int(n_bins) <= ops.CLS_MAX_BINS:
@@ -298,8 +297,7 @@ def load_rows(cfg: dict, split: str, synthetic: int, seed: int, device):
 
 
 def run(args) -> dict:
-    if not torch.cuda.is_available():
-        raise EdEvaluateError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+    require_device(EdEvaluateError)
     if not os.path.isfile(args.config):
         raise EdEvaluateError(f"config {args.config} does not exist")
     cfg = load_config(args.config)

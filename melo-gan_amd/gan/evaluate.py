@@ -54,6 +54,7 @@ from . import feature_metrics as FM
 from . import generate as G
 from . import music_metrics as MM
 from ..eval_pass import Packed, ResidentPass
+from ..pieces import require_device
 from .eval_engine import EvalEngine
 from .generate import EMOTIONS, GenerateError
 from .utils import check_labels, emotion_to_index
@@ -633,8 +634,7 @@ def main(argv=None) -> int:
     except GenerateError as e:
         print(f"evaluate: error: {e}", file=sys.stderr)
         return 2
-    if not torch.cuda.is_available():
-        raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+    require_device()
     from .dataset import GANDataset
     cfg = p.cfg
     if p.synthetic:

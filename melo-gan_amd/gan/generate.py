@@ -36,21 +36,18 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from .. import pieces
+from ..pieces import EMOTIONS, STYLE           # also for those who read generate.EMOTIONS and generate.STYLE
 from . import config as C
 from .eval_engine import EvalEngine
 
-EMOTIONS = ("happy", "sad", "angry", "calm")          # emotion_to_index (gan/utils.py) = the classifier's class order
 # app.py:53-65 (get_gan_features): the base vector of each emotion and the jitter added to it
 EMOTION_TABLE = ((1.0, 1.0, 0.8, 0.8, 0.5, 0.5),
                  (-1.0, -1.0, -0.5, -0.5, -0.5, -0.5),
                  (1.0, -1.0, 1.0, 1.0, -0.8, 0.8),
                  (-1.0, 1.0, -0.8, -0.8, 0.5, -0.5))
 JITTER = 0.15
-# app.py:109-110: (scale, bpm) per emotion; root key C, piano
-STYLE = {"happy": ("major", 140), "sad": ("minor", 70), "angry": ("minor", 160), "calm": ("major", 90)}
 DEFAULT_BATCH = 64
-WAV_PEAK_DB = -1.0
-WAV_MAX_SECONDS = 3600.0      # where --wav would cut a sample: 512 steps of at most 4 beats at 60 bpm stay below it
 
 
 class GenerateError(ValueError):
@@ -218,9 +215,7 @@ def parse_args(argv=None):
     ap.add_argument("--ed_config", type=str, default=None, help="ED config of the classifier that scores the samples")
     ap.add_argument("--ed_ckpt", type=str, default=None, help="ED checkpoint (ed_best.pth)")
     ap.add_argument("--ema", action="store_true", help="sample from the averaged weights in a full checkpoint's 'ema' block")
-    ap.add_argument("--wav", action="store_true", help="also render every sample to test_<emotion>_<k>.wav")
-    ap.add_argument("--wav-fs", type=int, default=44100, help="sample rate of the .wav files in Hz")
-    ap.add_argument("--voice", type=str, default="piano", help="the renderer's voice: piano, organ or sine")
+    pieces.add_wav_arguments(ap, help_wav="also render every sample to test_<emotion>_<k>.wav")
     return ap.parse_args(argv)
 
 
@@ -290,14 +285,7 @@ def plan(args) -> Plan:
             raise GenerateError(f"ED checkpoint {args.ed_ckpt} does not exist")
     out = args.out or cfg.get("SAMPLE_DIR", "experiments/gan/samples")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
-    wav = None
-    if getattr(args, "wav", False):
-        from .. import audio
-        wav = {"fs": args.wav_fs, "voice": args.voice, "peak_db": WAV_PEAK_DB}
-        try:
-            audio.check_settings(wav["fs"], wav["voice"], wav["peak_db"], WAV_MAX_SECONDS)
-        except audio.AudioError as e:
-            raise GenerateError(f"--wav: {e}") from e
+    wav = pieces.plan_wav(args, GenerateError)
     return Plan(cfg, ed_cfg, ckpt_path, ckpt, args.ed_ckpt, emotions, samples, out, seed, args.batch, ema, wav)
 
 
@@ -306,51 +294,30 @@ def midi_name(emotion: str, k: int) -> str:
 
 
 def wav_name(emotion: str, k: int) -> str:
+    """The .wav beside midi_name(emotion, k): the name pieces.write_pieces derives from the .mid's, x.mid -> x.wav."""
     return f"test_{emotion}_{k}.wav"
 
 
-def write_wavs(p: Plan, res: Samples, files: List[dict]) -> None:
-    """--wav: every sample's note list -- the one save_piano_roll_to_midi writes -- through one Renderer; files[i] gains wav,
-    seconds and truncated."""
-    from .. import audio, midi
-    lists = [midi.notes_from_roll(res.notes[i], bpm=STYLE[e][1], scale=STYLE[e][0], root_key=0)[0] for i, e in enumerate(res.emotion)]
-    r = audio.Renderer("cuda", p.wav["fs"], p.wav["voice"], p.wav["peak_db"], WAV_MAX_SECONDS)
-    for f, pcm, rep in zip(files, r.render(lists), r.report):
-        f["wav"] = wav_name(f["emotion"], f["k"])
-        f["seconds"], f["truncated"] = rep.seconds, rep.truncated
-        audio.write_wav(os.path.join(p.out, f["wav"]), pcm, p.wav["fs"])
-
-
 def write_outputs(p: Plan, res: Samples) -> dict:
-    from .. import midi
-    os.makedirs(p.out, exist_ok=True)
-    files = []
+    """Every sample with its emotion's scale and tempo through pieces.write_pieces, then summary.json."""
+    todo = []
     for i, (e, k) in enumerate(zip(res.emotion, res.k)):
-        scale, bpm = STYLE[e]
-        midi.save_piano_roll_to_midi(res.notes[i], os.path.join(p.out, midi_name(e, k)), bpm=bpm, scale=scale, root_key=0,
-                                     instrument_name="Acoustic Grand Piano")
-        files.append({"file": midi_name(e, k), "emotion": e, "k": k,
-                      "ed_pred": None if res.pred is None else EMOTIONS[int(res.pred[i])],
-                      "ed_p_target": None if res.p_target is None else float(res.p_target[i])})
+        f = {"file": midi_name(e, k), "emotion": e, "k": k,
+             "ed_pred": None if res.pred is None else EMOTIONS[int(res.pred[i])],
+             "ed_p_target": None if res.p_target is None else float(res.p_target[i])}
+        todo.append((f, (res.notes[i],) + STYLE[e]))
+    files = pieces.write_pieces(p.out, todo, p.wav)
     summary = {"checkpoint": p.ckpt_path, "weights": "ema" if p.ema else "raw", "ed_checkpoint": p.ed_ckpt, "seed": p.seed, "samples": p.samples,
                "batch": p.batch, "emotions": p.emotions, "per_emotion": res.summary, "files": files}
     if p.wav is not None:
-        write_wavs(p, res, files)
         summary["wav"] = dict(p.wav)
     with open(os.path.join(p.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     return summary
 
 
-def main(argv=None) -> int:
-    args = parse_args(argv)
-    try:
-        p = plan(args)
-    except GenerateError as e:
-        print(f"generate: error: {e}", file=sys.stderr)
-        return 2
-    if not torch.cuda.is_available():
-        raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+def run(p: Plan) -> None:
+    pieces.require_device()
     sampler = Sampler(p.cfg, p.ed_cfg, "cuda", p.batch)
     sampler.load_generator(p.ckpt, ema=p.ema)
     if p.ed_cfg is not None:
@@ -362,7 +329,10 @@ def main(argv=None) -> int:
     for e, s in res.summary.items():
         print(f"{e:<8} {s['n']:>4} {fmt(s['ed_accuracy'], '.3f'):>12} {fmt(s['ed_mean_p_target'], '.4f'):>17}")
     print(f"wrote {len(res.emotion)} MIDI files{' and WAV files' if p.wav is not None else ''} and summary.json to {p.out}")
-    return 0
+
+
+def main(argv=None) -> int:
+    return pieces.run_tool("generate", GenerateError, plan, run, parse_args(argv))
 
 
 if __name__ == "__main__":

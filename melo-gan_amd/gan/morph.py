@@ -19,7 +19,7 @@ classifier's ed_proj features (notes mode) and the rolls of every chunk are copi
 mg_path_probs / mg_path_d2 run once over them after the last chunk: nothing in the report depends on --batch.
 
 Writes (unless --no-files) morph_<a>_<b>_<k>_s<ss>.mid per step, or blend_<k>.mid, with bpm = round(sum_e w_e bpm_e) and the
-scale of the heaviest emotion (generate.STYLE); with --join also morph_<a>_<b>_<k>.mid, the first --join-notes rows of every
+scale of the heaviest emotion (pieces.STYLE); with --join also morph_<a>_<b>_<k>.mid, the first --join-notes rows of every
 step one after the other (morph_metrics.join_offsets), written at 120 bpm; with --wav the same note lists rendered by
 audio.Renderer.  morph.json holds, per pair, the step weights w, p_mean[s][k], the crossover of the mean curves,
 monotone_fraction, switch_fraction, and a `feature` and a `roll` block of path_length, endpoint_distance, straightness and ppl
@@ -38,10 +38,12 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .. import pieces
+from ..pieces import EMOTIONS, STYLE, joined_notes          # joined_notes also for those who read morph.joined_notes
 from . import morph_metrics as MM
 from .eval_engine import EvalEngine
-from .generate import (DEFAULT_BATCH, EMOTIONS, EMOTION_TABLE, JITTER, STYLE, WAV_MAX_SECONDS, WAV_PEAK_DB, GenerateError,
-                       _read_config, check_ed_config, check_gan_config, check_generator_checkpoint, load_checkpoint, plan_config)
+from .generate import (DEFAULT_BATCH, EMOTION_TABLE, JITTER, GenerateError, _read_config, check_ed_config, check_gan_config,
+                       check_generator_checkpoint, load_checkpoint, plan_config)
 
 NOISE_MODES = ("fixed", "slerp")
 
@@ -120,7 +122,7 @@ def heaviest(weights: Sequence[float]) -> int:
 
 
 def style_of(weights: Sequence[float]) -> Tuple[str, int]:
-    """(scale, bpm) of a weight vector: the scale of the heaviest emotion, bpm = round(sum_e w_e bpm_e) (generate.STYLE)."""
+    """(scale, bpm) of a weight vector: the scale of the heaviest emotion, bpm = round(sum_e w_e bpm_e) (pieces.STYLE)."""
     return STYLE[EMOTIONS[heaviest(weights)]][0], int(round(sum(float(w) * STYLE[e][1] for w, e in zip(weights, EMOTIONS))))
 
 
@@ -235,9 +237,7 @@ def parse_args(argv=None):
     ap.add_argument("--ed_ckpt", type=str, default=None, help="ED checkpoint (ed_best.pth)")
     ap.add_argument("--join", action="store_true", help="also write each path as one piece, morph_<a>_<b>_<k>.mid")
     ap.add_argument("--join-notes", type=int, default=64, help="rows of each step's roll that go into the joined piece")
-    ap.add_argument("--wav", action="store_true", help="also render every .mid to a .wav")
-    ap.add_argument("--wav-fs", type=int, default=44100, help="sample rate of the .wav files in Hz")
-    ap.add_argument("--voice", type=str, default="piano", help="the renderer's voice: piano, organ or sine")
+    pieces.add_wav_arguments(ap, help_wav="also render every .mid to a .wav")
     ap.add_argument("--no-files", action="store_true", help="write morph.json only")
     return ap.parse_args(argv)
 
@@ -322,8 +322,7 @@ def plan(args) -> Plan:
     if args.noise not in NOISE_MODES:
         raise MorphError(f"--noise {args.noise!r}: expected one of {', '.join(NOISE_MODES)}")
     files = not args.no_files
-    if (args.join or args.wav) and not files:
-        raise MorphError("--no-files writes morph.json only: it cannot go with --join or --wav")
+    wav = pieces.plan_wav(args, MorphError, files, args.join, "morph.json")
     if args.join and mode != "pairs":
         raise MorphError("--join joins the steps of a path: it needs --from / --to or --pairs")
     if args.join and args.join_notes < 1:
@@ -346,14 +345,6 @@ def plan(args) -> Plan:
         check_ed_config(ed_cfg, cfg, MorphError)
         if not os.path.isfile(args.ed_ckpt):
             raise MorphError(f"ED checkpoint {args.ed_ckpt} does not exist")
-    wav = None
-    if args.wav:
-        from .. import audio
-        wav = {"fs": args.wav_fs, "voice": args.voice, "peak_db": WAV_PEAK_DB}
-        try:
-            audio.check_settings(wav["fs"], wav["voice"], wav["peak_db"], WAV_MAX_SECONDS)
-        except audio.AudioError as e:
-            raise MorphError(f"--wav: {e}") from e
     out = args.out or cfg.get("SAMPLE_DIR", "experiments/gan/samples")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
     return Plan(cfg, ed_cfg, ckpt_path, ckpt, args.ed_ckpt, mode, pairs, blend, rows, args.steps, args.samples, args.noise, out, seed,
@@ -372,50 +363,22 @@ def blend_name(k: int) -> str:
     return f"blend_{k}.mid"
 
 
-def joined_notes(rolls: Sequence[np.ndarray], styles: Sequence[Tuple[str, int]], join_notes: int):
-    """The note list of a joined path: every step's first join_notes rows decoded with the step's scale and bpm, offset by
-    morph_metrics.join_offsets."""
-    from .. import midi
-    offsets = MM.join_offsets(rolls, [bpm for _, bpm in styles], join_notes)
-    out = []
-    for roll, (scale, bpm), off in zip(rolls, styles, offsets):
-        notes, _ = midi.notes_from_roll(np.asarray(roll)[:join_notes], bpm=bpm, scale=scale, root_key=0)
-        out += [(vel, pitch, off + start, off + end) for vel, pitch, start, end in notes]
-    return out
-
-
 def write_files(p: Plan, res: MorphResult) -> List[dict]:
     """The .mid (and --wav: .wav) files of a run; returns morph.json's files[] entries."""
-    from .. import midi
-    os.makedirs(p.out, exist_ok=True)
     rows, S1 = p.rows, p.rows.S1
-    files, lists = [], []               # lists: (file entry, notes, bpm) of everything written, for --wav
+    todo = []
     for pi, (a, b, k) in enumerate(rows.paths):
         rolls = res.notes[pi * S1:(pi + 1) * S1]
         styles = [style_of(rows.weights[pi * S1 + s]) for s in range(S1)]
         for s, (roll, (scale, bpm)) in enumerate(zip(rolls, styles)):
-            name = blend_name(k) if p.mode == "blend" else step_name(a, b, k, s)
-            midi.save_piano_roll_to_midi(roll, os.path.join(p.out, name), bpm=bpm, scale=scale, root_key=0,
-                                         instrument_name="Acoustic Grand Piano")
-            f = {"file": name, "k": k, "bpm": bpm, "scale": scale}
+            f = {"file": blend_name(k) if p.mode == "blend" else step_name(a, b, k, s), "k": k, "bpm": bpm, "scale": scale}
             f.update({"weights": [float(w) for w in rows.weights[pi * S1]]} if p.mode == "blend" else
                      {"from": EMOTIONS[a], "to": EMOTIONS[b], "step": s})
-            files.append(f)
-            lists.append((f, midi.notes_from_roll(roll, bpm=bpm, scale=scale, root_key=0)[0]))
+            todo.append((f, (roll, scale, bpm)))
         if p.join is not None:
-            notes = joined_notes(rolls, styles, p.join)
-            midi.write_smf(os.path.join(p.out, join_name(a, b, k)), notes, 120.0, 0)
             f = {"file": join_name(a, b, k), "k": k, "from": EMOTIONS[a], "to": EMOTIONS[b], "joined": True, "join_notes": p.join}
-            files.append(f)
-            lists.append((f, notes))
-    if p.wav is not None:
-        from .. import audio
-        r = audio.Renderer("cuda", p.wav["fs"], p.wav["voice"], p.wav["peak_db"], WAV_MAX_SECONDS)
-        for (f, _), pcm, rep in zip(lists, r.render([n for _, n in lists]), r.report):
-            f["wav"] = f["file"][:-4] + ".wav"
-            f["seconds"], f["truncated"] = rep.seconds, rep.truncated
-            audio.write_wav(os.path.join(p.out, f["wav"]), pcm, p.wav["fs"])
-    return files
+            todo.append((f, joined_notes(rolls, styles, p.join)))
+    return pieces.write_pieces(p.out, todo, p.wav)
 
 
 def report(p: Plan, res: MorphResult, weights: str, files: List[dict]) -> dict:
@@ -436,15 +399,8 @@ def report(p: Plan, res: MorphResult, weights: str, files: List[dict]) -> dict:
     return out
 
 
-def main(argv=None) -> int:
-    args = parse_args(argv)
-    try:
-        p = plan(args)
-    except GenerateError as e:
-        print(f"morph: error: {e}", file=sys.stderr)
-        return 2
-    if not torch.cuda.is_available():
-        raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+def run(p: Plan) -> None:
+    pieces.require_device()
     m = Morpher(p.cfg, p.ed_cfg, "cuda", p.batch)
     weights = m.load_generator(p.ckpt, ema=p.ema)
     if p.ed_cfg is not None:
@@ -460,7 +416,10 @@ def main(argv=None) -> int:
         print(f"{blk['from']:>6} -> {blk['to']:<6} crossover {fmt(blk['crossover'], '.3f'):>6}  monotone {fmt(blk['monotone_fraction'], '.2f'):>5}"
               f"  switch {fmt(blk['switch_fraction'], '.2f'):>5}  roll ppl {blk['roll']['ppl']:.4g}")
     print(f"wrote {len(files)} files and morph.json to {p.out}")
-    return 0
+
+
+def main(argv=None) -> int:
+    return pieces.run_tool("morph", GenerateError, plan, run, parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -28,6 +28,8 @@ from xml.sax.saxutils import escape
 
 import numpy as np
 
+from ..pieces import require_device
+
 EMOTIONS = ("happy", "sad", "angry", "calm")        # gan/utils.py emotion_to_index; anything else is "other"
 OTHER = "other"
 COLOURS = {"happy": "#e6a817", "sad": "#3b6fb6", "angry": "#c0392b", "calm": "#2e9e6b", OTHER: "#7f7f7f"}
@@ -239,8 +241,7 @@ class Tsne:
             self.check(Xh.shape[0], Xh.shape[1])
             if not np.isfinite(Xh).all():
                 raise TsneError("Tsne: X is not finite")
-            if not torch.cuda.is_available():
-                raise RuntimeError("melo_gan_amd has no CPU path: a MI355X (ROCm) device is required")
+            require_device()
             Xd = torch.from_numpy(np.ascontiguousarray(Xh)).cuda()
         n, dev = Xd.shape[0], Xd.device
         lr = max(n / self.exaggeration / 4.0, 50.0) if self.lr == "auto" else float(self.lr)

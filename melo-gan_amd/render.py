@@ -18,7 +18,7 @@ import sys
 from dataclasses import dataclass
 from typing import List
 
-from . import audio, midi
+from . import audio, midi, pieces
 
 
 class RenderError(ValueError):
@@ -83,21 +83,15 @@ def plan(args) -> Plan:
     return Plan(list(args.files), wavs, events, args.out, args.fs, args.voice, args.peak_db, args.max_seconds)
 
 
-def main(argv=None) -> int:
-    args = parse_args(argv)
-    try:
-        p = plan(args)
-    except RenderError as e:
-        print(f"render: error: {e}", file=sys.stderr)
-        return 2
-    r = audio.Renderer("cuda", p.fs, p.voice, p.peak_db, p.max_seconds)
-    pcm = r.render(p.notes)
+def run(p: Plan) -> None:
     os.makedirs(p.out, exist_ok=True)
-    for path, wav, q, rep in zip(p.files, p.wavs, pcm, r.report):
-        audio.write_wav(wav, q, p.fs)
+    for wav, rep in zip(p.wavs, pieces.write_wavs(p.notes, p.wavs, p.fs, p.voice, p.peak_db, p.max_seconds)):
         cut = f"  truncated at {p.max_seconds:g} s" if rep.truncated else ""
         print(f"{wav}: {rep.seconds:.3f} s, {rep.notes} notes{cut}")
-    return 0
+
+
+def main(argv=None) -> int:
+    return pieces.run_tool("render", RenderError, plan, run, parse_args(argv))
 
 
 if __name__ == "__main__":
