@@ -91,7 +91,12 @@ __global__ __launch_bounds__(64 * NW) void linear_skinny_kernel(const LinP p) {
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
     };
 
-    // a wave's whole range is at most 8*UNR deep in the layers this kernel serves: issue every load first
+    // a wave's whole range is at most 16 groups of 8 deep in the layers this kernel serves (plan_ksplit stops at 128 k per
+    // wave: every split plan whose K divides, decoder.pre.2's data gradient among them): no loop, so no round of loads
+    // waits for the MFMAs of the round before.  The compiler is left to place the loads: it sinks them between the MFMAs as
+    // a rolling window (58 VGPRs), and pinning all of them above the first MFMA (sched_barrier, 156 VGPRs, one workgroup
+    // per CU) measured 17.7 us against 11.7 for pre.2's data gradient and 16.4 against 11.2 for its forward.  The MFMAs run
+    // in k order whichever case is taken: the bits do not depend on it.
     auto run = [&](auto ngroups) {
         constexpr int G = decltype(ngroups)::value;
         float4 a[G], b[G];
@@ -104,7 +109,8 @@ __global__ __launch_bounds__(64 * NW) void linear_skinny_kernel(const LinP p) {
         for (int u = 0; u < G; ++u) mma4(a[u], b[u]);
     };
     const int span = kend - kbeg;
-    if (VEC && span == 8 * 8) run(std::integral_constant<int, 8>{});
+    if (VEC && span == 8 * 16) run(std::integral_constant<int, 16>{});
+    else if (VEC && span == 8 * 8) run(std::integral_constant<int, 8>{});
     else if (VEC && span == 8 * 4) run(std::integral_constant<int, 4>{});
     else if (VEC && span == 8 * 2) run(std::integral_constant<int, 2>{});
     else if (VEC && span == 8 * 1) run(std::integral_constant<int, 1>{});
@@ -160,12 +166,24 @@ __global__ __launch_bounds__(64 * NW) void linear_skinny_kernel(const LinP p) {
     }
 }
 
+constexpr int FIN_UNR = 8;   // plan_ksplit's deepest common split (decoder.pre.2's data gradient)
+
 __global__ void linear_finish_kernel(const float* __restrict__ part, float* __restrict__ y, long mn, int N, int ksplit,
                                      const mg_epilogue e, int perm_L, int perm_C) {
     const long di = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (di >= mn) return;
+    // FIN_UNR slabs' loads in flight at a time (one after the other they cost ~0.27 us each: a thread has nothing else to
+    // do); the additions stay in z order
     float v = 0.f;
-    for (int z = 0; z < ksplit; ++z) v += part[(long)z * mn + di];
+    int z = 0;
+    for (; z + FIN_UNR <= ksplit; z += FIN_UNR) {
+        float t[FIN_UNR];
+#pragma unroll
+        for (int u = 0; u < FIN_UNR; ++u) t[u] = part[(long)(z + u) * mn + di];
+#pragma unroll
+        for (int u = 0; u < FIN_UNR; ++u) v += t[u];
+    }
+    for (; z < ksplit; ++z) v += part[(long)z * mn + di];
     int n = (int)(di % N);
     if (perm_L) n = (n % perm_C) * perm_L + n / perm_C;
     v = mg_apply_epilogue(e, v, n, di);

@@ -1348,10 +1348,18 @@ class GanEngine:
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 fn()
+        # Forked: pre.2's data gradient heads the critical path and goes out FIRST, the side branch forks behind it (its
+        # finish launch included: one library call) -- enqueued in front, the 1024-workgroup weight gradient fills the chip
+        # and the critical launch queues for slots behind work that has ~37 us of slack.  Same launches, same job lists,
+        # same bits; MELO_P2_DGRAD_FIRST=0 (read here, i.e. when the step is captured) keeps the old order for the A/B.
+        dgrad_first = side is not None and os.environ.get("MELO_P2_DGRAD_FIRST", "1") == "1"
+        if dgrad_first:
+            ops.linear_dgrad(self.d_p2, PG("decoder.pre.2.weight"), self.d_p0, gref=self.a_p0, gact=ACT_RELU)
         if p2_job is not None:
             on_side(lambda: ops.wgrad_multi([p2_job], tag="_side"))
         on_side(lambda: ops.wgrad_multi(big, tag="_side2"))
-        ops.linear_dgrad(self.d_p2, PG("decoder.pre.2.weight"), self.d_p0, gref=self.a_p0, gact=ACT_RELU)
+        if not dgrad_first:
+            ops.linear_dgrad(self.d_p2, PG("decoder.pre.2.weight"), self.d_p0, gref=self.a_p0, gact=ACT_RELU)
         jobs.append(ops.linear_wgrad(self.lat, self.d_p0, GG("decoder.pre.0.weight"), db=GG("decoder.pre.0.bias"), defer=True))
         jobs.append(ops.linear_wgrad(self.a_n0, self.d_lat, GG("noise_to_latent.net.2.weight"),
                                      db=GG("noise_to_latent.net.2.bias"), defer=True))
