@@ -646,6 +646,43 @@ int mg_latent_rows(const float* mu, const float* logvar, int n_src, const float*
 int mg_latent_cycle(const float* z, const float* mu2, const float* mu, int n_src, const float* dirs, int n_dir, const int32_t* kind,
                     const int32_t* src_a, const int32_t* dir, int rows, int L, double* out, mg_stream_t stream);
 
+/* ---- MIDI events into note rolls; the classifier's verdicts per window and per file (melo_gan_amd.midi_import,
+ *      melo_gan_amd.emotion_discriminator.predict; csrc/roll_encode.hip, csrc/note_decode.h) ----
+ * An event is four int32 (pitch, velocity, dur_q, step_q), durations and steps in 1/64 beat; a velocity below 0 marks a rest.
+ * note_encode (csrc/note_decode.h, beside the decode it inverts) takes an event to one position of a roll, fp32, every
+ * operation rounded on its own:
+ *     p = clamp(pitch, 36, 96)       x0 = (p + 0.5) / 63.5 - 1
+ *     v = clamp(velocity, 60, 127)   x1 = ((v + 0.5 - 60) / 67) * 1.2 + (-0.2f), and 1.0 for v = 127
+ *     d = clamp(dur_q, 16, 256)      x2 = d / 128 - 1
+ *     s = clamp(step_q, 0, 256)      x3 = s / 128 - 1                           a rest: (-1, -1, -1, x3)
+ *   The generator's output contract (mg_note_stats' decode, midi.notes_from_roll) takes (x0 .. x3) back to (p, v, d / 64 beats,
+ *   s / 64 beats, or 0.1 beat for s < 7): on pitches 36..96, velocities 60..127, durations 16..256 and steps 7..256 the encode
+ *   is the decode's exact inverse.
+ * mg_roll_encode: one batch x (rows, T, 4) of windows of `events` (n_events, 4).  Batch row r is window
+ *     w = (counter[0] - base[0]) * rows + r            (mg_scatter_rows_cursor's rule; the launch does not advance the cursor)
+ *   of the W windows win_start (int64), win_len (int32): position i < win_len[w] = note_encode(events[win_start[w] + i]);
+ *   positions i >= win_len[w], and every position of a row with w >= W, hold the padding row (-1, -1, -1, -1).
+ *   loss[w, 0:8] (int64, written for w < dst_rows; zeros for w >= W) counts over the window's events: pitch raised, pitch
+ *   lowered, velocity raised, duration lengthened, duration shortened, steps in 1..6, steps of 0 (both decode as 0.1 beat),
+ *   rests.  The descriptors lie on the device, so the entry point cannot see them: a window with win_start < 0, win_len outside
+ *   [0, T] or win_start + win_len > n_events reads nothing of `events`; its row is NaN and its counts are -1.
+ *   One 64-lane workgroup per row, one 16-byte load and one 16-byte store per position, the counts summed per lane and by a
+ *   fixed butterfly.  events and x 16-byte aligned; rows 1..65535; T 1..2^20.
+ * mg_window_votes: logits (W, K) fp32 of W windows that belong to F files, file f owning the windows file_off[f] ..
+ *   file_off[f + 1] - 1 (int64, F + 1 entries):
+ *     probs (W, K) fp64       mg_path_probs' softmax (one device function under both)
+ *     win_pred (W) int32      the first index of the largest logit, NaN counting as the largest (mg_emotion_score's rule)
+ *     file_mean (F, K) fp64   the sum of the file's probs in window order over their number, one lane per word
+ *     file_pred (F) int32     the first index of the largest mean, by the same rule
+ *     switches (F) int32      the file's windows whose win_pred differs from the window's before it
+ *   A file without windows gets zeros, -1 and 0; a file whose offsets leave [0, W] or run backwards reads nothing: NaN, -1, -1.
+ *   K 2..32; W >= 0; F >= 1.
+ * Both: no atomics; capturable; eager runs, reruns and graph replays leave identical bits. */
+int mg_roll_encode(const int32_t* events, long n_events, const int64_t* win_start, const int32_t* win_len, long W, int T, int rows,
+                   float* x, int64_t* loss, long dst_rows, const uint64_t* counter, const uint64_t* base, mg_stream_t stream);
+int mg_window_votes(const float* logits, const int64_t* file_off, int F, int n_classes, long W, double* probs, int32_t* win_pred,
+                    double* file_mean, int32_t* file_pred, int32_t* switches, mg_stream_t stream);
+
 /* ---- rendering note lists to audio (csrc/render.hip; melo_gan_amd.audio, melo_gan_amd.render, generate --wav) ----
  * The reference stops at the .mid file; hearing one takes a synthesiser from outside.  mg_render_notes is an additive
  * synthesiser with an integer phase accumulator: F files in ONE launch, a lane per output sample.

@@ -13,8 +13,8 @@
 
 train_ae, ae.encode and ae.evaluate only ever run the decoder on what the encoder has just produced.  Here the decoder's input is
 written by mg_latent_rows: z = base + alpha * direction + sigma * std * N(0, I) per output row (ae/latent_edit.py builds the row
-descriptors).  ROWS are comma-separated row indices of the split's notes.npy; other .mid files cannot be sources, because the roll
-contract has no faithful inverse.  --prior samples z ~ temperature * N(0, I); --vary draws around each piece's posterior mean;
+descriptors).  ROWS are comma-separated row indices of the split's notes.npy; other .mid files become such rows through
+melo_gan_amd.midi_import, which reports what of a file the roll contract cannot hold.  --prior samples z ~ temperature * N(0, I); --vary draws around each piece's posterior mean;
 --from / --to walks between two pieces' means; --shift moves a piece along (mean latent of the target emotion) - (mean latent of
 its own emotion), both taken from one VaeEvaluator pass over the --centroids split (default: train), so that strength 1 carries
 the source class mean onto the target's.  --shift needs labels: <split dir>/emotion.npy or --labels.

@@ -4,6 +4,7 @@
 // is in include/melo_gan_hip.h (mg_path_d2, mg_path_probs); the host restatement is melo_gan_amd/gan/morph_metrics.py.
 // No atomics: every output word has one writer and a fixed summation order.
 #include "common.h"
+#include "softmax64.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -43,28 +44,13 @@ __global__ __launch_bounds__(PM_THREADS) void path_d2_kernel(const float* __rest
     if (u == 0) out[row] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
 }
 
-// One lane per row: the fp64 softmax of the row's fp32 logits by mg_cls_eval_acc's rule -- the maximum (the lowest index on
-// ties) is taken out and its own term, exp(0) = 1, is not computed; the other terms are added in class order.
+// One lane per row: the fp64 softmax of the row's fp32 logits by mg_cls_eval_acc's rule (softmax64.h).
 __global__ __launch_bounds__(PM_THREADS) void path_softmax_kernel(const float* __restrict__ logits, long rows, int K,
                                                                   double* __restrict__ probs) {
 #pragma clang fp contract(off)
     const long row = (long)blockIdx.x * PM_THREADS + threadIdx.x;
     if (row >= rows) return;
-    const float* z = logits + row * K;
-    double* p = probs + row * K;
-    int pred = 0;
-    for (int k = 1; k < K; ++k)
-        if (z[k] > z[pred]) pred = k;
-    const double m = (double)z[pred];
-    double rest = 0.0;
-    for (int k = 0; k < K; ++k)
-        if (k != pred) {
-            const double e = exp((double)z[k] - m);
-            p[k] = e;
-            rest = rest + e;
-        }
-    const double sum = 1.0 + rest;
-    for (int k = 0; k < K; ++k) p[k] = k == pred ? 1.0 / sum : p[k] / sum;
+    softmax64_row(logits + row * K, K, probs + row * K);
 }
 
 // One lane per accumulator word (g, s, k): the sum of probs[p, s, k] over the paths p = 0 .. P-1 of group g, in that order; the

@@ -1799,6 +1799,65 @@ def latent_cycle(z, mu2, mu, dirs, kind, src_a, dir, out=None):
     return out
 
 
+ROLL_LOSS_WORDS = 8
+VOTES_MAX_CLASSES = 32
+
+
+def roll_encode(events, win_start, win_len, x, loss, counter, base):
+    """One batch of windows of an event list as note rolls (mg_roll_encode): events (E, 4) int32 rows (pitch, velocity, dur_q,
+    step_q), win_start (W,) int64, win_len (W,) int32 -> x (B, T, 4) fp32, batch row r being window (counter - base) * B + r
+    (the padding row past a window's length and past W), and loss (dst_rows, 8) int64, the window's clamp counts.  counter /
+    base: int64 device scalars (1,); the launch does not advance them.  The windows stay on the device; one that points
+    outside events comes back as NaN."""
+    _chk(events, "roll_encode: events", dtype=torch.int32)
+    if events.dim() != 2 or events.shape[1] != 4:
+        raise ValueError(f"roll_encode: events (E, 4) expected, got {tuple(events.shape)}")
+    _chk(win_start, "roll_encode: win_start", dtype=torch.int64)
+    if win_start.dim() != 1 or win_start.shape[0] < 1:
+        raise ValueError(f"roll_encode: win_start (W >= 1,) expected, got {tuple(win_start.shape)}")
+    W = win_start.shape[0]
+    _chk(win_len, "roll_encode: win_len", (W,), torch.int32)
+    _chk(x, "roll_encode: x")
+    if x.dim() != 3 or x.shape[2] != 4 or not 1 <= x.shape[0] <= 65535 or not 1 <= x.shape[1] <= (1 << 20):
+        raise ValueError(f"roll_encode: x (B in 1..65535, T in 1..2^20, 4) expected, got {tuple(x.shape)}")
+    _chk(loss, "roll_encode: loss", dtype=torch.int64)
+    if loss.dim() != 2 or loss.shape[0] < 1 or loss.shape[1] != ROLL_LOSS_WORDS:
+        raise ValueError(f"roll_encode: loss (dst_rows >= 1, {ROLL_LOSS_WORDS}) expected, got {tuple(loss.shape)}")
+    if events.data_ptr() % 16 or x.data_ptr() % 16:
+        raise ValueError("roll_encode: events and x must be 16-byte aligned")
+    _cursor_scalars(counter, base)
+    L.check(L.load().mg_roll_encode(_p(events), events.shape[0], _p(win_start), _p(win_len), W, x.shape[1], x.shape[0], _p(x),
+                                    _p(loss), loss.shape[0], _p(counter), _p(base), _stream()), "mg_roll_encode")
+    return x
+
+
+def window_votes(logits, file_off, probs=None, win_pred=None, file_mean=None, file_pred=None, switches=None):
+    """The classifier's verdicts per window and per file (mg_window_votes): logits (W, K) fp32, file_off (F + 1,) int64 ->
+    probs (W, K) fp64, win_pred (W,) int32, file_mean (F, K) fp64, file_pred (F,) int32, switches (F,) int32, returned in
+    this order."""
+    _chk(logits, "window_votes: logits")
+    if logits.dim() != 2 or not 2 <= logits.shape[1] <= VOTES_MAX_CLASSES:
+        raise ValueError(f"window_votes: logits (W, K in 2..{VOTES_MAX_CLASSES}) expected, got {tuple(logits.shape)}")
+    W, K = logits.shape
+    _chk(file_off, "window_votes: file_off", dtype=torch.int64)
+    if file_off.dim() != 1 or file_off.shape[0] < 2:
+        raise ValueError(f"window_votes: file_off (F + 1 >= 2,) expected, got {tuple(file_off.shape)}")
+    F, d = file_off.shape[0] - 1, logits.device
+    probs = torch.empty(W, K, dtype=torch.float64, device=d) if probs is None else probs
+    win_pred = torch.empty(W, dtype=torch.int32, device=d) if win_pred is None else win_pred
+    file_mean = torch.empty(F, K, dtype=torch.float64, device=d) if file_mean is None else file_mean
+    file_pred = torch.empty(F, dtype=torch.int32, device=d) if file_pred is None else file_pred
+    switches = torch.empty(F, dtype=torch.int32, device=d) if switches is None else switches
+    _chk(probs, "window_votes: probs", (W, K), torch.float64)
+    _chk(win_pred, "window_votes: win_pred", (W,), torch.int32)
+    _chk(file_mean, "window_votes: file_mean", (F, K), torch.float64)
+    _chk(file_pred, "window_votes: file_pred", (F,), torch.int32)
+    _chk(switches, "window_votes: switches", (F,), torch.int32)
+    L.check(L.load().mg_window_votes(_p(logits), _p(file_off), F, K, W, _p(probs), _p(win_pred), _p(file_mean), _p(file_pred),
+                                     _p(switches), _stream()), "mg_window_votes")
+    return probs, win_pred, file_mean, file_pred, switches
+
+
 def voice_struct(mult, weight, decay, attack: int, release_tau: float, release_len: int, fs: float) -> L.Voice:
     """mg_voice from a partial table (equally long sequences of multipliers, weights and decay rates in 1/s) and the envelope:
     attack and release_len in samples, release_tau in seconds.  Only the table's length is checked here; the values are
