@@ -683,6 +683,49 @@ int mg_roll_encode(const int32_t* events, long n_events, const int64_t* win_star
 int mg_window_votes(const float* logits, const int64_t* file_off, int F, int n_classes, long W, double* probs, int32_t* win_pred,
                     double* file_mean, int32_t* file_pred, int32_t* switches, mg_stream_t stream);
 
+/* ---- integrated gradients of the frozen emotion classifier, per note (melo_gan_amd.emotion_discriminator.explain;
+ *      csrc/explain.hip) ----
+ * X (W, T, 4) fp32 holds W resident windows, win_len (W) int32 their lengths; the baseline b is the silent roll, every value
+ * -1 (mg_roll_encode's padding row).  A batch of B rows holds G = B / R windows of R consecutive rows each; batch row r
+ * belongs to window
+ *     w = (counter[0] - base[0]) * G + r / R           (mg_scatter_rows_cursor's rule with G for the batch; no launch
+ *                                                       advances the cursor)
+ * and has no window when r >= G * R or w >= W.
+ * mg_ig_rows: out (B, T, 4) fp32.  A row without a window is b.
+ *     MG_IG_PATH    (R = S steps):  b + alpha (x_w - b) with alpha = ((r % R) + 0.5) / R, evaluated in fp64 from the widened
+ *                   fp32 input, every operation rounded on its own, ONE rounding to fp32 at the store: a value equal to b
+ *                   stays b bit for bit.  win_len, rank and n_del are not read (may be NULL; D is ignored).
+ *     MG_IG_DELETE  (R = 2 D, n_del (D) int32, rank (W, T) int32 as mg_ig_rank leaves it):  x_w, with the positions
+ *                   t < win_len[w] whose rank is >= 0 and  < n_del[j]               for row j = r % R < D      (the strongest
+ *                   supporters), or                       >= win_len[w] - n_del[j - D]  for row j >= D         (the strongest
+ *                   opponents) replaced by b.
+ * mg_ig_seed: logits (B, K) fp32 of the batch, target (W) int32 -> dlogits (B, K) fp32, dlogits[r, j] = (j == target[w]) -
+ *   p[j] with p the fp64 softmax mg_window_votes reports (one device function under both), rounded once; logp (B) fp64 =
+ *   (z[k] - max) - log(1 + the other classes' terms in class order).  A row without a window gets zeros; a target outside
+ *   [0, K) gives NaN.  K 2..32.
+ * mg_ig_accumulate: dnotes (B, T, 4) fp32, the classifier's input gradients of a MG_IG_PATH batch -> for each of the batch's
+ *   windows w < W, all fp64:
+ *     attr[w, t, c] = (x - b) * (sum over the window's R rows, in row order, of dnotes / R);  exactly 0 where x = b
+ *     note[w, t]    = ((attr[w,t,0] + attr[w,t,1]) + attr[w,t,2]) + attr[w,t,3]
+ *     sums[w, 0:5]  = the sum over t of note, then of attr[.., c] for c = 0..3: thread u of 256 adds its positions u,
+ *                     u + 256, .. in order, then a fixed butterfly over each wave, then the four waves in order
+ *   Windows >= W are not written.  One workgroup per window; one 16-byte load per gradient position.
+ * mg_ig_rank: rank (W, T) int32 of note (W, T) fp64 within each window: for t < win_len[w] the number of u < win_len[w]
+ *   with note[u] > note[t], or note[u] == note[t] and u < t (descending, ties to the lower position: a permutation of
+ *   0 .. win_len - 1); -1 for t >= win_len[w].  Counted over tiles of mg_ig_rank_tile() values held in LDS.  A window with a
+ *   NaN among its real events, or a length outside [0, T], gets -1 everywhere.
+ * All: T 1..4096; B 1..65535 (mg_ig_seed: 2^24); X, out and dnotes 16-byte, attr 32-byte aligned; no atomics; capturable;
+ *   eager runs, reruns and graph replays leave identical bits. */
+enum { MG_IG_PATH = 0, MG_IG_DELETE = 1 };
+int mg_ig_rows(const float* X, const int32_t* win_len, const int32_t* rank, const int32_t* n_del, int D, long W, int T, int B, int R,
+               int mode, float* out, const uint64_t* counter, const uint64_t* base, mg_stream_t stream);
+int mg_ig_seed(const float* logits, const int32_t* target, long W, int B, int n_classes, int R, float* dlogits, double* logp,
+               const uint64_t* counter, const uint64_t* base, mg_stream_t stream);
+int mg_ig_accumulate(const float* dnotes, const float* X, long W, int T, int B, int R, double* attr, double* note, double* sums,
+                     const uint64_t* counter, const uint64_t* base, mg_stream_t stream);
+int mg_ig_rank(const double* note, const int32_t* win_len, long W, int T, int32_t* rank, mg_stream_t stream);
+int mg_ig_rank_tile(void);
+
 /* ---- rendering note lists to audio (csrc/render.hip; melo_gan_amd.audio, melo_gan_amd.render, generate --wav) ----
  * The reference stops at the .mid file; hearing one takes a synthesiser from outside.  mg_render_notes is an additive
  * synthesiser with an integer phase accumulator: F files in ONE launch, a lane per output sample.

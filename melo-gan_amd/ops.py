@@ -1858,6 +1858,119 @@ def window_votes(logits, file_off, probs=None, win_pred=None, file_mean=None, fi
     return probs, win_pred, file_mean, file_pred, switches
 
 
+IG_PATH, IG_DELETE = 0, 1
+IG_MAX_T, IG_MAX_CLASSES, IG_SUMS = 4096, 32, 5
+
+
+def ig_rank_tile() -> int:
+    """The values of `note` that mg_ig_rank holds in LDS at a time."""
+    return int(L.load().mg_ig_rank_tile())
+
+
+def _ig_windows(who, X, win_len=None):
+    """The resident windows X (W >= 1, T in 1..4096, 4) fp32, 16-byte aligned, and their lengths: returns (W, T)."""
+    _chk(X, f"{who}: X")
+    if X.dim() != 3 or X.shape[2] != 4 or X.shape[0] < 1 or not 1 <= X.shape[1] <= IG_MAX_T:
+        raise ValueError(f"{who}: X (W >= 1, T in 1..{IG_MAX_T}, 4) expected, got {tuple(X.shape)}")
+    if X.data_ptr() % 16:
+        raise ValueError(f"{who}: X must be 16-byte aligned")
+    if win_len is not None:
+        _chk(win_len, f"{who}: win_len", (X.shape[0],), torch.int32)
+    return X.shape[0], X.shape[1]
+
+
+def _ig_batch(who, rows, T, R, name):
+    """A batch (B in 1..65535, T, 4) fp32, 16-byte aligned, of R rows per window: returns B."""
+    _chk(rows, f"{who}: {name}")
+    if rows.dim() != 3 or tuple(rows.shape[1:]) != (T, 4) or not 1 <= rows.shape[0] <= 65535:
+        raise ValueError(f"{who}: {name} (B in 1..65535, {T}, 4) expected, got {tuple(rows.shape)}")
+    if rows.data_ptr() % 16:
+        raise ValueError(f"{who}: {name} must be 16-byte aligned")
+    if not 1 <= int(R) <= rows.shape[0]:
+        raise ValueError(f"{who}: rows_per_window = {R}: 1..{rows.shape[0]}, the batch")
+    return rows.shape[0]
+
+
+def ig_rows(X, out, rows_per_window: int, counter, base, mode=IG_PATH, win_len=None, rank=None, n_del=None):
+    """One batch of path or deletion rows of the resident windows X (W, T, 4) (mg_ig_rows): out (B, T, 4), batch row r
+    belonging to window (counter - base) * (B // R) + r // R.  IG_PATH (R steps): -1 + ((r % R) + 0.5) / R * (x + 1).
+    IG_DELETE (R = 2 D; win_len (W,), rank (W, T) int32, n_del (D,) int32): x with its n_del[j] strongest supporters (rows
+    j < D) or opponents (rows j >= D) replaced by -1.  Rows without a window are -1."""
+    W, T = _ig_windows("ig_rows", X, win_len)
+    R = int(rows_per_window)
+    B = _ig_batch("ig_rows", out, T, R, "out")
+    if mode not in (IG_PATH, IG_DELETE):
+        raise ValueError(f"ig_rows: mode = {mode}: IG_PATH or IG_DELETE")
+    D = 0
+    if mode == IG_DELETE:
+        if win_len is None or rank is None or n_del is None:
+            raise ValueError("ig_rows: deletion rows need win_len, rank and n_del")
+        _chk(rank, "ig_rows: rank", (W, T), torch.int32)
+        _chk(n_del, "ig_rows: n_del", dtype=torch.int32)
+        D = n_del.numel()
+        if n_del.dim() != 1 or D < 1 or R != 2 * D:
+            raise ValueError(f"ig_rows: rows_per_window = {R} with n_del {tuple(n_del.shape)}: two rows per count")
+    else:
+        win_len = rank = n_del = None
+    _cursor_scalars(counter, base)
+    L.check(L.load().mg_ig_rows(_p(X), _p(win_len), _p(rank), _p(n_del), D, W, T, B, R, mode, _p(out), _p(counter), _p(base),
+                                _stream()), "mg_ig_rows")
+    return out
+
+
+def ig_seed(logits, target, rows_per_window: int, dlogits, logp, counter, base):
+    """The seed of the classifier's backward pass (mg_ig_seed): logits (B, K) fp32 of a batch of R rows per window, target
+    (W,) int32 -> dlogits (B, K) fp32 = onehot(target) - softmax, logp (B,) fp64 = log softmax at the target; zeros for a
+    row without a window."""
+    _chk(logits, "ig_seed: logits")
+    if logits.dim() != 2 or not 2 <= logits.shape[1] <= IG_MAX_CLASSES or not 1 <= logits.shape[0] <= (1 << 24):
+        raise ValueError(f"ig_seed: logits (B in 1..2^24, K in 2..{IG_MAX_CLASSES}) expected, got {tuple(logits.shape)}")
+    B, K = logits.shape
+    _chk(target, "ig_seed: target", dtype=torch.int32)
+    if target.dim() != 1 or target.shape[0] < 1:
+        raise ValueError(f"ig_seed: target (W >= 1,) expected, got {tuple(target.shape)}")
+    if not 1 <= int(rows_per_window) <= B:
+        raise ValueError(f"ig_seed: rows_per_window = {rows_per_window}: 1..{B}, the batch")
+    _chk(dlogits, "ig_seed: dlogits", (B, K))
+    _chk(logp, "ig_seed: logp", (B,), torch.float64)
+    _cursor_scalars(counter, base)
+    L.check(L.load().mg_ig_seed(_p(logits), _p(target), target.shape[0], B, K, int(rows_per_window), _p(dlogits), _p(logp),
+                                _p(counter), _p(base), _stream()), "mg_ig_seed")
+    return dlogits, logp
+
+
+def ig_accumulate(dnotes, X, rows_per_window: int, attr, note, sums, counter, base):
+    """The path's gradients reduced per window (mg_ig_accumulate): dnotes (B, T, 4) fp32 of a batch of R path rows per window
+    and the resident windows X (W, T, 4) -> attr (W, T, 4), note (W, T), sums (W, 5) = total and the four channel sums, all
+    fp64, written for the batch's windows only."""
+    W, T = _ig_windows("ig_accumulate", X)
+    _ig_batch("ig_accumulate", dnotes, T, rows_per_window, "dnotes")
+    _chk(attr, "ig_accumulate: attr", (W, T, 4), torch.float64)
+    _chk(note, "ig_accumulate: note", (W, T), torch.float64)
+    _chk(sums, "ig_accumulate: sums", (W, IG_SUMS), torch.float64)
+    if attr.data_ptr() % 32:
+        raise ValueError("ig_accumulate: attr must be 32-byte aligned")
+    _cursor_scalars(counter, base)
+    L.check(L.load().mg_ig_accumulate(_p(dnotes), _p(X), W, T, dnotes.shape[0], int(rows_per_window), _p(attr), _p(note), _p(sums),
+                                      _p(counter), _p(base), _stream()), "mg_ig_accumulate")
+    return attr, note, sums
+
+
+def ig_rank(note, win_len, rank=None):
+    """The notes of every window ranked by attribution (mg_ig_rank): note (W, T) fp64, win_len (W,) int32 -> rank (W, T)
+    int32, descending, ties to the lower position, -1 past the window's length and everywhere in a window that holds a NaN."""
+    _chk(note, "ig_rank: note", dtype=torch.float64)
+    if note.dim() != 2 or note.shape[0] < 1 or not 1 <= note.shape[1] <= IG_MAX_T:
+        raise ValueError(f"ig_rank: note (W >= 1, T in 1..{IG_MAX_T}) expected, got {tuple(note.shape)}")
+    W, T = note.shape
+    _chk(win_len, "ig_rank: win_len", (W,), torch.int32)
+    if rank is None:
+        rank = torch.empty(W, T, dtype=torch.int32, device=note.device)
+    _chk(rank, "ig_rank: rank", (W, T), torch.int32)
+    L.check(L.load().mg_ig_rank(_p(note), _p(win_len), W, T, _p(rank), _stream()), "mg_ig_rank")
+    return rank
+
+
 def voice_struct(mult, weight, decay, attack: int, release_tau: float, release_len: int, fs: float) -> L.Voice:
     """mg_voice from a partial table (equally long sequences of multipliers, weights and decay rates in 1/s) and the envelope:
     attack and release_len in samples, release_tau in seconds.  Only the table's length is checked here; the values are
