@@ -726,6 +726,38 @@ int mg_ig_accumulate(const float* dnotes, const float* X, long W, int T, int B, 
 int mg_ig_rank(const double* note, const int32_t* win_len, long W, int T, int32_t* rank, mg_stream_t stream);
 int mg_ig_rank_tile(void);
 
+/* ---- shared motifs between note rolls, transposition-invariant (melo_gan_amd.motifs; csrc/motif.hip) ----
+ * Tokens.  A row (T, 4) fp32 is decoded position by position by the generator's output contract (csrc/note_decode.h, the
+ * decode of mg_note_stats).  A position with a non-finite value is skipped and takes no time; every other one, note or rest,
+ * takes ticks = (int)floor(step_beats * 64.0 + 0.5), in fp64.  With the row's sounding notes n_0 .. n_{M-1} in order, the row
+ * has max(M - 1, 0) tokens; token k - 1 (1 <= k < M) is
+ *     interval = pitch_k - pitch_{k-1}                                  -60..60
+ *     ioi      = the ticks of the positions from n_{k-1}'s up to the one in front of n_k's (rests between them count)
+ *     rhythm   = (ioi >= 12) + (ioi >= 24) + (ioi >= 48) + (ioi >= 96) + (ioi >= 192), and 0 in mode MG_MOTIF_INTERVAL
+ *     token    = (interval + 64) | (rhythm << 7)
+ * mg_motif_tokens: rolls (N, T, 4) -> tokens (N, T) uint16, 0xFFFF from the row's length on, and lengths (N) int32.  One
+ *   workgroup per row, chunks of 256 positions.  Every element of both outputs is written.
+ * Matching.  For token rows a (Mq tokens) and b (Mc tokens), run(i, j) = run(i - 1, j - 1) + 1 where a[i] == b[j], else 0;
+ * nothing carries across the start of either row.  L = the largest run, (i_end, j_end) the cell that attains it with the
+ * smallest i, then the smallest j.
+ * mg_motif_lcs: q_tokens (Nq, T), q_len (Nq), c_tokens (Nc, T), c_len (Nc) ->
+ *     packed (Nq, Nc) int64   (L << 32) | ((0xFFFF - i_end) << 16) | (0xFFFF - j_end), and 0 for L = 0: larger is better
+ *     reach (Nq, T) int32     reach[q, i] = the largest run(i, .) over the corpus rows that are not skipped; 0 from q_len[q] on
+ *   q_groups (Nq) / c_groups (Nc) int32, both or neither: a pair with equal group ids is skipped, packed 0, nothing in reach.
+ *   Lengths outside [0, T] are clamped into it; tokens from a row's length on are not read.  reach is cleared by the entry
+ *   point, collected by integer atomic maxima over workgroups of mg_motif_corpus_tile() corpus rows and finished in place by
+ *   a second launch; every element of both outputs is written.  Nq 1..65535.
+ * mg_motif_rank: packed (Nq, Nc), non-negative -> vals (Nq, k) int64 and idx (Nq, k) int32: the k largest values of each row in
+ *   descending order with their columns, equal values by ascending column; value 0 and column -1 from Nc on.  k 1..1024.
+ * All: T 1..4096; the token buffers 2-byte, int32 buffers 4-byte, int64 buffers 8-byte, rolls 16-byte aligned; integer
+ *   arithmetic throughout, so eager runs, reruns and graph replays leave identical bits; capturable. */
+enum { MG_MOTIF_INTERVAL_RHYTHM = 0, MG_MOTIF_INTERVAL = 1 };
+int mg_motif_tokens(const float* rolls, long N, int T, int mode, uint16_t* tokens, int32_t* lengths, mg_stream_t stream);
+int mg_motif_lcs(const uint16_t* q_tokens, const int32_t* q_len, int Nq, const uint16_t* c_tokens, const int32_t* c_len, long Nc,
+                 int T, const int32_t* q_groups, const int32_t* c_groups, int64_t* packed, int32_t* reach, mg_stream_t stream);
+int mg_motif_rank(const int64_t* packed, int Nq, long Nc, int k, int64_t* vals, int32_t* idx, mg_stream_t stream);
+int mg_motif_corpus_tile(void);
+
 /* ---- rendering note lists to audio (csrc/render.hip; melo_gan_amd.audio, melo_gan_amd.render, generate --wav) ----
  * The reference stops at the .mid file; hearing one takes a synthesiser from outside.  mg_render_notes is an additive
  * synthesiser with an integer phase accumulator: F files in ONE launch, a lane per output sample.

@@ -179,6 +179,10 @@ SIGNATURES = {
     "mg_ig_accumulate": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mg_ig_rank": (i32, [vp, vp, i64, i32, vp, vp]),
     "mg_ig_rank_tile": (i32, []),
+    "mg_motif_tokens": (i32, [vp, i64, i32, i32, vp, vp, vp]),
+    "mg_motif_lcs": (i32, [vp, vp, i32, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
+    "mg_motif_rank": (i32, [vp, i32, i64, i32, vp, vp, vp]),
+    "mg_motif_corpus_tile": (i32, []),
     "mg_render_notes": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, C.POINTER(Voice), vp, vp, vp]),
     "mg_pcm_peak": (i32, [vp, vp, i32, i64, vp, vp]),
     "mg_pcm_quantise": (i32, [vp, vp, vp, i32, i64, f32, vp, vp]),

@@ -1971,6 +1971,76 @@ def ig_rank(note, win_len, rank=None):
     return rank
 
 
+MOTIF_INTERVAL_RHYTHM, MOTIF_INTERVAL = 0, 1
+MOTIF_MAX_T, MOTIF_MAX_QUERIES, MOTIF_MAX_K, MOTIF_PAD = 4096, 65535, 1024, 0xFFFF
+
+
+def motif_corpus_tile() -> int:
+    return int(L.load().mg_motif_corpus_tile())
+
+
+def motif_tokens(rolls, mode: int, tokens=None, lengths=None):
+    """Interval (+ rhythm class) tokens of note rolls (mg_motif_tokens): rolls (N, T, 4) fp32 -> tokens (N, T) uint16, 0xFFFF
+    from a row's length on, and lengths (N,) int32, returned in this order."""
+    _chk(rolls, "motif_tokens: rolls")
+    if rolls.dim() != 3 or rolls.shape[2] != 4 or rolls.shape[0] < 1 or not 1 <= rolls.shape[1] <= MOTIF_MAX_T:
+        raise ValueError(f"motif_tokens: rolls (N >= 1, T in 1..{MOTIF_MAX_T}, 4) expected, got {tuple(rolls.shape)}")
+    if mode not in (MOTIF_INTERVAL_RHYTHM, MOTIF_INTERVAL):
+        raise ValueError(f"motif_tokens: mode = {mode}: MOTIF_INTERVAL_RHYTHM or MOTIF_INTERVAL")
+    N, T = rolls.shape[0], rolls.shape[1]
+    tokens = torch.empty(N, T, dtype=torch.uint16, device=rolls.device) if tokens is None else tokens
+    lengths = torch.empty(N, dtype=torch.int32, device=rolls.device) if lengths is None else lengths
+    _chk(tokens, "motif_tokens: tokens", (N, T), torch.uint16)
+    _chk(lengths, "motif_tokens: lengths", (N,), torch.int32)
+    if rolls.data_ptr() % 16:
+        raise ValueError("motif_tokens: rolls must be 16-byte aligned")
+    L.check(L.load().mg_motif_tokens(_p(rolls), N, T, int(mode), _p(tokens), _p(lengths), _stream()), "mg_motif_tokens")
+    return tokens, lengths
+
+
+def motif_lcs(q_tokens, q_len, c_tokens, c_len, q_groups=None, c_groups=None, packed=None, reach=None):
+    """The longest common run of every (query, corpus) pair of token rows and, per query position, the longest run that reaches
+    it (mg_motif_lcs): q_tokens (Nq, T) / c_tokens (Nc, T) uint16, q_len (Nq,) / c_len (Nc,) int32, optional group ids int32
+    (a pair with equal ids is skipped) -> packed (Nq, Nc) int64 and reach (Nq, T) int32, returned in this order."""
+    _chk(q_tokens, "motif_lcs: q_tokens", dtype=torch.uint16)
+    _chk(c_tokens, "motif_lcs: c_tokens", dtype=torch.uint16)
+    if q_tokens.dim() != 2 or c_tokens.dim() != 2 or q_tokens.shape[1] != c_tokens.shape[1]:
+        raise ValueError(f"motif_lcs: q_tokens (Nq, T) and c_tokens (Nc, T) expected, got {tuple(q_tokens.shape)} and "
+                         f"{tuple(c_tokens.shape)}")
+    (Nq, T), Nc = q_tokens.shape, c_tokens.shape[0]
+    if not 1 <= Nq <= MOTIF_MAX_QUERIES or Nc < 1 or not 1 <= T <= MOTIF_MAX_T:
+        raise ValueError(f"motif_lcs: Nq = {Nq}, Nc = {Nc}, T = {T}: Nq in 1..{MOTIF_MAX_QUERIES}, Nc >= 1, T in 1..{MOTIF_MAX_T}")
+    _chk(q_len, "motif_lcs: q_len", (Nq,), torch.int32)
+    _chk(c_len, "motif_lcs: c_len", (Nc,), torch.int32)
+    if (q_groups is None) != (c_groups is None):
+        raise ValueError("motif_lcs: q_groups and c_groups go together")
+    if q_groups is not None:
+        _chk(q_groups, "motif_lcs: q_groups", (Nq,), torch.int32)
+        _chk(c_groups, "motif_lcs: c_groups", (Nc,), torch.int32)
+    packed = torch.empty(Nq, Nc, dtype=torch.int64, device=q_tokens.device) if packed is None else packed
+    reach = torch.empty(Nq, T, dtype=torch.int32, device=q_tokens.device) if reach is None else reach
+    _chk(packed, "motif_lcs: packed", (Nq, Nc), torch.int64)
+    _chk(reach, "motif_lcs: reach", (Nq, T), torch.int32)
+    L.check(L.load().mg_motif_lcs(_p(q_tokens), _p(q_len), Nq, _p(c_tokens), _p(c_len), Nc, T, _p(q_groups), _p(c_groups),
+                                  _p(packed), _p(reach), _stream()), "mg_motif_lcs")
+    return packed, reach
+
+
+def motif_rank(packed, k: int, vals=None, idx=None):
+    """Every query's k best corpus rows (mg_motif_rank): packed (Nq, Nc) int64, non-negative -> vals (Nq, k) int64 descending
+    and idx (Nq, k) int32, equal values by ascending column; value 0 and column -1 from Nc on."""
+    _chk(packed, "motif_rank: packed", dtype=torch.int64)
+    if packed.dim() != 2 or packed.shape[0] < 1 or packed.shape[1] < 1 or not 1 <= int(k) <= MOTIF_MAX_K:
+        raise ValueError(f"motif_rank: packed (Nq >= 1, Nc >= 1) and k in 1..{MOTIF_MAX_K} expected, got {tuple(packed.shape)}, k = {k}")
+    Nq, Nc = packed.shape
+    vals = torch.empty(Nq, k, dtype=torch.int64, device=packed.device) if vals is None else vals
+    idx = torch.empty(Nq, k, dtype=torch.int32, device=packed.device) if idx is None else idx
+    _chk(vals, "motif_rank: vals", (Nq, k), torch.int64)
+    _chk(idx, "motif_rank: idx", (Nq, k), torch.int32)
+    L.check(L.load().mg_motif_rank(_p(packed), Nq, Nc, int(k), _p(vals), _p(idx), _stream()), "mg_motif_rank")
+    return vals, idx
+
+
 def voice_struct(mult, weight, decay, attack: int, release_tau: float, release_len: int, fs: float) -> L.Voice:
     """mg_voice from a partial table (equally long sequences of multipliers, weights and decay rates in 1/s) and the envelope:
     attack and release_len in samples, release_tau in seconds.  Only the table's length is checked here; the values are
