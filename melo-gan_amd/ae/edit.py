@@ -21,8 +21,8 @@ the source class mean onto the target's.  --shift needs labels: <split dir>/emot
 
 The needed source rows are encoded once; their mu / logvar stay resident.  One hipGraph per run -- stage the chunk's descriptors
 -> mg_latent_rows -> decode -> recon -> x -> encode -> mg_latent_cycle -> scatter z, recon, mu2 and the cycle words to their
-output positions -- is replayed per chunk of `batch` rows (a trailing partial chunk is padded with kind-0 rows), and the run ends
-with one device -> host read.  After the requested rows the run holds one identity row per source: the source's own
+output positions -- is replayed per chunk of `batch` rows (eval_pass.CursorPass; a trailing partial chunk is padded with kind-0
+rows), and the run ends with one device -> host read.  After the requested rows the run holds one identity row per source: the source's own
 reconstruction, which the note-level change and the classifier's `before` are measured against.
 
 Writes (unless --no-files) prior_<k>.mid, vary_r<row>_<k>.mid, path_r<a>_r<b>_s<ss>.mid (--join: also path_r<a>_r<b>.mid, the
@@ -79,7 +79,7 @@ class LatentEditor:
     """One eval-mode VaeEngine of `batch` rows behind mg_latent_rows."""
 
     def __init__(self, cfg: dict, device="cuda", batch: int = DEFAULT_BATCH):
-        from ..eval_pass import GraphCache
+        from ..eval_pass import CursorPass
         from .engine import VaeEngine
         require_device(AeEditError)
         if int(batch) < 1 or int(batch) > 32767:
@@ -92,11 +92,10 @@ class LatentEditor:
         eng = self.eng
         self.B = eng.B
         d = eng.dev
-        self.ctr = torch.zeros(1, dtype=torch.int64, device=d)
-        self.base = torch.zeros(1, dtype=torch.int64, device=d)
+        self.cur = CursorPass(d)
         self.desc = {n: torch.zeros((self.B,) + s, dtype=dt, device=d) for n, dt, s in DESCRIPTORS}    # the chunk's descriptors
         self.cyc = torch.zeros(self.B, 6, dtype=torch.float64, device=d)
-        self.graphs = GraphCache()
+        self.graphs = self.cur.graphs
         self.shape = None                   # what the resident arrays below were allocated for
         self.res = self.all = self.mu = self.logvar = self.dirs = None
 
@@ -121,8 +120,8 @@ class LatentEditor:
     # ---- one chunk --------------------------------------------------------------------------------------------
     def _launches(self, seed: int, interp: int):
         from .. import ops
-        eng, B, a, c = self.eng, self.B, self.all, self.desc
-        ops.stage_rows_cursor([(a[n], c[n]) for n, _, _ in DESCRIPTORS], B, None, a["kind"].shape[0], self.ctr, self.base)
+        eng, B, a, c, ctr, base = self.eng, self.B, self.all, self.desc, self.cur.ctr, self.cur.base
+        ops.stage_rows_cursor([(a[n], c[n]) for n, _, _ in DESCRIPTORS], B, None, a["kind"].shape[0], ctr, base)
         ops.latent_rows(self.mu, self.logvar, self.dirs, c["kind"], c["src_a"], c["src_b"], c["t"], c["dir"], c["alpha"], c["sigma"],
                         c["key"], eng.zl, interp, seed)
         eng.decode(False)
@@ -130,10 +129,10 @@ class LatentEditor:
         eng.encode(False)
         ops.latent_cycle(eng.zl, eng.mu, self.mu, self.dirs, c["kind"], c["src_a"], c["dir"], self.cyc)
         d = self.res.dev
-        ops.scatter_rows_cursor(eng.zl, d["z"], self.ctr, self.base)
-        ops.scatter_rows_cursor(eng.recon.view(B, -1), d["recon"], self.ctr, self.base)
-        ops.scatter_rows_cursor(eng.mu, d["mu2"], self.ctr, self.base)
-        ops.scatter_rows_cursor(self.cyc.view(torch.float32), d["cycle"].view(torch.float32), self.ctr, self.base)
+        ops.scatter_rows_cursor(eng.zl, d["z"], ctr, base)
+        ops.scatter_rows_cursor(eng.recon.view(B, -1), d["recon"], ctr, base)
+        ops.scatter_rows_cursor(eng.mu, d["mu2"], ctr, base)
+        ops.scatter_rows_cursor(self.cyc.view(torch.float32), d["cycle"].view(torch.float32), ctr, base)
 
     def _encode_sources(self, notes: torch.Tensor, sources: List[int]):
         """mu / logvar of the source rows, in chunks of `batch` in `sources` order (a trailing chunk's free slots hold zeros)."""
@@ -217,13 +216,7 @@ class LatentEditor:
             key = (seed, int(rows.interp))
             if key not in self.graphs:                          # the seed and interp are launch arguments the capture froze
                 self.graphs.clear()
-                self.ctr.zero_()
-            g = self.graphs.graph(key, lambda: self._launches(seed, int(rows.interp)))
-            self.res.buf.zero_()
-            self.ctr.zero_()
-            for _ in range(nb):
-                g.launch()
-                self.ctr.add_(1)
+            self.cur.replay(key, lambda: self._launches(*key), nb, self.res.buf.zero_)
             scored = self._score(ed, rows, host, R, R_all) if ed is not None else None
             out = self.res.host()                               # the run's one device -> host read; synchronises the stream
         scores = None

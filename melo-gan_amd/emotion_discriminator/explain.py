@@ -19,12 +19,12 @@ A note past the window's length equals b and gets exactly 0.  The notes are rank
 real events, ties to the lower t; padding has rank -1.
 
 The classifier's forward and input gradient are the ones the generator is trained against: GanEngine._ed_fwd / _ed_bwd of an
-eval-mode engine (gan.eval_engine.EvalEngine), fp32.  Pass 0 encodes the windows into the resident X chunk by chunk
-(mg_roll_encode), runs the forward, scatters the logits and takes the votes (mg_window_votes); one more row gives F(b).  Pass 1
-is one linear hipGraph -- mg_ig_rows -> _ed_fwd -> mg_ig_seed -> _ed_bwd -> mg_ig_accumulate -- replayed once per G = batch //
-steps windows, the cursor advancing behind each replay; then one mg_ig_rank.  Pass 2 (--deletion) is a second graph --
-mg_ig_rows in deletion mode -> _ed_fwd -> mg_ig_seed -- that removes the n strongest supporters, and the n strongest
-opponents, and reads the log-probability again.  The run ends with one device -> host read.
+eval-mode engine (gan.eval_engine.EvalEngine), fp32.  Pass 0 encodes the windows (eval_pass.DeviceWindows) into the resident X
+chunk by chunk (mg_roll_encode), runs the forward, scatters the logits and takes the votes (mg_window_votes); one more row gives
+F(b).  Pass 1 is one linear hipGraph -- mg_ig_rows -> _ed_fwd -> mg_ig_seed -> _ed_bwd -> mg_ig_accumulate -- replayed once per
+G = batch // steps windows, the cursor advancing behind each replay (eval_pass.CursorPass); then one mg_ig_rank.  Pass 2
+(--deletion) is a second graph -- mg_ig_rows in deletion mode -> _ed_fwd -> mg_ig_seed -- that removes the n strongest
+supporters, and the n strongest opponents, and reads the log-probability again.  The run ends with one device -> host read.
 
 host_ig_rows / host_ig_seed / host_ig_accumulate / host_ig_rank restate the four kernels in numpy; host_explain runs the whole
 method over any differentiable forward under torch autograd.
@@ -35,7 +35,6 @@ status 2.  Non-finite attributions are the same error.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 from dataclasses import dataclass
@@ -44,9 +43,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .. import midi_rolls as MR
-from ..midi_in import MidiImportError
 from ..pieces import require_device, run_tool
-from .predict import DEFAULT_BATCH, DEFAULT_MIN_EVENTS, MAX_CLASSES
+from .predict import DEFAULT_BATCH, check_batch, check_notes_config, load_tool_inputs
 
 DEFAULT_STEPS = 32
 DEFAULT_TOP = 8
@@ -243,10 +241,8 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=DEFAULT_STEPS, help="points of the midpoint rule along the path")
     ap.add_argument("--top", type=int, default=DEFAULT_TOP, help="notes listed at either end of the ranking")
     ap.add_argument("--deletion", type=str, default=None, help="counts of notes to remove, e.g. 1,2,4,8")
-    ap.add_argument("--hop", type=int, default=None, help="events between window starts (default: the config's max_notes)")
-    ap.add_argument("--min-events", type=int, default=DEFAULT_MIN_EVENTS)
+    MR.add_window_arguments(ap, max_notes=False)
     ap.add_argument("--batch", type=int, default=DEFAULT_BATCH)
-    ap.add_argument("--drums", action="store_true", help="keep the notes of channel 10")
     ap.add_argument("--save", type=str, default=None, help="write attr (W, T, 4) float64 to this .npy")
     ap.add_argument("--out", type=str, default="explain.json")
     return ap.parse_args(argv)
@@ -269,23 +265,12 @@ class ExplainPlan:
 
 def check_config(cfg: dict):
     """predict's requirements -- input_mode notes, note_dim 4, 2..32 classes -- and the kernels' T <= 4096."""
-    mode = cfg.get("input_mode", "latent")
-    if mode != "notes":
-        raise ExplainError(f"input_mode = {mode}: explain attributes the verdict to the notes of a roll; the latent classifier "
-                           "never sees them")
-    if int(cfg.get("note_dim", 4)) != 4:
-        raise ExplainError(f"note_dim = {cfg.get('note_dim')}: a roll holds 4 values per note")
-    K = int(cfg.get("n_classes", 4))
-    if not 2 <= K <= MAX_CLASSES:
-        raise ExplainError(f"n_classes = {K}: 2..{MAX_CLASSES}")
-    T = int(cfg.get("max_notes", 512))
-    if not 8 <= T <= MAX_T:
-        raise ExplainError(f"max_notes = {T}: 8..{MAX_T}")
+    check_notes_config(cfg, ExplainError, "explain attributes the verdict to the notes of a roll; the latent classifier never sees "
+                       "them", 8, MAX_T)
 
 
 def check_sizes(batch, steps):
-    if not 1 <= int(batch) <= 32767:
-        raise ExplainError(f"--batch = {batch}: must be in 1..32767")
+    check_batch(batch, ExplainError)
     if not 1 <= int(steps) <= int(batch):
         raise ExplainError(f"--steps = {steps}: must be in 1..--batch = {batch} (a window's path is one part of a batch)")
 
@@ -307,17 +292,9 @@ def rolls_plan(path: str, x, rows) -> MR.Plan:
 
 
 def plan(args) -> ExplainPlan:
-    from ..gan.config import load_config
     from .evaluate import class_names
-    if not os.path.isfile(args.config):
-        raise ExplainError(f"config {args.config} does not exist")
-    cfg = load_config(args.config)
-    check_config(cfg)
+    cfg = load_tool_inputs(args, ExplainError, check_config)
     T, K = int(cfg.get("max_notes", 512)), int(cfg.get("n_classes", 4))
-    if args.model is None:
-        raise ExplainError("give --model")
-    if not os.path.isfile(args.model):
-        raise ExplainError(f"checkpoint {args.model} does not exist")
     check_sizes(args.batch, args.steps)
     if int(args.top) < 1:
         raise ExplainError(f"--top = {args.top}: must be >= 1")
@@ -356,14 +333,7 @@ def plan(args) -> ExplainPlan:
             raise ExplainError(f"{args.notes}: a selected row holds a value that is not finite")
         source, p = x, rolls_plan(args.notes, x, rows)
     else:
-        try:
-            for f in args.files:
-                if not os.path.isfile(f):
-                    raise MidiImportError(f"{f}: no such file")
-            p = MR.plan_files(list(args.files), T, T if args.hop is None else args.hop, args.min_events, args.drums)
-        except MidiImportError as e:
-            raise ExplainError(str(e)) from e
-        source = p
+        source = p = MR.plan_from_args(args.files, T, args, ExplainError)
     require_device(ExplainError)
     return ExplainPlan(cfg, args.model, int(args.batch), int(args.steps), int(args.top), target, deletion, args.out, args.save,
                        source, p)
@@ -398,6 +368,7 @@ class Explainer:
 
     def __init__(self, ed_cfg: dict, device="cuda", batch: int = DEFAULT_BATCH, steps: int = DEFAULT_STEPS):
         import torch
+        from ..eval_pass import CursorPass
         require_device(ExplainError)
         check_config(ed_cfg)
         check_sizes(batch, steps)
@@ -410,12 +381,9 @@ class Explainer:
             raise ExplainError("explain: the fp32 notes-mode classifier only")
         self.B, self.S, self.T, self.K = eng.B, int(steps), eng.T, int(eng.n_classes)
         self.G = self.B // self.S
-        d = eng.dev
-        self.ctr = torch.zeros(1, dtype=torch.int64, device=d)
-        self.base = torch.zeros(1, dtype=torch.int64, device=d)
-        self.logp_rows = torch.zeros(self.B, dtype=torch.float64, device=d)
-        self.graphs = self.ee.graphs
-        self.X = self.held = self.res = self.n_del = None
+        self.cur = CursorPass(eng.dev, self.ee.graphs)
+        self.logp_rows = torch.zeros(self.B, dtype=torch.float64, device=eng.dev)
+        self.X = self.win = self.res = self.n_del = None    # the last run's arrays: the captured graphs hold their addresses
         self.replay_ms = None           # the last run's time per replay of the pass-1 graph (events around the replays)
 
     def load(self, path: str):
@@ -427,24 +395,24 @@ class Explainer:
     # ---- what the two graphs hold ----
     def _path_launches(self):
         from .. import ops
-        eng, r = self.eng, self.res.dev
-        ops.ig_rows(self.X, eng.notes, self.S, self.ctr, self.base)
+        eng, r, ctr, base = self.eng, self.res.dev, self.cur.ctr, self.cur.base
+        ops.ig_rows(self.X, eng.notes, self.S, ctr, base)
         eng._ed_fwd(eng.notes)
-        ops.ig_seed(eng.logits, r["target"], self.S, eng.dlogits, self.logp_rows, self.ctr, self.base)
+        ops.ig_seed(eng.logits, r["target"], self.S, eng.dlogits, self.logp_rows, ctr, base)
         eng._ed_bwd(eng.dnotes)
-        ops.ig_accumulate(eng.dnotes, self.X, self.S, r["attr"], r["note"], r["sums"], self.ctr, self.base)
+        ops.ig_accumulate(eng.dnotes, self.X, self.S, r["attr"], r["note"], r["sums"], ctr, base)
 
     def _deletion_launches(self):
         from .. import ops
         import torch
-        eng, r, R = self.eng, self.res.dev, 2 * self.n_del.numel()
+        eng, r, R, ctr, base = self.eng, self.res.dev, 2 * self.n_del.numel(), self.cur.ctr, self.cur.base
         G = self.B // R
-        ops.ig_rows(self.X, eng.notes, R, self.ctr, self.base, ops.IG_DELETE, self.held["win_len"], r["rank"], self.n_del)
+        ops.ig_rows(self.X, eng.notes, R, ctr, base, ops.IG_DELETE, self.win.win_len, r["rank"], self.n_del)
         eng._ed_fwd(eng.notes)
-        ops.ig_seed(eng.logits, r["target"], R, eng.dlogits, self.logp_rows, self.ctr, self.base)
+        ops.ig_seed(eng.logits, r["target"], R, eng.dlogits, self.logp_rows, ctr, base)
         # the batch's G windows of R fp64 words each, as rows of fp32 pairs, to their window positions
         ops.scatter_rows_cursor(self.logp_rows.view(torch.float32)[:2 * G * R].view(G, 2 * R),
-                                r["del_log_p"].view(torch.float32).view(-1, 2 * R), self.ctr, self.base)
+                                r["del_log_p"].view(torch.float32).view(-1, 2 * R), ctr, base)
 
     def run(self, source, target: Optional[int] = None, deletion: Sequence[int] = ()) -> dict:
         """source: an MR.Plan of windows of T events, or rolls (W, T, 4) float32 (every window of full length).  target: None
@@ -454,63 +422,48 @@ class Explainer:
         del_log_p (W, 2 D) fp64: the D supporter removals, then the D opponent removals."""
         import torch
         from .. import ops
-        from ..eval_pass import Packed
-        eng, B, K, T, S, G = self.eng, self.B, self.K, self.T, self.S, self.G
+        from ..eval_pass import DeviceWindows, Packed
+        eng, B, K, T, S, G, cur = self.eng, self.B, self.K, self.T, self.S, self.G, self.cur
         d = eng.dev
         is_plan = isinstance(source, MR.Plan)
         if is_plan:
-            p = source
-            W, E = p.win_start.shape[0], p.events.shape[0]
-            if p.T != T or W < 1 or ((p.win_start < 0) | (p.win_len < 0) | (p.win_len > T) | (p.win_start + p.win_len > E)).any() or \
-                    p.file_off[0] != 0 or p.file_off[-1] != W or (np.diff(p.file_off) < 0).any():
-                raise ExplainError(f"run: a plan of windows of {T} events inside its event list expected")
-            win_len, file_off = p.win_len, p.file_off
+            MR.check_plan(source, T, ExplainError)
+            W = source.win_start.shape[0]
         else:
             x = np.asarray(source)
             if x.dtype != np.float32 or x.ndim != 3 or tuple(x.shape[1:]) != (T, 4) or x.shape[0] < 1 or not np.isfinite(x).all():
                 raise ExplainError(f"run: finite float32 rolls (W >= 1, {T}, 4) expected")
             W = x.shape[0]
-            win_len, file_off = np.full(W, T, np.int32), np.array([0, W], np.int64)
         if target is not None and not 0 <= int(target) < K:
             raise ExplainError(f"run: target = {target}: None or a class in 0..{K - 1}")
         deletion = tuple(int(n) for n in deletion)
-        D, F = len(deletion), file_off.shape[0] - 1
+        D = len(deletion)
         if D and (min(deletion) < 0 or max(deletion) > T or 2 * D > B):
             raise ExplainError(f"run: deletion counts {deletion}: in 0..{T}, at most {B // 2} of them")
         nb0 = (W + B - 1) // B
         with torch.cuda.stream(eng.stream):
-            self.graphs.clear()             # the captured graphs hold the addresses of the arrays below
+            cur.graphs.clear()              # the captured graphs hold the addresses of the arrays below
+            self.win = win = DeviceWindows(source if is_plan else (np.full(W, T, np.int32), np.array([0, W], np.int64), T), d)
             parts = [("attr", (W, T, 4), torch.float64), ("note", (W, T), torch.float64), ("sums", (W, ops.IG_SUMS), torch.float64),
-                     ("probs", (W, K), torch.float64), ("file_mean", (F, K), torch.float64), ("log_p", (W,), torch.float64),
-                     ("log_p_silence", (W,), torch.float64), ("del_log_p", (W, max(1, 2 * D)), torch.float64),
-                     ("loss", (W, ops.ROLL_LOSS_WORDS), torch.int64), ("logits", (W, K), torch.float32),
-                     ("silence", (W, K), torch.float32), ("seed", (W, K), torch.float32), ("rank", (W, T), torch.int32),
-                     ("win_pred", (W,), torch.int32), ("target", (W,), torch.int32), ("file_pred", (F,), torch.int32),
-                     ("switches", (F,), torch.int32)]
+                     ("log_p", (W,), torch.float64), ("log_p_silence", (W,), torch.float64),
+                     ("del_log_p", (W, max(1, 2 * D)), torch.float64)] + win.vote_parts(K) + \
+                    [("silence", (W, K), torch.float32), ("seed", (W, K), torch.float32), ("rank", (W, T), torch.int32),
+                     ("target", (W,), torch.int32)]
             self.res = Packed(parts, d)
             r = self.res.dev
-            self.held = {"win_len": torch.from_numpy(np.ascontiguousarray(win_len, np.int32)).to(d),
-                         "file_off": torch.from_numpy(np.ascontiguousarray(file_off, np.int64)).to(d)}
             self.n_del = torch.tensor(deletion, dtype=torch.int32, device=d) if D else None
             # ---- pass 0: the resident windows, their logits and votes, and the silent roll's logits ----
             Xp = torch.full((nb0 * B, T, 4), -1.0, device=d)        # whole chunks; the rows past W stay silent
             self.X = Xp[:W]
-            if is_plan:
-                self.held.update(events=torch.from_numpy(p.events).to(d), win_start=torch.from_numpy(p.win_start).to(d))
-            else:
+            if not is_plan:
                 self.X.copy_(torch.from_numpy(x))
-            self.ctr.zero_()
-            self.base.zero_()
-            for c in range(nb0):
-                chunk = Xp[c * B:(c + 1) * B]
+            for c in cur.each(nb0):         # eager: every chunk has its own rows of X
+                rows = Xp[c * B:(c + 1) * B]
                 if is_plan:
-                    ops.roll_encode(self.held["events"], self.held["win_start"], self.held["win_len"], chunk, r["loss"], self.ctr,
-                                    self.base)
-                eng._ed_fwd(chunk)
-                ops.scatter_rows_cursor(eng.logits, r["logits"], self.ctr, self.base)
-                self.ctr.add_(1)
-            ops.window_votes(r["logits"], self.held["file_off"], r["probs"], r["win_pred"], r["file_mean"], r["file_pred"],
-                             r["switches"])
+                    win.encode(rows, r["loss"], cur)
+                eng._ed_fwd(rows)
+                ops.scatter_rows_cursor(eng.logits, r["logits"], cur.ctr, cur.base)
+            win.votes(r)
             if target is None:
                 r["target"].copy_(r["win_pred"])
             else:
@@ -518,28 +471,17 @@ class Explainer:
             eng.notes.fill_(-1.0)           # one extra row gives F(b): every row of this batch is the silent roll
             eng._ed_fwd(eng.notes)
             r["silence"].copy_(eng.logits[:1].expand(W, K))
-            self.ctr.zero_()
+            cur.ctr.zero_()
             for z, lp in ((r["logits"], r["log_p"]), (r["silence"], r["log_p_silence"])):      # F(x) and F(b) at the targets
-                ops.ig_seed(z, r["target"], 1, r["seed"], lp, self.ctr, self.base)
+                ops.ig_seed(z, r["target"], 1, r["seed"], lp, cur.ctr, cur.base)
             # ---- pass 1: the path ----
-            g = self.graphs.graph("path", self._path_launches)
-            self.ctr.zero_()
             nb = (W + G - 1) // G
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(nb):
-                g.launch()
-                self.ctr.add_(1)
-            t1.record()
-            ops.ig_rank(r["note"], self.held["win_len"], r["rank"])
+            t0, t1 = cur.replay("path", self._path_launches, nb)
+            ops.ig_rank(r["note"], win.win_len, r["rank"])
             # ---- pass 2: the deletion test ----
             if D:
-                self.ctr.zero_()
-                g2 = self.graphs.graph("deletion", self._deletion_launches)
-                self.ctr.zero_()
-                for _ in range((W + B // (2 * D) - 1) // (B // (2 * D))):
-                    g2.launch()
-                    self.ctr.add_(1)
+                G2 = B // (2 * D)
+                cur.replay("deletion", self._deletion_launches, (W + G2 - 1) // G2)
             host = self.res.host()          # the run's one device -> host read; synchronises the stream
             self.replay_ms = t0.elapsed_time(t1) / nb
         out = {k: v.numpy().copy() for k, v in host.items() if k not in ("silence", "seed")}
@@ -629,13 +571,7 @@ def run(ep: ExplainPlan) -> dict:
     X = ex.X.cpu().numpy()
     rep = report(ep.plan, X, res, names, ep.top, ep.deletion)
     rep.update(steps=ep.steps, classes=list(names), model=ep.model, replay_ms=ex.replay_ms)
-    os.makedirs(os.path.dirname(os.path.abspath(ep.out)), exist_ok=True)
-    try:
-        text = json.dumps(rep, indent=1, allow_nan=False)
-    except ValueError as e:
-        raise ExplainError(f"the report holds a value that is not finite ({e}): is {ep.model} a trained checkpoint?") from e
-    with open(ep.out, "w") as f:
-        f.write(text)
+    MR.write_report(ep.out, rep, ExplainError, f"the report holds a value that is not finite: is {ep.model} a trained checkpoint?")
     if ep.save:
         os.makedirs(os.path.dirname(os.path.abspath(ep.save)), exist_ok=True)
         np.save(ep.save, res["attr"])

@@ -1,12 +1,14 @@
 """What the held-out evaluators share (gan/evaluate.py, ae/evaluate.py, emotion_discriminator/evaluate.py): the check of a
 resident split, the per-split state a captured batch holds the addresses of, one packed result buffer with one device -> host
 read, the keyed cache of captured batches, and the pass itself -- reset, one replay per batch, one read.  What a batch
-launches, and in which order, stays with each evaluator."""
+launches, and in which order, stays with each evaluator.  And what the tools that walk chunks behind a host-advanced cursor
+share (predict, explain, midi_import, motifs, ae.edit): CursorPass, DeviceWindows and device_roll_encode."""
 from __future__ import annotations
 
 from types import SimpleNamespace
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import ops
@@ -102,3 +104,82 @@ class ResidentPass:
         self.ctr.zero_()
         for _ in range(self.split.nb):
             graph.launch()
+
+
+class CursorPass:
+    """A pass in chunks whose cursor the host advances: ctr (the chunks behind it) and base (0), int64 device scalars, and the
+    graphs captured over them.  What a chunk launches stays with the caller."""
+
+    def __init__(self, device, graphs: Optional[GraphCache] = None):
+        self.ctr = torch.zeros(1, dtype=torch.int64, device=device)
+        self.base = torch.zeros(1, dtype=torch.int64, device=device)
+        self.graphs = GraphCache() if graphs is None else graphs
+
+    def replay(self, key, launches, nb: int, reset=None):
+        """nb chunks of `launches`, captured under `key`, the cursor advancing behind each replay.  As in ResidentPass.run, a
+        new key's eager run starts from chunk 0 and goes in front of reset(), which discards what it wrote.  Returns the two
+        events around the replays: their time can be read once the stream is synchronised."""
+        if key not in self.graphs:
+            self.ctr.zero_()
+        graph = self.graphs.graph(key, launches)
+        if reset is not None:
+            reset()
+        self.ctr.zero_()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(nb):
+            graph.launch()
+            self.ctr.add_(1)
+        t1.record()
+        return t0, t1
+
+    def each(self, nb: int):
+        """replay's eager twin: `for c in each(nb)` runs its body at chunk c = 0 .. nb - 1, the cursor advancing behind it."""
+        self.ctr.zero_()
+        for c in range(nb):
+            yield c
+            self.ctr.add_(1)
+
+
+class DeviceWindows:
+    """The windows of a midi_rolls.Plan on the device: events (E, 4) int32, win_start (W,) int64, win_len (W,) int32, file_off
+    (F + 1,) int64, and W, F, T.  Windows that are rolls already are given as (win_len, file_off, T) and have no events to
+    encode.  While this object lives, the addresses a captured graph holds stay its arrays'."""
+
+    def __init__(self, p, device):
+        up = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype)).to(device)  # noqa: E731
+        self.events = self.win_start = None
+        if isinstance(p, tuple):
+            win_len, file_off, self.T = p
+        else:
+            win_len, file_off, self.T = p.win_len, p.file_off, p.T
+            self.events, self.win_start = up(p.events, np.int32), up(p.win_start, np.int64)
+        self.win_len, self.file_off = up(win_len, np.int32), up(file_off, np.int64)
+        self.W, self.F = self.win_len.shape[0], self.file_off.shape[0] - 1
+
+    def encode(self, x, loss, cur: CursorPass):
+        """mg_roll_encode of the cursor's chunk of windows into x (B, T, 4), its clamp counts into loss (W, 8)."""
+        return ops.roll_encode(self.events, self.win_start, self.win_len, x, loss, cur.ctr, cur.base)
+
+    def vote_parts(self, K: int) -> list:
+        """The Packed parts of the windows' clamp counts, logits and votes, the 8-byte ones first."""
+        return [("loss", (self.W, ops.ROLL_LOSS_WORDS), torch.int64), ("probs", (self.W, K), torch.float64),
+                ("file_mean", (self.F, K), torch.float64), ("logits", (self.W, K), torch.float32),
+                ("win_pred", (self.W,), torch.int32), ("file_pred", (self.F,), torch.int32), ("switches", (self.F,), torch.int32)]
+
+    def votes(self, r: dict):
+        """mg_window_votes over r["logits"] into the other parts of vote_parts."""
+        ops.window_votes(r["logits"], self.file_off, r["probs"], r["win_pred"], r["file_mean"], r["file_pred"], r["switches"])
+
+
+def device_roll_encode(p, batch: int = 64):
+    """midi_rolls.host_roll_encode's result from mg_roll_encode: chunks of `batch` windows, each scattered to its rows."""
+    d = torch.device("cuda")
+    win, cur, W, T = DeviceWindows(p, d), CursorPass(d), p.win_start.shape[0], p.T
+    B = max(1, min(int(batch), W))
+    x, out = torch.empty(B, T, 4, device=d), torch.empty(W, T * 4, device=d)
+    loss = torch.zeros(W, ops.ROLL_LOSS_WORDS, dtype=torch.int64, device=d)
+    for _ in cur.each((W + B - 1) // B):
+        win.encode(x, loss, cur)
+        ops.scatter_rows_cursor(x.view(B, T * 4), out, cur.ctr, cur.base)
+    return out.cpu().numpy().reshape(W, T, 4), loss.cpu().numpy()

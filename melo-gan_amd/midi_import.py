@@ -8,7 +8,7 @@ PATH is a file or a directory, searched for *.mid and *.midi (sorted).  Every fi
 events on the 1/64-beat grid (midi_in.events_from_notes) and cut into windows of at most --max-notes events, --hop events
 apart (midi_rolls.plan_windows); every window becomes one row of SPLIT_DIR/notes.npy (N, max_notes, 4) float32 in the
 generator's output contract, padded with the reference's padding row (-1, -1, -1, -1).  The encode is mg_roll_encode when a
-device is present and midi_rolls.host_roll_encode otherwise: the bits are the same.
+device is present and midi_rolls.host_roll_encode otherwise (midi_rolls.encode_plan): the bits are the same.
 
 --emotion E labels every row; --labels FILE.csv holds lines `file name,emotion` (the file's base name; happy, sad, angry,
 calm).  With labels, emotion.npy (N,) int64 holds the class index and numeric_features.npy (N, 6) generate.EMOTION_TABLE's row
@@ -24,7 +24,6 @@ from __future__ import annotations
 
 import argparse
 import csv
-import json
 import os
 import sys
 from dataclasses import dataclass
@@ -36,21 +35,14 @@ from . import midi_rolls as MR
 from .midi_in import MidiImportError
 from .pieces import EMOTIONS, run_tool
 
-DEFAULT_MAX_NOTES = 512
-DEFAULT_MIN_EVENTS = 8
-ENCODE_BATCH = 64
-
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Import MIDI files as a split of note rolls")
     ap.add_argument("paths", nargs="+", metavar="PATH", help="a .mid / .midi file, or a directory searched for them")
     ap.add_argument("--out", type=str, required=True, help="the split directory to write")
-    ap.add_argument("--max-notes", type=int, default=DEFAULT_MAX_NOTES)
-    ap.add_argument("--hop", type=int, default=None, help="events between window starts (default: --max-notes)")
-    ap.add_argument("--min-events", type=int, default=DEFAULT_MIN_EVENTS)
+    MR.add_window_arguments(ap, max_notes=True)
     ap.add_argument("--emotion", type=str, default=None, help="one label for every file: " + ", ".join(EMOTIONS))
     ap.add_argument("--labels", type=str, default=None, help="CSV of lines `file name,emotion`")
-    ap.add_argument("--drums", action="store_true", help="keep the notes of channel 10")
     ap.add_argument("--cpu", action="store_true", help="encode on the host even when a device is present")
     return ap.parse_args(argv)
 
@@ -87,21 +79,20 @@ def plan(args) -> ImportPlan:
         raise MidiImportError("--emotion and --labels exclude each other")
     if args.max_notes < 1 or args.max_notes > (1 << 20):
         raise MidiImportError(f"--max-notes = {args.max_notes}: 1..2^20")
-    hop = args.max_notes if args.hop is None else args.hop
-    files = MR.find_files(args.paths)
+    if args.emotion is not None and args.emotion.lower() not in EMOTIONS:
+        raise MidiImportError(f"--emotion '{args.emotion}': one of {', '.join(EMOTIONS)}")
+    table = read_labels(args.labels) if args.labels is not None else None
+    p = MR.plan_from_args(args.paths, args.max_notes, args, MidiImportError, search=True)
+    files = [f["file"] for f in p.files]
     labels = None
     if args.emotion is not None:
-        if args.emotion.lower() not in EMOTIONS:
-            raise MidiImportError(f"--emotion '{args.emotion}': one of {', '.join(EMOTIONS)}")
         labels = [EMOTIONS.index(args.emotion.lower())] * len(files)
-    elif args.labels is not None:
-        table = read_labels(args.labels)
+    elif table is not None:
         missing = [f for f in files if os.path.basename(f) not in table]
         if missing:
             raise MidiImportError(f"--labels: no line for {os.path.basename(missing[0])}" +
                                   (f" and {len(missing) - 1} more" if len(missing) > 1 else ""))
         labels = [table[os.path.basename(f)] for f in files]
-    p = MR.plan_files(files, args.max_notes, hop, args.min_events, args.drums)
     device = False
     if not args.cpu:
         import torch
@@ -109,33 +100,10 @@ def plan(args) -> ImportPlan:
     return ImportPlan(p, args.out, labels, device)
 
 
-def device_roll_encode(p: MR.Plan, batch: int = ENCODE_BATCH):
-    """midi_rolls.host_roll_encode's result from mg_roll_encode: chunks of `batch` windows, each scattered to its rows."""
-    import torch
-    from . import ops
-    d = torch.device("cuda")
-    W, T = p.win_start.shape[0], p.T
-    B = max(1, min(int(batch), W))
-    events = torch.from_numpy(p.events).to(d)
-    ws, wl = torch.from_numpy(p.win_start).to(d), torch.from_numpy(p.win_len).to(d)
-    x = torch.empty(B, T, 4, device=d)
-    out = torch.empty(W, T * 4, device=d)
-    loss = torch.zeros(W, ops.ROLL_LOSS_WORDS, dtype=torch.int64, device=d)
-    ctr, base = torch.zeros(1, dtype=torch.int64, device=d), torch.zeros(1, dtype=torch.int64, device=d)
-    for _ in range((W + B - 1) // B):
-        ops.roll_encode(events, ws, wl, x, loss, ctr, base)
-        ops.scatter_rows_cursor(x.view(B, T * 4), out, ctr, base)
-        ctr.add_(1)
-    return out.cpu().numpy().reshape(W, T, 4), loss.cpu().numpy()
-
-
 def run(ip: ImportPlan) -> dict:
     from .gan.generate import EMOTION_TABLE
     p = ip.plan
-    if ip.device:
-        x, loss = device_roll_encode(p)
-    else:
-        x, loss = MR.host_roll_encode(p.events, p.win_start, p.win_len, p.T)
+    x, loss = MR.encode_plan(p, ip.device)
     W, F = x.shape[0], len(p.files)
     file_of = np.repeat(np.arange(F), np.diff(p.file_off))
     os.makedirs(ip.out, exist_ok=True)
@@ -156,8 +124,7 @@ def run(ip: ImportPlan) -> dict:
     rows = [{"file": p.files[int(file_of[w])]["file"], "window_start": int(p.win_local[w]), "events": int(p.win_len[w]),
              "start_beat": float(p.start_beat[w]), "loss": {n: int(v) for n, v in zip(MR.LOSS, loss[w])}} for w in range(W)]
     rep = {"max_notes": p.T, "rows": rows, "files": files, "encode": "device" if ip.device else "host"}
-    with open(os.path.join(ip.out, "index.json"), "w") as fh:
-        json.dump(rep, fh, indent=1, allow_nan=False)
+    MR.write_report(os.path.join(ip.out, "index.json"), rep)
     n_f = sum(1 for b in files if b["faithful"])
     print(f"midi_import: {F} files, {W} rows of {p.T} notes -> {ip.out} ({n_f} of {F} files faithful; "
           f"{'labelled' if ip.file_label is not None else 'no labels'})")

@@ -1,5 +1,7 @@
-"""From MIDI files to note rolls on the host: the window plan, the numpy restatements of mg_roll_encode and mg_window_votes,
-and what was lost on the way.  numpy only: nothing here imports torch or touches a GPU.
+"""From MIDI files to note rolls on the host: the window plan and its bounds check, the numpy restatements of mg_roll_encode
+and mg_window_votes, what was lost on the way, and what predict, explain, midi_import and motifs share around the plan: the
+window arguments, the plan of an argument list, the choice of the encode, the report writer.  numpy only: importing this
+imports no torch and touches no GPU.
 
 The roll contract's decode (csrc/note_decode.h, midi.notes_from_roll, gan.music_metrics.decode_rolls) is not injective, but on
 its image -- pitches 36..96, velocities 60..127, durations 16..256 and steps 7..256 on the 1/64-beat grid -- it has an exact
@@ -8,6 +10,7 @@ it.  Outside the image the encode clamps and counts: LOSS names the eight counts
 """
 from __future__ import annotations
 
+import json
 import os
 from dataclasses import dataclass
 from typing import List, Sequence
@@ -21,6 +24,7 @@ LOSS = ("pitch_raised", "pitch_lowered", "velocity_raised", "duration_lengthened
         "steps_zero", "rests")
 PITCH_LO, PITCH_HI, VEL_LO, VEL_HI, DUR_LO, Q_HI = 36, 96, 60, 127, 16, 256
 EXTENSIONS = (".mid", ".midi")
+DEFAULT_MAX_NOTES, DEFAULT_MIN_EVENTS = 512, 8
 
 
 def plan_windows(E: int, T: int, hop: int, min_events: int):
@@ -62,6 +66,12 @@ def encode_events(events):
     return x, fired
 
 
+def windows_outside(win_start, win_len, E: int, T: int) -> bool:
+    """Whether a window begins in front of an event list of E events, ends past it or is longer than T."""
+    ws, wl = np.asarray(win_start, np.int64), np.asarray(win_len, np.int64)
+    return bool(((ws < 0) | (wl < 0) | (wl > T) | (ws + wl > E)).any())
+
+
 def host_roll_encode(events, win_start, win_len, T: int, rows: int = None):
     """mg_roll_encode on the host, all windows at once: (x float32 (rows, T, 4), loss int64 (rows, 8)); rows defaults to the
     number of windows W, rows past W hold the padding row and zero counts.  A window that points outside `events` raises."""
@@ -69,7 +79,7 @@ def host_roll_encode(events, win_start, win_len, T: int, rows: int = None):
     ws, wl = np.asarray(win_start, np.int64), np.asarray(win_len, np.int64)
     W, T = ws.shape[0], int(T)
     rows = W if rows is None else int(rows)
-    if wl.shape != (W,) or rows < W or ((ws < 0) | (wl < 0) | (wl > T) | (ws + wl > ev.shape[0])).any():
+    if wl.shape != (W,) or rows < W or windows_outside(ws, wl, ev.shape[0], T):
         raise ValueError("host_roll_encode: a window points outside the event list or is longer than T")
     code, fired = encode_events(ev)
     x = np.full((rows, T, 4), -1.0, np.float32)
@@ -182,6 +192,60 @@ def plan_files(paths: Sequence[str], T: int, hop: int, min_events: int, drums: b
     return Plan(np.ascontiguousarray(np.concatenate(evs), np.int32), np.concatenate(starts).astype(np.int64),
                 np.concatenate(lens).astype(np.int32), np.concatenate(local).astype(np.int64), np.concatenate(beats),
                 np.array(off, np.int64), files, int(T))
+
+
+def check_plan(p: Plan, T: int = None, err=ValueError):
+    """The one bounds check of a Plan: at least one window, every window inside the event list and no longer than p.T,
+    file_off rising from 0 to W; with T, windows of T events.  Raises err."""
+    if not isinstance(p, Plan) or (T is not None and p.T != T):
+        raise err("a plan of windows" + ("" if T is None else f" of {T} events") + " expected")
+    W = p.win_start.shape[0]
+    if W < 1 or p.win_len.shape != (W,) or windows_outside(p.win_start, p.win_len, p.events.shape[0], p.T) or \
+            p.file_off[0] != 0 or p.file_off[-1] != W or (np.diff(p.file_off) < 0).any():
+        raise err("a window points outside the event list, or the files' offsets do not cover the windows")
+
+
+def add_window_arguments(ap, max_notes: bool):
+    """--hop, --min-events and --drums; max_notes: --max-notes too, for a tool whose window length no config sets."""
+    if max_notes:
+        ap.add_argument("--max-notes", type=int, default=DEFAULT_MAX_NOTES, help="events per window of a MIDI file")
+    ap.add_argument("--hop", type=int, default=None,
+                    help="events between window starts (default: " + ("--max-notes)" if max_notes else "the config's max_notes)"))
+    ap.add_argument("--min-events", type=int, default=DEFAULT_MIN_EVENTS)
+    ap.add_argument("--drums", action="store_true", help="keep the notes of channel 10")
+
+
+def plan_from_args(paths: Sequence[str], T: int, args, err, search: bool = False) -> Plan:
+    """plan_files over a tool's PATH arguments, which search looks through with find_files and which otherwise must all be
+    files, with its window arguments.  Every MidiImportError is raised again as err(its message)."""
+    try:
+        files = find_files(paths) if search else list(paths)
+        for f in files:
+            if not os.path.isfile(f):
+                raise midi_in.MidiImportError(f"{f}: no such file")
+        return plan_files(files, T, T if args.hop is None else args.hop, args.min_events, args.drums)
+    except midi_in.MidiImportError as e:
+        raise err(str(e)) from e
+
+
+def encode_plan(p: Plan, device: bool):
+    """(x float32 (W, T, 4), loss int64 (W, 8)) from mg_roll_encode on the device or from host_roll_encode: the same bits."""
+    if device:
+        from .eval_pass import device_roll_encode
+        return device_roll_encode(p)
+    return host_roll_encode(p.events, p.win_start, p.win_len, p.T)
+
+
+def write_report(path: str, rep: dict, err=ValueError, what: str = "the report holds a value that is not finite"):
+    """rep as JSON at path, whose directory is made.  The text is complete before the file is opened: a value that is not
+    finite raises err("<what> (<json's words>)") and leaves no file."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    try:
+        text = json.dumps(rep, indent=1, allow_nan=False)
+    except ValueError as e:
+        raise err(f"{what} ({e})") from e
+    with open(path, "w") as f:
+        f.write(text)
 
 
 def loss_block(loss_rows, info: dict) -> dict:

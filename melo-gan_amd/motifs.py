@@ -47,7 +47,7 @@ import numpy as np
 
 from . import midi_rolls as MR
 from .gan.music_metrics import decode_rolls
-from .midi_in import GRID, MidiImportError
+from .midi_in import GRID
 from .pieces import run_tool
 
 MODES = {"interval+rhythm": 0, "interval": 1}
@@ -319,10 +319,7 @@ def parse_args(argv=None):
     ap.add_argument("--tokens", type=str, default="interval+rhythm", help=" or ".join(MODES))
     ap.add_argument("--min-len", type=int, default=DEFAULT_MIN_LEN, help="tokens a shared run needs to be reported and to count as copied")
     ap.add_argument("--top", type=int, default=DEFAULT_TOP, help="corpus rows kept per query row")
-    ap.add_argument("--max-notes", type=int, default=512, help="events per window of a MIDI file")
-    ap.add_argument("--hop", type=int, default=None, help="events between window starts (default: --max-notes)")
-    ap.add_argument("--min-events", type=int, default=8)
-    ap.add_argument("--drums", action="store_true", help="keep the notes of channel 10")
+    MR.add_window_arguments(ap, max_notes=True)
     ap.add_argument("--batch", type=int, default=DEFAULT_BATCH, help="query rows per pair matrix")
     ap.add_argument("--cpu", action="store_true", help="the numpy restatement instead of the device")
     ap.add_argument("--out", type=str, default="motifs.json")
@@ -362,7 +359,6 @@ def plan_set(paths: Sequence[str], args, what: str) -> list:
     """The parts of a set, host only: ("rolls", RollSet) for a .npy or a split directory, ("midi", midi_rolls.Plan) for MIDI
     files, which run() encodes."""
     parts = []
-    hop = args.max_notes if args.hop is None else args.hop
     for p in paths:
         if os.path.isdir(p) and os.path.isfile(os.path.join(p, "notes.npy")):
             x = _load_rolls(os.path.join(p, "notes.npy"))
@@ -373,10 +369,7 @@ def plan_set(paths: Sequence[str], args, what: str) -> list:
             names = [f"{p}#{i}" for i in range(x.shape[0])]
             parts.append(("rolls", RollSet(x, list(names), names, [p] * x.shape[0])))
         elif os.path.isdir(p) or (os.path.isfile(p) and p.lower().endswith(MR.EXTENSIONS)):
-            try:
-                parts.append(("midi", MR.plan_files(MR.find_files([p]), args.max_notes, hop, args.min_events, args.drums)))
-            except MidiImportError as e:
-                raise MotifError(f"{what}: {e}") from e
+            parts.append(("midi", MR.plan_from_args([p], args.max_notes, args, lambda m: MotifError(f"{what}: {m}"), search=True)))
         elif os.path.exists(p):
             raise MotifError(f"{what}: {p}: not a MIDI file, a directory or a .npy of rolls")
         else:
@@ -429,11 +422,7 @@ def _materialise(parts: list, device: bool) -> List[RollSet]:
         if kind == "rolls":
             out.append(part)
             continue
-        if device:
-            from .midi_import import device_roll_encode
-            x, _ = device_roll_encode(part)
-        else:
-            x, _ = MR.host_roll_encode(part.events, part.win_start, part.win_len, part.T)
+        x, _ = MR.encode_plan(part, device)
         files = [part.files[f]["file"] for f in np.repeat(np.arange(len(part.files)), np.diff(part.file_off))]
         out.append(RollSet(x, list(files), [f"{f}@{int(s)}" for f, s in zip(files, part.win_local)], list(files)))
     return out
@@ -496,9 +485,7 @@ def run(p: MotifPlan) -> dict:
         print(f"motifs: mean longest {rep['summary']['mean_longest']:.2f} against the baseline's "
               f"{rep['baseline']['summary']['mean_longest']:.2f}; mean copied share {rep['summary']['mean_copied_share']:.3f} "
               f"against {rep['baseline']['summary']['mean_copied_share']:.3f}")
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)) or ".", exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(rep, fh, indent=1, allow_nan=False)
+    MR.write_report(a.out, rep)
     return rep
 
 
