@@ -93,6 +93,7 @@ class EdEngine:
         self.rng_seed = int(cfg.get("seed", 42))
         self.stream = share.stream if share is not None else torch.cuda.Stream(device=d)
         self._graphs = {}
+        self.updates = 0         # optimiser steps this engine issued: a graph that advances it baked the learning rate (set_lr)
         self._tails: Dict[int, "EdEngine"] = {}
         # the resident training split of the staged step (attach_split); a tail stages from its owner's
         self._owner = share if share is not None else self
@@ -147,11 +148,10 @@ class EdEngine:
 
     def set_lr(self, lr: float):
         """ReduceLROnPlateau: the learning rate is a launch argument of the AdamW kernel, baked into every captured
-        graph that contains the update ('update', 'update#ticked' and the one-graph training steps 'step_rng' and
-        'step_staged'): those are dropped and re-captured with the new rate on their next run.  Engines sharing this one's parameters
-        (tail()) follow."""
+        graph that contains the update -- those whose capture saw `updates` advance (ops.run_graphed's record): they are
+        dropped and re-captured with the new rate on their next run.  Engines sharing this one's parameters (tail()) follow."""
         self.lr = float(lr)
-        for k in [k for k in self._graphs if k.startswith("update") or k in ("step_rng", "step_staged")]:
+        for k in [k for k, st in self._graphs.items() if st != "warm" and st.deltas[0]]:
             del self._graphs[k]
         for t in self._tails.values():
             t.set_lr(lr)
@@ -369,20 +369,23 @@ class EdEngine:
                       weight_decay=self.weight_decay if self.decoupled else 0.0,
                       ticked_rng_step=self.rng_step if fp.ticked else None)
         fp.ticked = False
+        self.updates += 1
 
     def run(self, name: str, use_graph: bool = True):
-        """hipGraph replay of backward_rng / update / forward_eval (first call eager, second call captures)."""
+        """hipGraph replay of a sub-step -- backward_rng, update, step_rng, step_staged, forward_eval -- (first call eager,
+        second call captures).  What its Python does to host_state() is recorded at the capture and re-applied by each
+        replay (ops.run_graphed); an update arriving behind the mask draw that advanced its state is a key of its own."""
         fn = getattr(self, name)
         if not use_graph:
             return fn()
-        key = name + ("#ticked" if name == "update" and self.P.ticked else "")
-        try:
-            ops.run_graphed(self._graphs, key, fn)
-        finally:
-            if name.endswith("_rng"):
-                self.P.ticked = True
-            if name in ("update", "step_rng", "step_staged"):
-                self.P.ticked = False
+        ops.run_graphed(self._graphs, name, fn, self)
+
+    def host_state(self):
+        """The host state the sub-steps change and a graph replay has to re-apply: (flags, counters)."""
+        return (self.P.ticked,), (self.updates,)
+
+    def set_host_state(self, flags, counters):
+        (self.P.ticked,), (self.updates,) = flags, counters
 
     def forward_eval(self):
         self.forward(train=False)

@@ -102,6 +102,7 @@ class EdLatentEngine(EdEngine):
             adam = dict(p=fp.data, m=fp.m, v=fp.v, state=fp.state, lr=self.lr, betas=self.betas,
                         weight_decay=self.weight_decay if self.decoupled else 0.0)
             fp.ticked = False
+            self.updates += 1
         ops.mlp_cls_wgrad_update(self.net, self.x, self.dlogits, self.w_off, self.b_off, fp.grad, self.loss_rows, self.loss, adam=adam,
                                  metrics=self._owner.metrics if metrics else None, logits=self.logits, y=self.y,
                                  rng_step=self.rng_step if apply else None)

@@ -201,7 +201,7 @@ class DataParallel:
         before the first step().  A no-op for engines without graphs (the CPU stand-ins of the tests) or use_graph=False."""
         e = self.engine
         self._prepared = True
-        if not self.active or not use_graph or not hasattr(e, "_capture") or self.mode == "ingraph":
+        if not self.active or not use_graph or not hasattr(e, "host_state") or self.mode == "ingraph":
             return                          # ingraph: the collectives are graph nodes, nothing to capture ahead of them
         import torch
         keep = [e.D.data, e.D.grad, e.D.m, e.D.v, e.D.state, e.GE.data, e.GE.grad, e.GE.m, e.GE.v, e.GE.state, e.rng_step]
@@ -209,7 +209,7 @@ class DataParallel:
         if getattr(e, "ema", None) is not None:
             keep.append(e.ema)          # the dry steps' generator updates move the shadow too
         saved = [t.clone() for t in keep]
-        nbt, ticked = e.num_batches_tracked, (e.D.ticked, e.GE.ticked)
+        host = e.host_state()
         dry, self._dry = self._dry, True
         try:
             for g_step in (True, True, False, False):
@@ -220,7 +220,7 @@ class DataParallel:
         for t, v in zip(keep, saved):
             t.copy_(v)
         e.params_changed()
-        e.num_batches_tracked, (e.D.ticked, e.GE.ticked) = nbt, ticked
+        e.set_host_state(*host)
         torch.cuda.synchronize()
         e.capture_locked = True
 

@@ -1451,42 +1451,27 @@ class GanEngine:
     # -------------------------------------------------------------------------------------
     def run(self, name: str, use_graph: bool = True):
         """Run one of the sub-step methods (d_backward, d_update, g_step_rng, dg_step_rng, ...), replaying its hipGraph
-        when captured (the first call runs eagerly, which also warms every workspace)."""
+        when captured (the first call runs eagerly, which also warms every workspace).  What the sub-step's Python does
+        to host_state() is recorded at the capture and re-applied by each replay (ops.run_graphed); an update arriving
+        with its Adam state already advanced -- with or without the Philox counter to advance -- is a key of its own."""
         fn = getattr(self, name)
         if not use_graph:
             return fn()
-        # An update graph exists in several forms (Adam state advanced by the preceding draw -- with or without the
-        # Philox counter to advance -- or by itself); a replayed graph does not run the Python that tracks which one
-        # applies, so it is tracked here by sub-step name.
-        fp_upd = {"d_update": self.D, "g_update": self.GE, "d_update_g_critic_chain": self.D}.get(name)
-        key = name + (f"#{fp_upd.ticked}" if fp_upd is not None and fp_upd.ticked else "")
-        try:
-            return self._run_graph(key, fn)
-        finally:
-            if name.endswith("_step_rng"):                      # draw and update(s) both inside: nothing left pending
-                self.D.ticked = self.GE.ticked = False
-            elif name == "dg_forward_d_backward_rng":         # the fused draw: both updates are still to come
-                self.D.ticked, self.GE.ticked = True, "nobump"
-            elif name.endswith("_rng"):
-                (self.D if name.startswith("d_") else self.GE).ticked = True
-            if fp_upd is not None:
-                fp_upd.ticked = False
+        ops.run_graphed(self._graphs, name, fn, self, self._capture)
 
-    def _run_graph(self, name: str, fn):
-        st = ops.run_graphed(self._graphs, name, fn, lambda f: self._capture(name, f))
-        if st is not None:
-            self.num_batches_tracked += st[1]
+    def host_state(self):
+        """The host state the sub-steps change and a graph replay has to re-apply: (flags, counters)."""
+        return (self.D.ticked, self.GE.ticked), (self.num_batches_tracked,)
 
-    def _capture(self, name: str, fn):
-        """Capture fn's launches from the current stream into a hipGraph; returns (graph, BatchNorm forward passes it
-        contains -- num_batches_tracked is host state a replay does not touch)."""
-        if getattr(self, "capture_locked", False):
-            raise RuntimeError(f"GanEngine.run({name}): graph capture after DataParallel.prepare() -- every sub-step of "
-                               "a data-parallel run must be captured before the first collective is issued")
-        nbt = self.num_batches_tracked
-        g = ops.Graph.capture(fn)
-        delta, self.num_batches_tracked = self.num_batches_tracked - nbt, nbt
-        return g, delta                 # ops.run_graphed stores it under self._graphs[name]
+    def set_host_state(self, flags, counters):
+        (self.D.ticked, self.GE.ticked), (self.num_batches_tracked,) = flags, counters
+
+    def _capture(self, fn):
+        """ops.Graph.capture, refused once DataParallel.prepare() has locked the set of graphs."""
+        if self.capture_locked:
+            raise RuntimeError(f"GanEngine.run({fn.__name__}): graph capture after DataParallel.prepare() -- every sub-step "
+                               "of a data-parallel run must be captured before the first collective is issued")
+        return ops.Graph.capture(fn)
 
     # -------------------------------------------------------------------------------------
     # inference (app.py:92-119: E_num -> G in eval mode)

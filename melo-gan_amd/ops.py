@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -2792,19 +2792,51 @@ class Graph:
             pass
 
 
-def run_graphed(graphs: dict, key: str, fn, capture=Graph.capture):
-    """One call of a sub-step that is replayed as a hipGraph.  graphs[key] goes None -> "warm" -> captured: the first call
-    runs fn eagerly (which allocates every workspace and sets the function attributes), the second captures and launches,
-    later ones launch.  capture(fn) makes what is stored here -- a Graph, or GanEngine's (Graph, BatchNorm passes) -- and may
-    refuse.  Returns the stored entry when a graph was launched, None after the eager call."""
+class Captured(NamedTuple):
+    """A captured sub-step of an engine with host state: the Graph (entry[0].kernel_nodes) and the host effects its Python
+    had during the capture -- the flags as it left them, how far it advanced the counters."""
+    graph: Graph
+    flags: tuple
+    deltas: tuple
+
+    def launch(self):
+        self.graph.launch()
+
+    @property
+    def kernel_nodes(self):
+        return self.graph.kernel_nodes
+
+
+def run_graphed(graphs: dict, name: str, fn, host=None, capture=Graph.capture):
+    """One call of the sub-step `name` that is replayed as a hipGraph.  graphs[key] goes None -> "warm" -> captured: the
+    first call runs fn eagerly (which allocates every workspace and sets the function attributes), the second captures and
+    launches, later ones launch.  capture(fn) makes the Graph and may refuse.  Returns the stored entry when a graph was
+    launched, None after the eager call.
+
+    host: the engine whose host state fn's Python changes and later sub-steps read -- host_state() gives (flags,
+    counters), set_host_state(flags, counters) writes them.  A replay runs no Python, so the capture is the one source of
+    what to re-apply: the entry is a Captured with the flags fn left and the counters' advance, and every pure replay sets
+    those flags and advances the counters by as much.  The eager and the capturing call apply nothing: fn has just run.
+    A set flag (an optimiser step's pending launch form) selects launches, so the sub-step arriving with one has a graph of
+    its own: key = name#flags, plain `name` when none is set."""
+    flags, counters = host.host_state() if host is not None else ((), ())
+    key = name + ("#" + "/".join(map(str, flags)) if any(flags) else "")
     st = graphs.get(key)
     if st is None:
         fn()
         graphs[key] = "warm"
         return None
     if st == "warm":
-        st = graphs[key] = capture(fn)
-    (st[0] if isinstance(st, tuple) else st).launch()
+        st = capture(fn)
+        if host is not None:
+            left, after = host.host_state()
+            st = Captured(st, left, tuple(a - b for a, b in zip(after, counters)))
+        graphs[key] = st
+        st.launch()
+    else:
+        st.launch()
+        if host is not None:
+            host.set_host_state(st.flags, tuple(c + d for c, d in zip(counters, st.deltas)))
     return st
 
 

@@ -113,32 +113,113 @@ def test_spectral_norm_checkpoint_weights_fold_at_load():
 
 def test_run_graphed_goes_eager_then_captures_then_replays():
     """ops.run_graphed, the one copy of the training engines' None -> "warm" -> captured step, with a stand-in capture: the
-    dict keeps the format bench.py and the tests read ("warm", then what capture returned: a graph or a tuple led by one)."""
+    dict keeps the format bench.py and the tests read ("warm", then the graph -- or, for an engine with host state, a tuple
+    led by it that launches and counts kernel nodes like it)."""
     from melo_gan_amd import ops
 
-    class FakeGraph:
-        launches = 0
-
-        def launch(self):
-            self.launches += 1
-
-    for wrap in (lambda g: g, lambda g: (g, 2)):
+    for host in (None, FakeHost()):
         graphs, calls, g = {}, [], FakeGraph()
+        wrap = (lambda g: g) if host is None else (lambda g: (g, (False,), (0, 0)))
 
         def capture(fn):
             calls.append("capture")
-            return wrap(g)
+            return g
 
         fn = lambda: calls.append("eager")  # noqa: E731
-        assert ops.run_graphed(graphs, "k", fn, capture) is None and graphs == {"k": "warm"} and calls == ["eager"]
+        assert ops.run_graphed(graphs, "k", fn, host, capture) is None and graphs == {"k": "warm"} and calls == ["eager"]
         for n in (1, 2, 3):
-            assert ops.run_graphed(graphs, "k", fn, capture) is graphs["k"] and graphs["k"] == wrap(g) and g.launches == n
+            assert ops.run_graphed(graphs, "k", fn, host, capture) is graphs["k"] and graphs["k"] == wrap(g) and g.launches == n
+            assert graphs["k"].kernel_nodes == 7 and (host is None or isinstance(graphs["k"], tuple))
         assert calls == ["eager", "capture"]
         # a capture that raises leaves the key warm: the next call captures again
         graphs["j"] = "warm"
         with pytest.raises(RuntimeError):
-            ops.run_graphed(graphs, "j", fn, lambda f: (_ for _ in ()).throw(RuntimeError("locked")))
+            ops.run_graphed(graphs, "j", fn, host, lambda f: (_ for _ in ()).throw(RuntimeError("locked")))
         assert graphs["j"] == "warm"
+
+
+class FakeGraph:
+    launches, kernel_nodes = 0, 7
+
+    def launch(self):
+        self.launches += 1
+
+
+class FakeHost:
+    """The engines' side of ops.run_graphed: one flag and two counters."""
+
+    def __init__(self):
+        self.flag, self.n, self.updates = False, 0, 0
+
+    def host_state(self):
+        return (self.flag,), (self.n, self.updates)
+
+    def set_host_state(self, flags, counters):
+        (self.flag,), (self.n, self.updates) = flags, counters
+
+
+def fake_capture(fn):
+    """ops.Graph.capture as far as the host sees it: fn's Python runs once, nothing is launched."""
+    fn()
+    return FakeGraph()
+
+
+def test_run_graphed_replays_the_host_effects_of_the_capture():
+    """A captured entry carries what its sub-step's Python did to the host state during the capture and a replay re-applies
+    exactly that: after an eager call, the capturing call and three replays the state is what five eager calls leave, call by
+    call -- the capturing call adds nothing of its own (the counter moves by 1, never 2)."""
+    from melo_gan_amd import ops
+    graphs, host, eager = {}, FakeHost(), FakeHost()
+
+    def sub_step(h):
+        h.flag = not h.flag
+        h.n += 1
+        h.updates += 3
+
+    def draw(h):
+        h.flag = "nobump"
+
+    for call in range(5):
+        for h, run in ((eager, lambda name, fn: fn()), (host, lambda name, fn: ops.run_graphed(graphs, name, fn, host, fake_capture))):
+            h.flag = False
+            run("step", lambda: sub_step(h))          # arrives plain, leaves the flag set
+            assert h.host_state() == ((True,), (2 * call + 1, 6 * call + 3)), (call, h is host)
+            run("step", lambda: sub_step(h))          # the same name arriving with the flag pending: a graph of its own
+            run("draw", lambda: draw(h))
+        assert host.host_state() == eager.host_state() == (("nobump",), (2 * call + 2, 6 * call + 6)), call
+    assert set(graphs) == {"step", "step#True", "draw"} and all(k.split("#")[0] in ("step", "draw") for k in graphs)
+    assert all(g.launches == 4 for g, _, _ in graphs.values())
+    assert graphs["step"][1:] == ((True,), (1, 3)) and graphs["step#True"][1:] == ((False,), (1, 3))
+    assert graphs["draw"][1:] == (("nobump",), (0, 0))
+    # a capture that raises: the key stays warm and the state is as fn left it
+    host.flag = "nobump"
+    ops.run_graphed(graphs, "late", lambda: sub_step(host), host, fake_capture)
+    assert graphs["late#nobump"] == "warm" and host.host_state() == ((False,), (11, 33))
+
+    def refuse(fn):
+        fn()
+        raise RuntimeError("locked")
+    host.flag = "nobump"
+    with pytest.raises(RuntimeError):
+        ops.run_graphed(graphs, "late", lambda: sub_step(host), host, refuse)
+    assert graphs["late#nobump"] == "warm" and host.host_state() == ((False,), (12, 36))
+
+
+def test_set_lr_drops_the_graphs_whose_capture_saw_an_update():
+    """EdEngine.set_lr on stand-in entries: exactly the captured graphs whose record holds an optimiser step go -- by the
+    record, whatever the key -- and a tail engine follows."""
+    import types
+    from melo_gan_amd import ops
+    from melo_gan_amd.emotion_discriminator.engine import EdEngine
+    entry = lambda updates: ops.Captured(FakeGraph(), (False,), (updates,))  # noqa: E731
+    tail = types.SimpleNamespace(_graphs={"step_staged": entry(1), "forward_eval": entry(0)}, _tails={})
+    tail.set_lr = lambda lr: EdEngine.set_lr(tail, lr)
+    eng = types.SimpleNamespace(_tails={3: tail}, _graphs={
+        "step_rng": entry(1), "update#True": entry(1), "anything": entry(2), "backward_rng": entry(0), "forward_eval": entry(0),
+        "update": "warm"})
+    EdEngine.set_lr(eng, 0.5)
+    assert eng.lr == tail.lr == 0.5
+    assert set(eng._graphs) == {"backward_rng", "forward_eval", "update"} and set(tail._graphs) == {"forward_eval"}
 
 
 def test_graph_cache_rules(monkeypatch):
