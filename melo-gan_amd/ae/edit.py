@@ -44,11 +44,16 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from .. import ops
+from ..checkpoints import load_vae_checkpoint
+from ..eval_pass import CursorPass, Packed
+from ..gan.config import read_config
 from ..pieces import EMOTIONS, STYLE, add_wav_arguments, joined_notes, plan_wav, require_device, run_tool, write_pieces
 from . import latent_edit as LE
+from .engine import VaeEngine
+from .evaluate import AeEvaluateError, VaeEvaluator, _load_labels, _load_notes, _split_path
 
 DEFAULT_BATCH = 64
-SPLITS = ("val", "train", "test")
 JOIN_NOTES = 64
 
 
@@ -79,8 +84,6 @@ class LatentEditor:
     """One eval-mode VaeEngine of `batch` rows behind mg_latent_rows."""
 
     def __init__(self, cfg: dict, device="cuda", batch: int = DEFAULT_BATCH):
-        from ..eval_pass import CursorPass
-        from .engine import VaeEngine
         require_device(AeEditError)
         if int(batch) < 1 or int(batch) > 32767:
             raise AeEditError(f"batch = {batch}: must be in 1..32767")
@@ -101,25 +104,10 @@ class LatentEditor:
 
     def load(self, path: str):
         """The weights and BatchNorm buffers of train_ae's ae_best.pth / ae_final.pth, checked against the config first."""
-        from .encode import load_model
-        if not os.path.isfile(path):
-            raise AeEditError(f"checkpoint {path} does not exist")
-        eng = self.eng
-        ck = torch.load(path, map_location="cpu", weights_only=False)
-        sd = ck["model_state"] if isinstance(ck, dict) and "model_state" in ck else ck
-        if not isinstance(sd, dict):
-            raise AeEditError(f"{path}: neither a train_ae checkpoint nor a state_dict")
-        for k, shape in list(eng.P.spec.items()) + [(k, tuple(v.shape)) for k, v in eng.buf.items()]:
-            if k not in sd:
-                raise AeEditError(f"{path}: no '{k}': not a checkpoint of this VAE")
-            if tuple(sd[k].shape) != tuple(shape):
-                raise AeEditError(f"{path}: '{k}' has shape {tuple(sd[k].shape)}, the config (MAX_NOTES {eng.T}, LATENT_DIM "
-                                  f"{eng.latent}) implies {tuple(shape)}")
-        load_model(eng, path)
+        load_vae_checkpoint(self.eng, path, AeEditError)
 
     # ---- one chunk --------------------------------------------------------------------------------------------
     def _launches(self, seed: int, interp: int):
-        from .. import ops
         eng, B, a, c, ctr, base = self.eng, self.B, self.all, self.desc, self.cur.ctr, self.cur.base
         ops.stage_rows_cursor([(a[n], c[n]) for n, _, _ in DESCRIPTORS], B, None, a["kind"].shape[0], ctr, base)
         ops.latent_rows(self.mu, self.logvar, self.dirs, c["kind"], c["src_a"], c["src_b"], c["t"], c["dir"], c["alpha"], c["sigma"],
@@ -150,7 +138,6 @@ class LatentEditor:
         """The rows' latents, decodings and re-encodings.  notes: the resident split (n, MAX_NOTES, 4) the rows' sources index
         (None when there are none).  centroids: latent_edit.centroids()'s result, or its (K, K, L) difference table, whose row
         label * K + target a shift row names.  ed: emotion_discriminator.evaluate.EdEvaluator with its weights loaded."""
-        from ..eval_pass import Packed
         eng, B = self.eng, self.B
         d, Ld, T = eng.dev, eng.latent, eng.T
         if not isinstance(rows, LE.Rows) or rows.R < 1:
@@ -233,7 +220,6 @@ class LatentEditor:
         """The classifier over the resident results, in chunks of its own batch: `after` scores the decoded rolls (input_mode
         notes) or z (latent), `cycled` mu2 (latent only), `before` the identity row of each row's source.  Per row the
         probability of its target and of its source label and the prediction (mg_emotion_score) go into the packed result."""
-        from .. import ops
         e, d = ed.eng, self.res.dev
         dev, K, R_pad = e.dev, e.n_classes, d["z"].shape[0]
         latent = e.input_mode == "latent"
@@ -348,36 +334,6 @@ def parse_strengths(text: str) -> List[float]:
     return out
 
 
-def _split_path(cfg: dict, name: str) -> str:
-    return os.path.join(cfg.get("SPLITS_DIR", "data/splits"), name, "notes.npy") if name in SPLITS else name
-
-
-def _load_notes(path: str, T: int) -> np.ndarray:
-    if not os.path.isfile(path):
-        raise AeEditError(f"split array {path} does not exist")
-    try:
-        notes = np.ascontiguousarray(np.load(path), dtype=np.float32)
-    except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
-        raise AeEditError(f"cannot read {path}: {e}") from e
-    if notes.ndim != 3 or notes.shape[0] < 1 or tuple(notes.shape[1:]) != (T, 4):
-        raise AeEditError(f"{path}: an (n, {T}, 4) array with n >= 1 expected, got {notes.shape}")
-    return notes
-
-
-def _load_labels(path: str, n: int, K: int) -> np.ndarray:
-    from ..gan.utils import emotion_to_index
-    try:
-        emo = np.load(path, allow_pickle=True)
-    except Exception as e:      # noqa: BLE001
-        raise AeEditError(f"cannot read labels {path}: {e}") from e
-    if len(emo) != n:
-        raise AeEditError(f"{path} holds {len(emo)} entries, the split {n} rows")
-    idx = np.array([emotion_to_index(e) for e in emo], dtype=np.int64)
-    if ((idx < 0) | (idx >= K)).any():
-        raise AeEditError(f"{path}: labels outside [0, {K}) (unknown emotion names map to -1)")
-    return idx
-
-
 @dataclass
 class Plan:
     cfg: dict
@@ -407,7 +363,6 @@ class Plan:
 def plan(args) -> Plan:
     """Every check of what comes from outside, on the host (no GPU needed); raises AeEditError."""
     from .. import midi
-    from ..gan.config import load_config
     K = len(EMOTIONS)
     modes = [m for m, on in (("prior", args.prior is not None), ("vary", args.vary is not None), ("path", args.from_ is not None),
                              ("shift", args.shift is not None)) if on]
@@ -456,11 +411,7 @@ def plan(args) -> Plan:
         pieces = parse_rows(args.vary, "--vary")
     if (args.ed_ckpt is None) != (args.ed_config is None):
         raise AeEditError("--ed_config and --ed_ckpt go together")
-    if not os.path.isfile(args.config):
-        raise AeEditError(f"config {args.config} does not exist")
-    cfg = load_config(args.config)
-    if not isinstance(cfg, dict):
-        raise AeEditError(f"config {args.config} is not a YAML mapping")
+    cfg = read_config(args.config, "config", AeEditError)
     check_ae_config(cfg)
     T = int(cfg["MAX_NOTES"])
     notes = labels = c_notes = c_labels = c_source = None
@@ -471,11 +422,11 @@ def plan(args) -> Plan:
         source = f"synthetic:{args.synthetic}"
     elif mode != "prior":
         path = _split_path(cfg, args.split)
-        notes = _load_notes(path, T)
+        notes = _load_notes(path, T, AeEditError)
         source = path
         lp = args.labels or os.path.join(os.path.dirname(path), "emotion.npy")
         if os.path.isfile(lp):
-            labels = _load_labels(lp, notes.shape[0], K)
+            labels = _load_labels(lp, notes.shape[0], K, AeEditError)
         elif args.labels:
             raise AeEditError(f"labels {lp} do not exist")
     else:
@@ -500,11 +451,11 @@ def plan(args) -> Plan:
             c_notes, c_labels, c_source = notes, labels, source
         else:
             c_source = _split_path(cfg, args.centroids)
-            c_notes = _load_notes(c_source, T)
+            c_notes = _load_notes(c_source, T, AeEditError)
             clp = os.path.join(os.path.dirname(c_source), "emotion.npy")
             if not os.path.isfile(clp):
                 raise AeEditError(f"--centroids: {clp} does not exist: the class means need labels")
-            c_labels = _load_labels(clp, c_notes.shape[0], K)
+            c_labels = _load_labels(clp, c_notes.shape[0], K, AeEditError)
         for k in sorted({target} | {int(labels[p]) for p in pieces}):
             if not (c_labels == k).any():
                 raise AeEditError(f"--centroids: {c_source} has no row of class {EMOTIONS[k]}: it has no mean")
@@ -515,9 +466,7 @@ def plan(args) -> Plan:
             raise AeEditError(f"checkpoint {args.model} does not exist")
     ed_cfg = None
     if args.ed_config is not None:
-        if not os.path.isfile(args.ed_config):
-            raise AeEditError(f"ED config {args.ed_config} does not exist")
-        ed_cfg = load_config(args.ed_config)
+        ed_cfg = read_config(args.ed_config, "ED config", AeEditError)
         if not os.path.isfile(args.ed_ckpt):
             raise AeEditError(f"ED checkpoint {args.ed_ckpt} does not exist")
     out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/ae"), "ae_edit")
@@ -591,7 +540,6 @@ def run(p: Plan) -> dict:
         check_classifier(cls.eng, ed.eng.T, ed.eng.latent)
     cent = counts = None
     if p.mode == "shift":
-        from .evaluate import AeEvaluateError, VaeEvaluator
         try:
             ev = VaeEvaluator(p.cfg, "cuda", p.batch, share=ed.eng, n_classes=len(EMOTIONS))
             ev.evaluate(torch.from_numpy(p.centroid_notes).cuda(), torch.from_numpy(p.centroid_labels).cuda())

@@ -15,14 +15,13 @@ from pathlib import Path
 import numpy as np
 import torch
 
+from ..checkpoints import load_vae_checkpoint
 from ..gan.config import load_config
 from .engine import VaeEngine
 
 
 def load_model(eng: VaeEngine, path: str):
-    ckpt = torch.load(path, map_location="cpu", weights_only=False)
-    sd = ckpt["model_state"] if "model_state" in ckpt else ckpt          # encode.py:118-119
-    eng.load_state({k: sd[k] for k in eng.P.spec}, {k: sd[k] for k in eng.buf})
+    load_vae_checkpoint(eng, path, ValueError)
 
 
 @torch.no_grad()

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from .. import ops
-from ..gan.engine import FlatParams, BN_EPS, BN_MOM, norm_buffers
+from ..params import FlatParams, BN_EPS, BN_MOM, norm_buffers
 from ..ops import ACT_RELU, ACT_TANH
 
 ENC = ((0, 4, 32), (3, 32, 64), (6, 64, 128))       # (index in encoder.conv, Cin, Cout)
@@ -117,6 +117,15 @@ class VaeEngine:
         self.P.load(P)
         for k in self.buf:
             self.buf[k].copy_(Bf[k])
+
+    def state_dict(self):
+        """The reference VAE's state_dict() (CPU): ae_final.pth as it is, ae_best.pth's `model_state`."""
+        sd = self.P.state_dict()
+        for k, v in self.buf.items():
+            sd[k] = v.cpu().clone()
+            if k.endswith("running_var"):
+                sd[k.replace("running_var", "num_batches_tracked")] = torch.tensor(self.num_batches_tracked, dtype=torch.int64)
+        return sd
 
     def init_weights(self, seed: int = 42):
         """torch default initialisers are what the reference uses for the VAE (no weights_init in train_ae.py)."""

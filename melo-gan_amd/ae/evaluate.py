@@ -26,12 +26,12 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..gan.config import load_config
-from ..gan.utils import emotion_to_index
+from ..checkpoints import load_vae_checkpoint
+from ..gan.config import read_config
+from ..gan.utils import label_indices
 from ..pieces import EMOTIONS, require_device
 from ..eval_pass import Packed, ResidentPass, check_split
 from . import metrics as M
-from .encode import load_model
 from .engine import VaeEngine
 
 DEFAULT_BATCH = 64
@@ -74,19 +74,8 @@ class VaeEvaluator:
         self.acc_host = self.rows = None
 
     def load(self, path: str):
-        """The weights and BatchNorm buffers of train_ae's ae_best.pth / ae_final.pth (encode.load_model)."""
-        if not os.path.isfile(path):
-            raise AeEvaluateError(f"checkpoint {path} does not exist")
-        eng = self.eng
-        ck = torch.load(path, map_location="cpu", weights_only=False)
-        sd = ck["model_state"] if isinstance(ck, dict) and "model_state" in ck else ck
-        for k, shape in list(eng.P.spec.items()) + [(k, tuple(v.shape)) for k, v in eng.buf.items()]:
-            if k not in sd:
-                raise AeEvaluateError(f"{path}: no '{k}': not a checkpoint of this VAE")
-            if tuple(sd[k].shape) != tuple(shape):
-                raise AeEvaluateError(f"{path}: '{k}' has shape {tuple(sd[k].shape)}, the config (MAX_NOTES {eng.T}, LATENT_DIM "
-                                      f"{eng.latent}) implies {tuple(shape)}")
-        load_model(eng, path)
+        """The weights and BatchNorm buffers of train_ae's ae_best.pth / ae_final.pth, checked against the config first."""
+        load_vae_checkpoint(self.eng, path, AeEvaluateError)
 
     def _launches(self, jobs, order, order_len, keep_recon, metrics=True):
         """One batch.  metrics=False leaves the accumulation out (the pass is then timed without it; the cursor is the
@@ -136,16 +125,32 @@ class VaeEvaluator:
         return rep
 
 
-def _load_labels(path: str, n: int, K: int) -> np.ndarray:
+def _split_path(cfg: dict, name: str) -> str:
+    return os.path.join(cfg.get("SPLITS_DIR", "data/splits"), name, "notes.npy") if name in SPLITS else name
+
+
+def _load_notes(path: str, T: int, err) -> np.ndarray:
+    if not os.path.isfile(path):
+        raise err(f"split array {path} does not exist")
+    try:
+        notes = np.ascontiguousarray(np.load(path), dtype=np.float32)
+    except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
+        raise err(f"cannot read {path}: {e}") from e
+    if notes.ndim != 3 or notes.shape[0] < 1 or tuple(notes.shape[1:]) != (T, 4):
+        raise err(f"{path}: an (n, {T}, 4) array with n >= 1 expected, got {notes.shape}")
+    return notes
+
+
+def _load_labels(path: str, n: int, K: int, err) -> np.ndarray:
     try:
         emo = np.load(path, allow_pickle=True)
-    except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
-        raise AeEvaluateError(f"cannot read labels {path}: {e}") from e
+    except Exception as e:      # noqa: BLE001
+        raise err(f"cannot read labels {path}: {e}") from e
     if len(emo) != n:
-        raise AeEvaluateError(f"{path} holds {len(emo)} entries, the split {n} rows")
-    idx = np.array([emotion_to_index(e) for e in emo], dtype=np.int64)
+        raise err(f"{path} holds {len(emo)} entries, the split {n} rows")
+    idx = label_indices(emo, None).numpy()
     if ((idx < 0) | (idx >= K)).any():
-        raise AeEvaluateError(f"{path}: labels outside [0, {K}) (unknown emotion names map to -1)")
+        raise err(f"{path}: labels outside [0, {K}) (unknown emotion names map to -1)")
     return idx
 
 
@@ -166,9 +171,7 @@ def parse_args(argv=None):
 def run(args) -> dict:
     from ..midi import save_recon_midi
     require_device(AeEvaluateError)
-    if not os.path.isfile(args.config):
-        raise AeEvaluateError(f"config {args.config} does not exist")
-    cfg = load_config(args.config)
+    cfg = read_config(args.config, "config", AeEvaluateError)
     if args.recon_midi < 0:
         raise AeEvaluateError("--recon-midi must be >= 0")
     ev = VaeEvaluator(cfg, "cuda", args.batch)
@@ -183,20 +186,14 @@ def run(args) -> dict:
     else:
         if args.model is None:
             raise AeEvaluateError("give --model (or --synthetic N)")
-        path = args.split
-        if args.split in SPLITS:
-            path = os.path.join(cfg.get("SPLITS_DIR", "data/splits"), args.split, "notes.npy")
-        if not os.path.isfile(path):
-            raise AeEvaluateError(f"split array {path} does not exist")
-        notes = torch.from_numpy(np.ascontiguousarray(np.load(path), dtype=np.float32))
+        path = _split_path(cfg, args.split)
+        notes = torch.from_numpy(_load_notes(path, T, AeEvaluateError))
         labels_path = args.labels or os.path.join(os.path.dirname(path), "emotion.npy")
         if args.labels and not os.path.isfile(labels_path):
             raise AeEvaluateError(f"labels {labels_path} do not exist")
-        idx = _load_labels(labels_path, notes.shape[0], K) if os.path.isfile(labels_path) else None
+        idx = _load_labels(labels_path, notes.shape[0], K, AeEvaluateError) if os.path.isfile(labels_path) else None
         ev.load(args.model)
         source = path
-    if notes.dim() != 3 or notes.shape[0] < 1:
-        raise AeEvaluateError(f"{source}: an (n, {T}, 4) array with n >= 1 expected, got {tuple(notes.shape)}")
     dev_notes = notes.cuda()
     dev_labels = None if idx is None else torch.from_numpy(idx).cuda()
     rep = ev.evaluate(dev_notes, dev_labels, keep_recon=args.recon_midi > 0, names=EMOTIONS)

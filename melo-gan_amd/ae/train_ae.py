@@ -27,6 +27,7 @@ from .. import ops
 from ..midi import save_recon_midi
 from ..gan.config import load_config
 from ..gan.train_gan import _scalar_writer
+from ..gan.utils import label_indices
 from .engine import VaeEngine
 
 
@@ -35,15 +36,6 @@ def _load_split(cfg, name, device):
     if not os.path.exists(p):
         raise FileNotFoundError(f"{p} not found (export the split's normalised notes to one array, or use --synthetic)")
     return torch.from_numpy(np.load(p).astype(np.float32)).to(device)
-
-
-def state_dict(eng: VaeEngine):
-    sd = eng.P.state_dict()
-    for k, v in eng.buf.items():
-        sd[k] = v.cpu().clone()
-        if k.endswith("running_var"):
-            sd[k.replace("running_var", "num_batches_tracked")] = torch.tensor(eng.num_batches_tracked, dtype=torch.int64)
-    return sd
 
 
 def augment_from_cfg(cfg, seed: int = 0):
@@ -58,14 +50,13 @@ def augment_from_cfg(cfg, seed: int = 0):
 
 def _val_labels(cfg, n, device):
     """The validation split's class indices for --eval-every, or None without <SPLITS_DIR>/val/emotion.npy."""
-    from ..gan.utils import emotion_to_index
     p = os.path.join(cfg.get("SPLITS_DIR", "data/splits"), "val", "emotion.npy")
     if not os.path.exists(p):
         return None
-    idx = np.array([emotion_to_index(e) for e in np.load(p, allow_pickle=True)], dtype=np.int64)
+    idx = label_indices(np.load(p, allow_pickle=True), None)       # unchecked here: the evaluator refuses what lies outside
     if len(idx) != n:
         raise ValueError(f"{p} holds {len(idx)} entries, the validation split {n} rows")
-    return torch.from_numpy(idx).to(device)
+    return idx.to(device)
 
 
 def train(cfg, synthetic: int = 0, eval_every: int = 0):
@@ -161,7 +152,7 @@ def train(cfg, synthetic: int = 0, eval_every: int = 0):
                     save_recon_midi(val_x[j].cpu().numpy(), e1.recon[0].cpu().numpy(), recon_dir, f"ep{epoch}_val{j:03d}")
             if va[0] < best_val:
                 best_val, no_improve = va[0], 0
-                torch.save({"epoch": epoch, "model_state": state_dict(eng)}, os.path.join(model_dir, "ae_best.pth"))
+                torch.save({"epoch": epoch, "model_state": eng.state_dict()}, os.path.join(model_dir, "ae_best.pth"))
                 print("Saved new best model ->", os.path.join(model_dir, "ae_best.pth"))
             else:
                 no_improve += 1
@@ -170,7 +161,7 @@ def train(cfg, synthetic: int = 0, eval_every: int = 0):
                 break
     writer.close()
     print("Training complete. Best val:", best_val)
-    torch.save(state_dict(eng), os.path.join(model_dir, "ae_final.pth"))
+    torch.save(eng.state_dict(), os.path.join(model_dir, "ae_final.pth"))
     return eng
 
 

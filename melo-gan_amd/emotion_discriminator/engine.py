@@ -25,7 +25,7 @@ import torch
 
 from .. import ops
 from ..ops import ACT_GELU
-from ..gan.engine import FlatParams, emotion_disc_spec, norm_buffers
+from ..params import FlatParams, emotion_disc_spec, norm_buffers
 from .layers import tail_bwd, tail_fwd
 
 Tensor = torch.Tensor

@@ -29,7 +29,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..gan.config import load_config
+from ..checkpoints import ed_state_shapes, read_ed_state, state_mismatches
+from ..gan.config import read_config
 from ..eval_pass import Packed, ResidentPass, check_split
 from ..pieces import EMOTIONS, require_device
 from . import metrics as M
@@ -100,24 +101,17 @@ class EdEvaluator:
         """train_ed's ed_best.pth / ed_epochNNN.pth ({"model": state_dict, ...}), or a bare state_dict (the reference's
         EmotionDiscriminator.state_dict(), weight_orig / _u / _v under spectral norm).  Every key and shape is checked
         against the config first."""
-        if not os.path.isfile(path):
-            raise EdEvaluateError(f"checkpoint {path} does not exist")
-        ck = torch.load(path, map_location="cpu", weights_only=False)
-        sd = ck["model"] if isinstance(ck, dict) and isinstance(ck.get("model"), dict) else ck
-        if not isinstance(sd, dict):
-            raise EdEvaluateError(f"{path}: neither a train_ed checkpoint nor a state_dict")
-        self.load_state(sd, path)
+        # weights_only=False, as this tool always read it: an ed_best.pth carries the training config, whatever its YAML held
+        self.load_state(read_ed_state(path, EdEvaluateError, weights_only=False), path)
 
     def load_state(self, sd: dict, where: str = "state_dict"):
         eng = self.eng
-        for k, v in eng.state_dict().items():
-            if k.endswith("num_batches_tracked"):
-                continue
-            if k not in sd:
-                raise EdEvaluateError(f"{where}: no '{k}': not a checkpoint of this classifier (input_mode {eng.input_mode}, "
-                                      f"use_spectral_norm {bool(eng.sn_names)})")
-            if tuple(sd[k].shape) != tuple(v.shape):
-                raise EdEvaluateError(f"{where}: '{k}' has shape {tuple(sd[k].shape)}, the config implies {tuple(v.shape)}")
+        missing, bad = state_mismatches(sd, ed_state_shapes(eng.cfg, eng.sn_names))
+        if missing:
+            raise EdEvaluateError(f"{where}: no '{missing[0]}': not a checkpoint of this classifier (input_mode {eng.input_mode}, "
+                                  f"use_spectral_norm {bool(eng.sn_names)})")
+        if bad:
+            raise EdEvaluateError("{}: '{}' has shape {}, the config implies {}".format(where, *bad[0]))
         eng.load_state(sd)          # in place: captured graphs keep their addresses
         self.acc_host = None
 
@@ -298,9 +292,7 @@ def load_rows(cfg: dict, split: str, synthetic: int, seed: int, device):
 
 def run(args) -> dict:
     require_device(EdEvaluateError)
-    if not os.path.isfile(args.config):
-        raise EdEvaluateError(f"config {args.config} does not exist")
-    cfg = load_config(args.config)
+    cfg = read_config(args.config, "config", EdEvaluateError)
     if args.robustness < 0:
         raise EdEvaluateError("--robustness must be >= 0")
     if args.synthetic < 0:

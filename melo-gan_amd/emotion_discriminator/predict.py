@@ -27,6 +27,7 @@ import sys
 from dataclasses import dataclass
 
 from .. import midi_rolls as MR
+from ..gan.config import read_config
 from ..pieces import require_device, run_tool
 
 DEFAULT_BATCH, MAX_CLASSES, DEFAULT_MIN_EVENTS = 64, 32, MR.DEFAULT_MIN_EVENTS
@@ -60,10 +61,7 @@ def check_batch(batch, err):
 
 def load_tool_inputs(args, err, check) -> dict:
     """The config of --config, which must exist and pass check(cfg); --model must be given and exist, --batch be in range."""
-    from ..gan.config import load_config
-    if not os.path.isfile(args.config):
-        raise err(f"config {args.config} does not exist")
-    cfg = load_config(args.config)
+    cfg = read_config(args.config, "config", err)
     check(cfg)
     if args.model is None:
         raise err("give --model")

@@ -37,7 +37,7 @@ import torch
 
 from .. import ops
 from ..gan import config as C
-from ..gan.utils import check_labels, emotion_to_index, seed_everything
+from ..gan.utils import label_indices, seed_everything
 from .engine import EdEngine
 from .latent_engine import make_engine
 
@@ -76,8 +76,7 @@ def load_split(cfg: dict, split: str, device):
         raise FileNotFoundError(f"{paths}: export the split to notes.npy / emotion.npy (the per-file .npz loader of the "
                                 "reference is not implemented)")
     notes = torch.from_numpy(np.ascontiguousarray(np.load(paths[0]), dtype=np.float32)).to(device)
-    labels = check_labels(torch.tensor([emotion_to_index(e) for e in np.load(paths[1], allow_pickle=True)], dtype=torch.int64),
-                          int(cfg.get("n_classes", 4)), f"{split} split labels").to(device)
+    labels = label_indices(np.load(paths[1], allow_pickle=True), int(cfg.get("n_classes", 4)), f"{split} split labels").to(device)
     return notes, labels
 
 
@@ -114,9 +113,9 @@ def load_latent_split(cfg: dict, split: str, device):
         if not os.path.exists(p):
             raise FileNotFoundError(f"{p}: export the split's latents / labels to encoder_feats.npy (melo_gan_amd.ae.encode) and "
                                     "emotion.npy")
-    labels = [emotion_to_index(e) for e in np.load(lab_path, allow_pickle=True)]
-    feats, labels = latent_rows(np.load(path, allow_pickle=True), labels, int(cfg.get("latent_dim", 128)), path)
-    labels = check_labels(torch.tensor(labels, dtype=torch.int64), int(cfg.get("n_classes", 4)), f"{split} split labels")
+    feats, emotions = latent_rows(np.load(path, allow_pickle=True), np.load(lab_path, allow_pickle=True), int(cfg.get("latent_dim", 128)),
+                                  path)
+    labels = label_indices(emotions, int(cfg.get("n_classes", 4)), f"{split} split labels")      # of the rows that are left
     return torch.from_numpy(feats).to(device), labels.to(device)
 
 

@@ -5,6 +5,8 @@ gan_config.yaml keys and their `cfg.get` defaults: /root/reference/src/gan/train
 """
 from __future__ import annotations
 
+import os
+
 import yaml
 
 # code defaults of the reference trainer (the YAML file may override any of them)
@@ -20,6 +22,16 @@ def load_config(path: str) -> dict:
     """train_gan.py:35-37."""
     with open(path) as f:
         return yaml.safe_load(f)
+
+
+def read_config(path: str, what: str, err) -> dict:
+    """load_config for a tool: `what` (config, ED config) must exist and hold a YAML mapping, else err."""
+    if not os.path.isfile(path):
+        raise err(f"{what} {path} does not exist")
+    cfg = load_config(path)
+    if not isinstance(cfg, dict):
+        raise err(f"{what} {path} is not a YAML mapping")
+    return cfg
 
 
 def with_gan_defaults(cfg: dict, require: bool = True) -> dict:

@@ -9,16 +9,18 @@ from typing import Optional
 
 import torch
 
+from .. import ops
+from ..checkpoints import check_generator_checkpoint, ema_checkpoint, load_ed_checkpoint, load_generator_state, read_checkpoint
 from ..eval_pass import GraphCache
+from ..pieces import EMOTIONS
 from . import config as C
+from .engine import GanEngine
 
 
 class EvalEngine:
     """Abstract: a subclass sets `error` (GenerateError or EvaluateError: what every check here raises) and _check_config."""
 
     def __init__(self, cfg: dict, ed_cfg: Optional[dict], device, batch: int):
-        from .engine import GanEngine
-        from .generate import EMOTIONS
         if int(batch) < 1:
             raise self.error(f"batch = {batch}: must be >= 1")
         cfg = {"LR_G": 0.0, "LR_D": 0.0, **C.with_gan_defaults(cfg, require=False)}      # the rates are never used here
@@ -39,17 +41,14 @@ class EvalEngine:
 
     def _read(self, ck):
         """A checkpoint dict or path (gan_final.pth, gan_epochNNNN.pth; this trainer's or the reference's) -> (dict, name)."""
-        from .generate import load_checkpoint
-        if isinstance(ck, (str, os.PathLike)):
-            return load_checkpoint(str(ck), err=self.error), str(ck)
+        if isinstance(ck, (str, os.PathLike)):      # weights_only=None, torch's default: a GAN file holds tensors and numbers
+            return read_checkpoint(str(ck), self.error, weights_only=None), str(ck)
         return ck, "checkpoint"
 
     def load_generator(self, ck, ema: bool = False) -> str:
         """G (with its BatchNorm running statistics) and E_num from a checkpoint dict or path.  ema: the averaged weights and
         their recalibrated statistics from a full checkpoint's `ema` block instead (a *_ema.pth file is an ordinary {G, E_num}
         file and needs no flag).  Returns which weights were loaded: "ema" or "raw"."""
-        from .generate import check_generator_checkpoint
-        from .train_gan import load_generator_state
         ck, path = self._read(ck)
         if ema:
             ck = ema_checkpoint(ck, path, self.error)
@@ -77,23 +76,11 @@ class EvalEngine:
 
     def load_ed(self, path: str):
         """The frozen classifier (train_ed's ed_best.pth or a bare state_dict; spectral-norm keys folded)."""
-        from .train_gan import load_ed_checkpoint
         if not self.has_ed:
             raise self.error(f"this {type(self).__name__} was built without an ED config")
         if not os.path.isfile(path):
             raise self.error(f"ED checkpoint {path} does not exist")
         load_ed_checkpoint(self.eng, path)
-
-
-def ema_checkpoint(ck, path: str, err) -> dict:
-    """{'G', 'E_num'} of a full checkpoint's `ema` block (train_gan.save_checkpoint), for check_generator_checkpoint and
-    load_generator_state; raises err, naming the file, when the checkpoint has none."""
-    blk = ck.get("ema") if isinstance(ck, dict) else None
-    if not isinstance(blk, dict) or "G" not in blk or "E_num" not in blk:
-        have = sorted(ck) if isinstance(ck, dict) else type(ck).__name__
-        raise err(f"{path}: no averaged weights in this checkpoint (--ema reads the 'ema' block of a full gan_epochNNNN.pth "
-                  f"written with EMA_DECAY > 0; has {have}).  A *_ema.pth file loads without the flag")
-    return {"G": blk["G"], "E_num": blk["E_num"]}
 
 
 def recalibrate_bn(eval_engine: EvalEngine, dataset, seed: int) -> bool:
@@ -106,7 +93,6 @@ def recalibrate_bn(eval_engine: EvalEngine, dataset, seed: int) -> bool:
     torch's momentum=None cumulative average -- so that the buffers end as the plain mean over the batches of the per-batch
     mean and unbiased variance.  Host code over existing kernels; writes this engine's buffers and activations only.
     n < B: the buffers stay as they are, a [WARN] is printed, returns False."""
-    from .. import ops
     eng, B = eval_engine.eng, eval_engine.B
     n = len(dataset)
     k = n // B

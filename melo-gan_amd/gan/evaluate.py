@@ -53,11 +53,13 @@ import torch
 from . import feature_metrics as FM
 from . import generate as G
 from . import music_metrics as MM
+from ..checkpoints import check_critic_checkpoint, check_generator_checkpoint, ema_checkpoint, read_checkpoint
 from ..eval_pass import Packed, ResidentPass
 from ..pieces import require_device
+from .config import read_config
 from .eval_engine import EvalEngine
 from .generate import EMOTIONS, GenerateError
-from .utils import check_labels, emotion_to_index
+from .utils import label_indices
 
 DEFAULT_BATCH = 64
 DEFAULT_KNN_K, MAX_KNN_K = 3, 8
@@ -119,17 +121,8 @@ def check_music_options(music: bool, cfg: dict, batch: int = DEFAULT_BATCH):
 
 def check_checkpoint(ck, cfg: dict, path: str = "checkpoint") -> bool:
     """G and E_num as the sampler needs them; returns whether the checkpoint also holds a critic ('D') of the config's shapes."""
-    from .engine import discriminator_spec
-    G.check_generator_checkpoint(ck, cfg, path, err=EvaluateError)
-    if "D" not in ck:
-        return False
-    spec = discriminator_spec(int(cfg["NOTE_DIM"]), 256, int(cfg.get("ENCODER_OUT_DIM", 128)))
-    for k, shape in spec.items():
-        if k not in ck["D"]:
-            raise EvaluateError(f"{path}: D lacks {k}")
-        if tuple(ck["D"][k].shape) != tuple(shape):
-            raise EvaluateError(f"{path}: D.{k} has shape {tuple(ck['D'][k].shape)}, the GAN config implies {tuple(shape)}")
-    return True
+    check_generator_checkpoint(ck, cfg, path, EvaluateError)
+    return check_critic_checkpoint(ck, cfg, path, EvaluateError)
 
 
 def check_split_arrays(notes, emotions, numeric, latent, cfg: dict, where: str = "split"):
@@ -147,8 +140,7 @@ def check_split_arrays(notes, emotions, numeric, latent, cfg: dict, where: str =
     if latent is not None and tuple(latent.shape) != (n, ld):
         raise EvaluateError(f"{where}: encoder features have shape {tuple(latent.shape)}, expected ({n}, {ld})")
     try:
-        return check_labels(torch.tensor([emotion_to_index(e) for e in emotions], dtype=torch.int64), len(EMOTIONS),
-                            f"{where}: emotion labels")
+        return label_indices(emotions, len(EMOTIONS), f"{where}: emotion labels")
     except ValueError as e:
         raise EvaluateError(str(e)) from e
 
@@ -596,15 +588,14 @@ def plan(args) -> Plan:
                             "(a multiple of 4 in 4..1024)")
     music = bool(getattr(args, "music_metrics", False))
     check_music_options(music, cfg, args.batch)
-    ckpt = G.load_checkpoint(ckpt_path, err=EvaluateError)
+    ckpt = read_checkpoint(ckpt_path, EvaluateError, weights_only=None)      # torch's default: a GAN file holds tensors and numbers
     has_critic = check_checkpoint(ckpt, cfg, ckpt_path)
     ema = bool(getattr(args, "ema", False))
     if ema:
-        from .eval_engine import ema_checkpoint
-        G.check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, EvaluateError), cfg, ckpt_path, err=EvaluateError)
+        check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, EvaluateError), cfg, ckpt_path, EvaluateError)
     ed_cfg = None
     if args.ed_config is not None:
-        ed_cfg = G._read_config(args.ed_config, "ED config", EvaluateError)
+        ed_cfg = read_config(args.ed_config, "ED config", EvaluateError)
         check_ed_config(ed_cfg, cfg, f"ED config {args.ed_config}")
         check_feature_options(features, knn_k, ed_cfg)
         if not os.path.isfile(args.ed_ckpt):

@@ -37,6 +37,7 @@ import numpy as np
 import torch
 
 from .. import pieces
+from ..checkpoints import check_generator_checkpoint, ema_checkpoint, read_checkpoint
 from ..pieces import EMOTIONS, STYLE           # also for those who read generate.EMOTIONS and generate.STYLE
 from . import config as C
 from .eval_engine import EvalEngine
@@ -86,36 +87,6 @@ def check_ed_config(ed_cfg: dict, cfg: dict, err=GenerateError, prefix: str = ""
                       f"{cfg['LATENT_DIM']}")
     else:
         raise err(f"{prefix}ED config: input_mode = {mode!r}, expected 'notes' or 'latent'")
-
-
-def check_generator_checkpoint(ck, cfg: dict, path: str = "checkpoint", err=GenerateError):
-    """A dict with 'G' (with its BatchNorm running statistics) and 'E_num' whose tensors have the shapes the config implies."""
-    from .engine import feature_encoder_spec, generator_spec
-    if not isinstance(ck, dict) or "G" not in ck or "E_num" not in ck:
-        have = sorted(ck) if isinstance(ck, dict) else type(ck).__name__
-        raise err(f"{path}: not a generator checkpoint (needs 'G' and 'E_num'; has {have})")
-    gspec = generator_spec(int(cfg["NOISE_DIM"]), int(cfg["LATENT_DIM"]), cfg.get("INTEGRATION_MODE", "conditioning"), 512,
-                           int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg.get("ENCODER_OUT_DIM", 128)))
-    for bn, ch in (("decoder.deconv.1", 128), ("decoder.deconv.4", 64)):
-        gspec[bn + ".running_mean"] = gspec[bn + ".running_var"] = (ch,)
-    espec = feature_encoder_spec(int(cfg.get("NUMERIC_INPUT_DIM", 6)), tuple(cfg.get("ENCODER_HIDDEN", [256, 128])),
-                                 int(cfg.get("ENCODER_OUT_DIM", 128)))
-    for part, spec in (("G", gspec), ("E_num", espec)):
-        sd = ck[part]
-        for k, shape in spec.items():
-            if k not in sd:
-                raise err(f"{path}: {part} lacks {k}")
-            if tuple(sd[k].shape) != tuple(shape):
-                raise err(f"{path}: {part}.{k} has shape {tuple(sd[k].shape)}, the GAN config implies {tuple(shape)}")
-
-
-def load_checkpoint(path: str, err=GenerateError) -> dict:
-    if not os.path.isfile(path):
-        raise err(f"checkpoint {path} does not exist")
-    try:
-        return torch.load(path, map_location="cpu")
-    except Exception as e:      # noqa: BLE001 -- any unreadable file is the same user error
-        raise err(f"cannot read checkpoint {path}: {e}") from e
 
 
 @dataclass
@@ -235,19 +206,10 @@ class Plan:
     wav: Optional[dict] = None          # --wav: {"fs", "voice", "peak_db"}
 
 
-def _read_config(path: str, what: str, err=GenerateError) -> dict:
-    if not os.path.isfile(path):
-        raise err(f"{what} {path} does not exist")
-    cfg = C.load_config(path)
-    if not isinstance(cfg, dict):
-        raise err(f"{what} {path} is not a YAML mapping")
-    return cfg
-
-
 def plan_config(args, err=GenerateError):
     """What generate's and evaluate's command lines share: the GAN config with its defaults and the keys every later check
     reads, the pairing of --ed_ckpt with --ed_config, and the checkpoint's path.  Returns (cfg, checkpoint path)."""
-    cfg = C.with_gan_defaults(_read_config(args.config, "config", err), require=False)
+    cfg = C.with_gan_defaults(C.read_config(args.config, "config", err), require=False)
     missing = [k for k in ("NOISE_DIM", "LATENT_DIM", "MAX_NOTES", "NOTE_DIM") if k not in cfg]
     if missing:
         raise err(f"config {args.config} lacks {', '.join(missing)}")
@@ -270,16 +232,12 @@ def plan(args) -> Plan:
     check_gan_config(cfg)
     if int(cfg["NOTE_DIM"]) != 4:
         raise GenerateError(f"NOTE_DIM = {cfg['NOTE_DIM']}: the MIDI writer reads (pitch, velocity, duration, step) rows")
-    ckpt = load_checkpoint(ckpt_path)
+    ckpt = read_checkpoint(ckpt_path, GenerateError, weights_only=None)      # torch's default: a GAN file holds tensors and numbers
     ema = bool(getattr(args, "ema", False))
-    if ema:
-        from .eval_engine import ema_checkpoint
-        check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, GenerateError), cfg, ckpt_path)
-    else:
-        check_generator_checkpoint(ckpt, cfg, ckpt_path)
+    check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, GenerateError) if ema else ckpt, cfg, ckpt_path, GenerateError)
     ed_cfg = None
     if args.ed_config is not None:
-        ed_cfg = _read_config(args.ed_config, "ED config")
+        ed_cfg = C.read_config(args.ed_config, "ED config", GenerateError)
         check_ed_config(ed_cfg, cfg)
         if not os.path.isfile(args.ed_ckpt):
             raise GenerateError(f"ED checkpoint {args.ed_ckpt} does not exist")

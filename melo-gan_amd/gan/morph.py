@@ -39,11 +39,12 @@ import numpy as np
 import torch
 
 from .. import pieces
+from ..checkpoints import check_generator_checkpoint, ema_checkpoint, read_checkpoint
 from ..pieces import EMOTIONS, STYLE, joined_notes          # joined_notes also for those who read morph.joined_notes
 from . import morph_metrics as MM
+from .config import read_config
 from .eval_engine import EvalEngine
-from .generate import (DEFAULT_BATCH, EMOTION_TABLE, JITTER, GenerateError, _read_config, check_ed_config, check_gan_config,
-                       check_generator_checkpoint, load_checkpoint, plan_config)
+from .generate import DEFAULT_BATCH, EMOTION_TABLE, JITTER, GenerateError, check_ed_config, check_gan_config, plan_config
 
 NOISE_MODES = ("fixed", "slerp")
 
@@ -333,15 +334,11 @@ def plan(args) -> Plan:
     if files and int(cfg["NOTE_DIM"]) != 4:
         raise MorphError(f"NOTE_DIM = {cfg['NOTE_DIM']}: the MIDI writer reads (pitch, velocity, duration, step) rows (--no-files "
                          "reports without writing any)")
-    ckpt = load_checkpoint(ckpt_path, MorphError)
-    if args.ema:
-        from .eval_engine import ema_checkpoint
-        check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, MorphError), cfg, ckpt_path, MorphError)
-    else:
-        check_generator_checkpoint(ckpt, cfg, ckpt_path, MorphError)
+    ckpt = read_checkpoint(ckpt_path, MorphError, weights_only=None)         # torch's default: a GAN file holds tensors and numbers
+    check_generator_checkpoint(ema_checkpoint(ckpt, ckpt_path, MorphError) if args.ema else ckpt, cfg, ckpt_path, MorphError)
     ed_cfg = None
     if args.ed_config is not None:
-        ed_cfg = _read_config(args.ed_config, "ED config", MorphError)
+        ed_cfg = read_config(args.ed_config, "ED config", MorphError)
         check_ed_config(ed_cfg, cfg, MorphError)
         if not os.path.isfile(args.ed_ckpt):
             raise MorphError(f"ED checkpoint {args.ed_ckpt} does not exist")

@@ -26,10 +26,9 @@ import json
 import os
 import time
 
-from collections import OrderedDict
-
 import torch
 
+from ..checkpoints import ema_block, load_ed_checkpoint, resume_checkpoint, save_checkpoint, save_ema_final
 from . import config as C
 from .dataset import GANDataset
 from .dp import DataParallel
@@ -54,200 +53,6 @@ def _scalar_writer(log_dir):
             def close(self):
                 self.f.close()
         return _Jsonl(log_dir)
-
-
-def load_ed_checkpoint(eng: GanEngine, path: str):
-    """train_gan.py:121-128: load_state_dict(strict=False); missing file => random ED with a warning."""
-    if not os.path.exists(path):
-        print(f"[WARN] ED checkpoint not found at {path}. ED will be random!")
-        return False
-    print(f"[INFO] Loading pre-trained Emotion Discriminator from {path}")
-    ckpt = torch.load(path, map_location="cpu")
-    sd = ckpt["model"] if "model" in ckpt else ckpt
-    # strict=False semantics: a key the checkpoint lacks keeps its initial value (reported, not silent -- a spectral-norm
-    # triple with one part missing counts as missing); a key of the wrong shape raises, as load_state_dict does
-    missing, bad = [], []
-    for k in eng.ED.spec:
-        w = spectral_norm_weight(sd, k)
-        if w is None:
-            missing.append(k)
-        elif tuple(w.shape) != tuple(eng.ED.spec[k]):
-            bad.append(f"{k}: checkpoint {tuple(w.shape)} vs model {tuple(eng.ED.spec[k])}")
-        else:
-            eng.ED.p[k].copy_(w.float())
-    for k in eng.EDbuf:
-        if k not in sd:
-            missing.append(k)
-        elif tuple(sd[k].shape) != tuple(eng.EDbuf[k].shape):
-            bad.append(f"{k}: checkpoint {tuple(sd[k].shape)} vs model {tuple(eng.EDbuf[k].shape)}")
-        else:
-            eng.EDbuf[k].copy_(sd[k].float())
-    if bad:
-        raise RuntimeError("Error(s) in loading state_dict for EmotionDiscriminator: size mismatch for " + "; ".join(bad))
-    if missing:
-        print(f"[WARN] ED checkpoint {path} lacks {len(missing)} key(s), left at their initial values: {', '.join(missing)}")
-    eng.fold_ed()          # derived scale / shift / re-laid weights: eagerly, outside any graph
-    return True
-
-
-def spectral_norm_weight(sd: dict, key: str):
-    """sd[key], or -- for a layer the reference wrapped in nn.utils.spectral_norm (`use_spectral_norm`, ed_model.py:29-32,
-    79-82: state_dict keys `<key>_orig`, `<key>_u`, `<key>_v`) -- the weight that wrapper uses in eval mode:
-    weight_orig / sigma with sigma = u^T W v over W = weight_orig flattened to (out, -1), no power iteration.  The GAN step
-    only ever runs the emotion discriminator frozen and in eval mode, so folding sigma in at load time is exact."""
-    if key in sd:
-        return sd[key]
-    if key + "_orig" in sd and key + "_u" in sd and key + "_v" in sd:
-        w = sd[key + "_orig"].double()
-        sigma = torch.dot(sd[key + "_u"].double(), w.flatten(1).mv(sd[key + "_v"].double()))
-        return (w / sigma).float()
-    return None
-
-
-def save_checkpoint(eng: GanEngine, path: str, epoch=None, full=True, ema=None):
-    """train_gan.py:267-282: {'epoch','G','D','E_num','opt_G','opt_D'} every SAVE_FREQ epochs; final {'G','E_num'}.  ema: the
-    block of ema_block() -- one more key, 'ema', of a full checkpoint (the reference's loaders index by key and ignore it)."""
-    sd = eng.state_dicts()
-    if not full:
-        torch.save({"G": sd["G"], "E_num": sd["E_num"]}, path)
-        return
-    betas = tuple(eng.betas)
-    ck = {"epoch": epoch, "G": sd["G"], "D": sd["D"], "E_num": sd["E_num"],
-          "opt_G": adam_state_dict(eng.GE, eng.lr_g, betas), "opt_D": adam_state_dict(eng.D, eng.lr_d, betas)}
-    if ema is not None:
-        ck["ema"] = ema
-    torch.save(ck, path)
-
-
-def ema_block(eng: GanEngine, calib) -> dict:
-    """The `ema` key of a full checkpoint: decay, ramp, offset; 'G' under G's state-dict keys -- the parameters float64 from the
-    shadow, the BatchNorm buffers float32 from `calib` (an EvalEngine that holds the averaged weights, after recalibrate_bn),
-    num_batches_tracked int64 -- and 'E_num', float64."""
-    sd = eng.ema_state_dicts()
-    G = OrderedDict()
-    for k, v in sd["G"].items():
-        G[k] = v
-        if k in ("decoder.deconv.1.bias", "decoder.deconv.4.bias"):     # BN buffers follow weight/bias
-            base = k[:-len("bias")]
-            G[base + "running_mean"] = calib.eng.Gbuf[base + "running_mean"].cpu().clone()
-            G[base + "running_var"] = calib.eng.Gbuf[base + "running_var"].cpu().clone()
-            G[base + "num_batches_tracked"] = torch.tensor(calib.eng.num_batches_tracked, dtype=torch.int64)
-    return {"decay": float(eng.ema_decay), "ramp": bool(eng.ema_ramp), "offset": float(eng.ema_offset), "G": G, "E_num": sd["E_num"]}
-
-
-def save_ema_final(block: dict, path: str):
-    """gan_final_ema.pth: gan_final.pth's keys with the averaged parameters rounded to float32 and the recalibrated buffers --
-    an ordinary generator checkpoint (the reference's app.py loads it as it is)."""
-    f32 = lambda sd: OrderedDict((k, v.float() if v.is_floating_point() else v) for k, v in sd.items())  # noqa: E731
-    torch.save({"G": f32(block["G"]), "E_num": f32(block["E_num"])}, path)
-
-
-def adam_state_dict(fp, lr: float, betas, eps: float = 1e-8, weight_decay: float = 0.0) -> dict:
-    """The flat optimiser state as `torch.optim.Adam.state_dict()` of the reference's optimisers (train_gan.py:136-145:
-    opt_G over list(G.parameters()) + list(E_num.parameters()), opt_D over D.parameters()): parameter i of the optimiser is
-    entry i of the flat buffer's spec (module definition order, the generator's tensors before the numeric encoder's), with
-    its own `step`, `exp_avg`, `exp_avg_sq`.  `optimizer.load_state_dict()` of a reference trainer accepts it as is."""
-    step = float(fp.state[0].item())
-    state = {}
-    for i, k in enumerate(fp.spec):
-        off, n = fp.offsets[k]
-        state[i] = {"step": torch.tensor(step, dtype=torch.float32),
-                    "exp_avg": fp.m[off:off + n].view(fp.spec[k]).detach().cpu().clone(),
-                    "exp_avg_sq": fp.v[off:off + n].view(fp.spec[k]).detach().cpu().clone()}
-    group = {"lr": float(lr), "betas": tuple(float(b) for b in betas), "eps": eps, "weight_decay": weight_decay, "amsgrad": False,
-             "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "params": list(range(len(fp.spec)))}
-    return {"state": state, "param_groups": [group]}
-
-
-def load_adam_state_dict(fp, sd: dict):
-    """Inverse of adam_state_dict (resume): fills the flat moment buffers, the step counter and the running beta powers
-    the update kernel keeps beside it (state = [step, beta1^step, beta2^step, -])."""
-    state = sd["state"]
-    if not state:                       # an optimiser that never stepped: fresh moments
-        fp.m.zero_(); fp.v.zero_(); fp.state.zero_()
-        return
-    if len(state) != len(fp.spec):
-        raise ValueError(f"optimizer state_dict has {len(state)} parameter entries, this optimiser has {len(fp.spec)}")
-    steps = set()
-    for i, k in enumerate(fp.spec):
-        if i not in state:
-            raise ValueError(f"optimizer state_dict lacks entry {i} ({k})")
-        st = state[i]
-        for part in ("exp_avg", "exp_avg_sq"):
-            if tuple(st[part].shape) != tuple(fp.spec[k]):
-                raise ValueError(f"optimizer state_dict entry {i} ({k}).{part}: shape {tuple(st[part].shape)} != {tuple(fp.spec[k])}")
-        steps.add(float(st["step"]))
-    if len(steps) != 1:
-        raise ValueError(f"optimizer state_dict: per-parameter step counts differ ({sorted(steps)}); the flat optimiser keeps one")
-    for i, k in enumerate(fp.spec):
-        off, n = fp.offsets[k]
-        fp.m[off:off + n].copy_(state[i]["exp_avg"].reshape(-1).to(fp.m.device))
-        fp.v[off:off + n].copy_(state[i]["exp_avg_sq"].reshape(-1).to(fp.v.device))
-    step = steps.pop()
-    b1, b2 = sd["param_groups"][0]["betas"]
-    fp.state[0], fp.state[1], fp.state[2] = step, float(b1) ** step, float(b2) ** step
-
-
-def _replay_beta_powers(fp, betas):
-    """The running beta powers exactly as the update kernels hold them after fp.state[0] steps: a product in fp64, one factor
-    per step, of the betas rounded to fp32 (they are float launch arguments).  load_adam_state_dict's closed form differs from
-    it in the last bits (beta2 = 0.9 is not an fp32 number), enough to move single weights of a resumed run by an ulp."""
-    step = int(fp.state[0].item())
-    if step < 1:
-        return
-    b1, b2 = (torch.tensor(float(b), dtype=torch.float32).item() for b in betas)
-    p1 = p2 = 1.0
-    for _ in range(step):
-        p1 *= b1
-        p2 *= b2
-    fp.state[1], fp.state[2] = p1, p2
-
-
-def load_generator_state(eng: GanEngine, ck: dict):
-    """G (with its BatchNorm running statistics) and E_num of a checkpoint dict -- gan_final.pth or gan_epochNNNN.pth, of
-    this trainer or the reference's.  The caller runs eng.params_changed() once everything is loaded."""
-    eng.GE.load({**{"G." + k: v for k, v in ck["G"].items()}, **{"E." + k: v for k, v in ck["E_num"].items()}})
-    for k in eng.Gbuf:
-        eng.Gbuf[k].copy_(ck["G"][k].float())
-
-
-def resume_checkpoint(eng: GanEngine, path: str) -> int:
-    """Continue from a gan_epochNNNN.pth written by save_checkpoint (or by the reference trainer, train_gan.py:267-276):
-    G (with its BatchNorm buffers), D, E_num, both optimisers.  Returns the epoch the checkpoint was written after."""
-    ck = torch.load(path, map_location="cpu")
-    for key in ("G", "D", "E_num", "opt_G", "opt_D"):
-        if key not in ck:
-            raise KeyError(f"{path}: not a full training checkpoint (no '{key}')")
-    load_generator_state(eng, ck)
-    eng.D.load(ck["D"])
-    nbt = [v for k, v in ck["G"].items() if k.endswith("num_batches_tracked")]
-    if nbt:
-        eng.num_batches_tracked = int(nbt[0])
-    load_adam_state_dict(eng.GE, ck["opt_G"])
-    load_adam_state_dict(eng.D, ck["opt_D"])
-    for fp in (eng.GE, eng.D):
-        _replay_beta_powers(fp, eng.betas)
-    eng.params_changed()
-    blk = ck.get("ema")
-    if eng.ema is None:
-        if blk is not None:
-            print(f"[WARN] {path} holds averaged weights ('ema') but EMA_DECAY is 0: the block is ignored and averaging stays off")
-    elif blk is None:
-        eng.ema_reset()         # averaging starts here: the shadow is the resumed weights, the ramp counts from this step
-    else:
-        if float(blk["decay"]) != eng.ema_decay or bool(blk["ramp"]) != eng.ema_ramp:
-            print(f"[WARN] {path}: averaged with EMA_DECAY {blk['decay']} / EMA_RAMP {blk['ramp']}, continuing with "
-                  f"{eng.ema_decay} / {eng.ema_ramp}")
-        shadow = torch.zeros(eng.GE.n, dtype=torch.float64)
-        for k, shape in eng.GE.spec.items():
-            src = blk["G" if k.startswith("G.") else "E_num"][k[2:]]
-            if tuple(src.shape) != tuple(shape):
-                raise ValueError(f"{path}: ema.{k}: shape {tuple(src.shape)} != {tuple(shape)}")
-            o, n = eng.GE.offsets[k]
-            shadow[o:o + n] = src.reshape(-1).to(torch.float64)
-        eng.ema_reset(shadow, float(blk["offset"]))     # its BatchNorm buffers are recomputed at the next save, never resumed
-    return int(ck.get("epoch") or 0)
 
 
 def train(cfg: dict, ed_cfg: dict, ed_ckpt: str, synthetic: int = 0, use_graph: bool = True, resume: str = None,

@@ -57,6 +57,13 @@ def emotion_to_index(emotion):
         return -1
 
 
+def label_indices(emotions, n_classes=4, what: str = "emotion labels"):
+    """The int64 class indices of a split's emotion entries (names, one-hot rows, numbers: emotion_to_index), checked by
+    check_labels; n_classes None: unchecked, unknown names stay -1."""
+    idx = torch.tensor([emotion_to_index(e) for e in emotions], dtype=torch.int64)
+    return idx if n_classes is None else check_labels(idx, n_classes, what)
+
+
 @torch.no_grad()
 def compute_gradient_penalty(D, real_samples, fake_samples, numeric_embedding, device=None, alpha=None):
     """VALUE of the WGAN-GP penalty (utils.py:75-90) for a melo_gan_amd Discriminator: interpolate, critic

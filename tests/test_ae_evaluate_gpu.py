@@ -120,7 +120,7 @@ def test_cli_end_to_end(tmp_path):
     from melo_gan_amd.ae import encode as E
     from melo_gan_amd.ae import evaluate as EV
     from melo_gan_amd.ae.engine import VaeEngine
-    from melo_gan_amd.ae.train_ae import state_dict
+    state_dict = VaeEngine.state_dict
     T = 32
     P, Bf = model(T)
     notes, labels = split(T)

@@ -97,7 +97,7 @@ def test_latent_export_matches_the_oracle_encoder(tmp_path):
     import melo_gan_amd  # noqa: F401
     from melo_gan_amd.ae import encode as E
     from melo_gan_amd.ae.engine import VaeEngine
-    from melo_gan_amd.ae.train_ae import state_dict
+    state_dict = VaeEngine.state_dict
     T, L, B = 32, 8, 4
     spec, bufs = O.vae_spec(T, L)
     P = O.fill_params(spec, 6.0, O.norm_affine_names(spec))

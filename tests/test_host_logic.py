@@ -41,7 +41,7 @@ def test_optimizer_checkpoint_is_a_torch_adam_state_dict():
     import torch
     from collections import OrderedDict
     from melo_gan_amd.gan.engine import FlatParams
-    from melo_gan_amd.gan.train_gan import adam_state_dict, load_adam_state_dict
+    from melo_gan_amd.checkpoints import adam_state_dict, load_adam_state_dict
     spec = OrderedDict([("a.weight", (3, 4)), ("a.bias", (3,)), ("b.weight", (2, 3, 5))])
     fp = FlatParams(spec, "cpu", first="b.weight")           # flat order differs from the spec's order on purpose
     g = torch.Generator().manual_seed(0)
@@ -70,7 +70,7 @@ def test_optimizer_state_dict_is_validated_on_load():
     import torch
     from collections import OrderedDict
     from melo_gan_amd.gan.engine import FlatParams
-    from melo_gan_amd.gan.train_gan import adam_state_dict, load_adam_state_dict
+    from melo_gan_amd.checkpoints import adam_state_dict, load_adam_state_dict
     spec = OrderedDict([("a.weight", (3, 4)), ("a.bias", (3,))])
     fp = FlatParams(spec, "cpu")
     fp.state[0] = 3.0
@@ -93,9 +93,9 @@ def test_optimizer_state_dict_is_validated_on_load():
 
 def test_spectral_norm_checkpoint_weights_fold_at_load():
     """A frozen emotion discriminator trained with use_spectral_norm (ed_model.py:29-32): the weight its eval-mode forward
-    uses is weight_orig / (u^T W v); train_gan.spectral_norm_weight reproduces what torch's wrapper computes."""
+    uses is weight_orig / (u^T W v); checkpoints.spectral_norm_weight reproduces what torch's wrapper computes."""
     import torch
-    from melo_gan_amd.gan.train_gan import spectral_norm_weight
+    from melo_gan_amd.checkpoints import spectral_norm_weight
     torch.manual_seed(0)
     conv = torch.nn.utils.spectral_norm(torch.nn.Conv1d(4, 8, 5, padding=2))
     lin = torch.nn.utils.spectral_norm(torch.nn.Linear(6, 3))

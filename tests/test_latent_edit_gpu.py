@@ -475,3 +475,31 @@ def test_command_with_a_classifier_and_wav(tmp_path):
     # a classifier that does not fit the VAE is refused
     (tmp_path / "ed9.yaml").write_text(yaml.safe_dump(dict(ed_cfg, latent_dim=LAT + 1)))
     assert ED.main(argv[:argv.index("--ed_config")] + ["--ed_config", str(tmp_path / "ed9.yaml"), "--ed_ckpt", str(tmp_path / "ed_best.pth")]) == 2
+
+
+# ---- a real checkpoint file through the VAE's three loaders -------------------------------------------------------------
+def test_one_checkpoint_file_loads_alike_through_editor_evaluator_and_encode(tmp_path):
+    """MAX_NOTES 16, LATENT_DIM 8, batch 2: the smallest VAE the engine takes with two samples in a BatchNorm batch.  One
+    file written from VaeEngine.state_dict(); parameters and buffers bit for bit behind each loader."""
+    from melo_gan_amd.ae import encode
+    from melo_gan_amd.ae.engine import VaeEngine
+    from melo_gan_amd.ae.evaluate import VaeEvaluator
+    cfg = dict(MAX_NOTES=16, LATENT_DIM=8, BATCH_SIZE=2)
+    src = VaeEngine(cfg, "cuda", 2)
+    src.init_weights(5)
+    for i, v in enumerate(src.buf.values()):
+        v.add_(0.125 * (i + 1))
+    src.num_batches_tracked = 4
+    want = src.state_dict()
+    assert all(int(v) == 4 for k, v in want.items() if k.endswith("num_batches_tracked"))
+    ckpt = str(tmp_path / "ae_best.pth")
+    torch.save({"epoch": 1, "model_state": want}, ckpt)
+    editor, evaluator, plain = ED.LatentEditor(cfg, "cuda", 2), VaeEvaluator(cfg, "cuda", 2), VaeEngine(cfg, "cuda", 2)
+    editor.load(ckpt)
+    evaluator.load(ckpt)
+    encode.load_model(plain, ckpt)
+    for name, eng in (("edit", editor.eng), ("evaluate", evaluator.eng), ("encode", plain)):
+        for k in src.P.spec:
+            assert torch.equal(eng.P.p[k].cpu(), want[k]), (name, k)
+        for k in src.buf:
+            assert torch.equal(eng.buf[k].cpu(), want[k]), (name, k)
