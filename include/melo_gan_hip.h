@@ -880,6 +880,47 @@ int mg_pair_knn(const float* A, long nA, const float* B, long nB, int D, int exc
                 size_t work_bytes, mg_stream_t stream);
 int mg_pair_margin(const float* A, long nA, const float* B, long nB, int D, const float* r2B, float* out, void* work,
                    size_t work_bytes, mg_stream_t stream);
+/* ---- Frechet distance and covariance spectra of feature sets (melo_gan_amd.gan.evaluate --feature-metrics --frechet;
+ *      csrc/frechet.hip) ----
+ * The one metric of the feature_space block that is no function of pairwise dot products: it needs second moments and a
+ * symmetric eigensolver, both in fp64.  For row sets X, Y with means mx, my and unbiased covariances Sx, Sy
+ *   FD = |mx - my|^2 + tr Sx + tr Sy - 2 tr (Sx Sy)^(1/2),   tr (Sx Sy)^(1/2) = sum_i sqrt(max(lambda_i(B), 0)),
+ *   B = H^T Sy H,   H = V diag(sqrt(max(w, 0))),   Sx = V diag(w) V^T
+ * B is symmetric positive semi-definite by construction and stays well defined for rank-deficient covariances (fewer rows
+ * than D); no square root of a non-symmetric product is formed.
+ * mg_feat_moments:  X (n, D) contiguous fp32, 16-byte aligned, D a multiple of 4 in 4..256, 2 <= n <= 2^20 -> mean (D) and
+ *                   cov (D, D) fp64, the full matrix, exactly symmetric.  Two passes: column sums / n, then the sum of outer
+ *                   products of the centred rows (fp32 widened to fp64, minus the fp64 mean) on v_mfma_f64_16x16x4_f64,
+ *                   divided by n - 1.  Rows past the end of a 16-row tile and columns past D are zero after centring.
+ * mg_sym_eig:       A (batch, D, D) fp64, D in 1..256, 1 <= batch <= 4096; the symmetric part (A + A^T) / 2 is decomposed.
+ *                   w (batch, D) ascending; V (batch, D, D) or null: orthonormal columns in w's order; info (batch, 2) int32 =
+ *                   {sweeps run, converged 0 / 1}.  Cyclic two-sided Jacobi: one workgroup of 1024 lanes per matrix, barriers
+ *                   only; a sweep is the D - 1 (D odd: D) steps of a round-robin tournament, each step D / 2 disjoint
+ *                   rotations applied as one J^T A J.  A pair is left alone when |a_pq| <= 2^-53 sqrt|a_pp a_qq| or
+ *                   |a_pq| <= 2^-53 |A|_F / m (m = D rounded up to even); t = tan of the angle comes from theta = (a_qq - a_pp) / (2 a_pq) as
+ *                   sign / (|theta| + hypot(1, theta)), never from theta^2.  The solve ends with the first sweep that rotates
+ *                   nothing (that sweep is counted) or after 30 sweeps: converged = 0 then, w = the current diagonal.  The
+ *                   columns of V are normalised once, after the last sweep (their norms drift with c^2 + s^2's rounding).
+ * mg_frechet_pairs: means (S, D), covs (S, D, D) fp64 of S sets (1..4096), D in 1..256; pairs (P, 2) int32 on the device,
+ *                   P in 1..65535, ordered (a, b): H comes from set a.  Launches: one mg_sym_eig of the S covariances (a set is
+ *                   decomposed once however many pairs name it); the batched fp64 product kernel twice (T = S_b H_a, then
+ *                   B = H_a^T T); one eigenvalue-only solve of the P matrices B; one finishing launch.
+ *                   out (P, 4) = {fd, |ma - mb|^2, tr Sa + tr Sb, sum_i sqrt(max(lambda_i, 0))}: fd and the last entry are NaN
+ *                   when set a's or the pair's solve did not converge; all four when a pair names a set outside 0 .. S - 1.
+ *                   spectrum (S, 3) = {participation ratio (sum w)^2 / sum w^2, effective rank exp(-sum p ln p), top-1 share
+ *                   max w / sum w} of each covariance's eigenvalues clamped at 0; NaN when they sum to 0 or the solve did not
+ *                   converge.  info (S + P, 2): mg_sym_eig's, sets first.
+ * Partials (column sums and 16 x 16 tiles per run of rows) and the solver's working copies live in `work`, 16-byte aligned:
+ * mg_frechet_workspace_bytes(n, D, S, P) serves mg_feat_moments on n rows (n = 0: not asked), mg_sym_eig on a batch of S
+ * (P = 0) and mg_frechet_pairs on S sets and P pairs; 0 for sizes outside the limits.  Folds run in a fixed order and there
+ * are no floating-point atomics: two runs, and an eager run and a graph replay, leave identical bits.  Capturable; bad
+ * arguments return -1 before any launch. */
+size_t mg_frechet_workspace_bytes(long n, int D, int S, int P);
+int mg_feat_moments(const float* X, long n, int D, double* mean, double* cov, void* work, size_t work_bytes, mg_stream_t stream);
+int mg_sym_eig(const double* A, int batch, int D, double* w, double* V, int32_t* info, void* work, size_t work_bytes,
+               mg_stream_t stream);
+int mg_frechet_pairs(const double* means, const double* covs, int S, int D, const int32_t* pairs, int P, double* out,
+                     double* spectrum, int32_t* info, void* work, size_t work_bytes, mg_stream_t stream);
 /* The inverse of mg_stage_rows_cursor for one fp32 array: row r of src (rows, width) goes to row
  *   p = (counter[0] - base[0]) * rows + r   of dst (dst_rows, width); rows with p >= dst_rows are dropped (the padded tail of
  * a pass's last batch).  Capturable: a replayed evaluation batch leaves its features at their split position. */

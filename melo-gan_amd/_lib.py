@@ -195,6 +195,10 @@ SIGNATURES = {
     "mg_pair_ksum": (i32, [vp, i64, vp, i64, i32, i32, vp, vp, sz, vp]),
     "mg_pair_knn": (i32, [vp, i64, vp, i64, i32, i32, i32, vp, vp, sz, vp]),
     "mg_pair_margin": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]),
+    "mg_frechet_workspace_bytes": (sz, [i64, i32, i32, i32]),
+    "mg_feat_moments": (i32, [vp, i64, i32, vp, vp, vp, sz, vp]),
+    "mg_sym_eig": (i32, [vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "mg_frechet_pairs": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "mg_scatter_rows_cursor": (i32, [vp, i32, i32, vp, i64, vp, vp, vp]),
     "mg_note_acc_words": (i64, [i32]),
     "mg_note_acc_reset": (i32, [vp, i32, vp]),

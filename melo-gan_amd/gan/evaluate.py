@@ -8,8 +8,8 @@ ed_model.py):
     python -m melo_gan_amd.gan.evaluate --config config/gan_config.yaml \
         [--ckpt <CHECKPOINT_DIR>/gan_final.pth | gan_epochNNNN.pth] [--split <VAL_SPLIT>] [--feats <ENCODER_FEATS_VAL>] \
         [--ed_config config/ed_config.yaml --ed_ckpt data/models/ed/ed_best.pth] [--seed <SEED>] [--batch 64] \
-        [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3] [--tsne]] [--memorisation] [--music-metrics]
-        [--ema]
+        [--out <LOG_DIR>/eval.json] [--synthetic N] [--feature-metrics [--knn-k 3] [--tsne] [--frechet]] [--memorisation]
+        [--music-metrics] [--ema]
 
 --ema evaluates the averaged generator in the `ema` block of a full checkpoint (EMA_DECAY, gan/ema.py) with that checkpoint's
 critic -- the critic has no average; the noise is keyed by (seed, split row), so the same checkpoint and seed with and without
@@ -34,6 +34,11 @@ Jensen-Shannon divergence of seven histograms between real and generated music. 
 --tsne (needs --feature-metrics) lets one LOOK at those features: after the pass the stashed real and generated features are
 embedded jointly by exact t-SNE on the device (gan/tsne.py) and written next to the report as <out stem>_tsne.npy / .svg --
 colour = emotion, marker shape = real / generated -- with a `tsne` block (parameters, final KL, file names) in the report.
+--frechet (needs --feature-metrics) adds the Frechet distance between the real and the generated features -- whole sets, per
+emotion and the real-emotion x generated-emotion table -- and the spectrum of every feature covariance (effective rank,
+participation ratio, top-1 share: a generator collapsed onto a few directions shows a rank far below the real data's).  The
+moments are fp64 (mg_feat_moments), the eigenvalues come from the device's Jacobi solver (mg_frechet_pairs), and the results
+ride in the buffer of the pair kernels' sums: the block is still one device -> host read (gan/feature_metrics.py).
 Every input from outside is checked on the host before any GPU use.
 """
 from __future__ import annotations
@@ -104,6 +109,18 @@ def check_tsne_options(tsne: bool, features: bool, n: Optional[int] = None):
             TS.Tsne().check(2 * int(n), 1)
         except TS.TsneError as e:
             raise EvaluateError(f"--tsne: {e} (the real and the generated rows are embedded jointly: 2 x {n})") from e
+
+
+def check_frechet_options(frechet: bool, features: bool, ed_cfg: Optional[dict] = None):
+    """The Frechet distance is computed from the feature stashes, which only --feature-metrics fills; the moments kernel reads
+    rows of a multiple of 4 in 4..256 features."""
+    if not frechet:
+        return
+    if not features:
+        raise EvaluateError("--frechet needs --feature-metrics: it compares the classifier features that pass stashes")
+    dim = None if ed_cfg is None else ed_cfg.get("notes_hidden")
+    if dim is not None and (int(dim) % 4 or not 4 <= int(dim) <= 256):
+        raise EvaluateError(f"--frechet: notes_hidden = {dim}: the moments kernel reads a multiple of 4 in 4..256 features")
 
 
 def check_music_options(music: bool, cfg: dict, batch: int = DEFAULT_BATCH):
@@ -267,15 +284,19 @@ class Evaluator(EvalEngine):
     """One GanEngine of `batch` rows in eval mode: encoder dropout off, generator BatchNorm on running statistics, no
     optimiser, no update of any buffer.  features: also keep every row's encoder features of the real and the generated roll
     and report the feature-space metrics over them (notes-mode classifier only); knn_k: the manifolds' neighbour count.
-    music: also decode every real and generated row into notes and report the `music` block (NOTE_DIM 4 only)."""
+    music: also decode every real and generated row into notes and report the `music` block (NOTE_DIM 4 only).
+    frechet (needs features): also report the Frechet distance and the covariance spectra of the feature sets."""
     error = EvaluateError
 
     def __init__(self, cfg: dict, ed_cfg: Optional[dict], device="cuda", batch: int = DEFAULT_BATCH, features: bool = False,
-                 knn_k: int = DEFAULT_KNN_K, music: bool = False):
+                 knn_k: int = DEFAULT_KNN_K, music: bool = False, frechet: bool = False):
         from .. import ops
         self.features, self.knn_k, self.music = bool(features), int(knn_k), bool(music)      # _check_config reads them
+        self.frechet = bool(frechet)
         super().__init__(cfg, ed_cfg, device, batch)
         eng = self.eng
+        if self.frechet:
+            check_frechet_options(True, True, {"notes_hidden": eng.ed_feat_dim})
         self.has_d = False                                  # load_critic / copy_from: the critic's weights mean something
         self.ed_real = self.has_ed and eng.ed_mode == "notes"
         d = eng.dev
@@ -290,6 +311,7 @@ class Evaluator(EvalEngine):
 
     def _check_config(self, cfg: dict, ed_cfg: Optional[dict]):
         check_feature_options(self.features, self.knn_k, ed_cfg)
+        check_frechet_options(self.frechet, self.features, ed_cfg)
         check_music_options(self.music, cfg, self.B)
         if ed_cfg is not None:
             check_ed_config(ed_cfg, cfg)
@@ -398,7 +420,8 @@ class Evaluator(EvalEngine):
                 if A is not None and A.shape[0] > k]
         out = Packed([("sums", (n_sums,), torch.float64)] +
                      [(side + tag, (A.shape[0],), torch.float32) for tag, A, _ in sets for side in ("fr", "rf")] +
-                     ([("nn_fake", (n,), torch.float32), ("nn_real", (n,), torch.float32)] if train is not None else []), dev)
+                     ([("nn_fake", (n,), torch.float32), ("nn_real", (n,), torch.float32)] if train is not None else []) +
+                     (self._frechet_parts(R, F, Re, Fe) if self.frechet else []), dev)
         ks = out.dev["sums"]
         slot = iter(range(n_sums))
 
@@ -420,6 +443,8 @@ class Evaluator(EvalEngine):
         if train is not None:
             ops.pair_knn(F, train, out.dev["nn_fake"].view(n, 1))
             ops.pair_knn(R, train, out.dev["nn_real"].view(n, 1))
+        if self.frechet:
+            self._frechet_launches(out.dev)
         host = {name: v.numpy() for name, v in out.host().items()}      # every result of the pair kernels in one read
         hk = host["sums"]
         sums = {"xx": hk[s_xx], "yy": hk[s_yy], "xy": hk[s_xy], "xx_e": [hk[i] for i in s_xx_e], "yy_e": [hk[i] for i in s_yy_e],
@@ -429,7 +454,67 @@ class Evaluator(EvalEngine):
         block = FM.feature_block(R.shape[1], k, EMOTIONS, counts, sums, marg)
         if train is not None:
             block["nn_train"] = FM.nn_summary(host["nn_fake"], host["nn_real"])
+        if self.frechet:
+            self._frechet_entries(block, counts, host)
         return block
+
+    # ---- --frechet: the moments of every set of at least 2 rows, then one mg_frechet_pairs ----
+    def _frechet_parts(self, R, F, Re, Fe):
+        """Plans the sets (whole real, whole fake, every emotion's real and fake slice; fewer than 2 rows: left out) and the
+        pairs (whole x whole, every real emotion x generated emotion); returns their parts of the result buffer."""
+        K = self.K
+        named = [("real", R), ("fake", F)] + [(f"real{e}", Re[e]) for e in range(K)] + [(f"fake{e}", Fe[e]) for e in range(K)]
+        self._fd_sets = [(name, X) for name, X in named if X is not None and X.shape[0] >= 2]
+        at = {name: i for i, (name, _) in enumerate(self._fd_sets)}
+        wanted = [("whole", "real", "fake")] + [((e, f), f"real{e}", f"fake{f}") for e in range(K) for f in range(K)]
+        self._fd_pairs = [(tag, at[a], at[b]) for tag, a, b in wanted if a in at and b in at]
+        S, P = len(self._fd_sets), len(self._fd_pairs)
+        if not P:           # no set on one of the sides: nothing to launch
+            return []
+        return [("fd_out", (P, 4), torch.float64), ("fd_spectrum", (S, 3), torch.float64), ("fd_info", (S + P, 2), torch.int32)]
+
+    def _frechet_launches(self, dev_views):
+        from .. import ops
+        if not self._fd_pairs:
+            return
+        dev, D, S = self.eng.dev, self.eng.ed_feat_dim, len(self._fd_sets)
+        means = torch.empty(S, D, dtype=torch.float64, device=dev)
+        covs = torch.empty(S, D, D, dtype=torch.float64, device=dev)
+        for i, (_, X) in enumerate(self._fd_sets):
+            ops.feat_moments(X, means[i], covs[i])
+        pairs = torch.tensor([[a, b] for _, a, b in self._fd_pairs], dtype=torch.int32).to(dev)
+        ops.frechet_pairs(means, covs, pairs, dev_views["fd_out"], dev_views["fd_spectrum"], dev_views["fd_info"])
+
+    def _frechet_entries(self, block, counts, host):
+        """The host side: NaN (a solve that did not converge) becomes None, with a line on stderr."""
+        K = self.K
+        rows = {"whole": None, "ef": [[None] * K for _ in range(K)]}
+        spectra = {"real": None, "fake": None, "real_e": [None] * K, "fake_e": [None] * K}
+        if self._fd_pairs:
+            S = len(self._fd_sets)
+            out, spec, info = host["fd_out"], host["fd_spectrum"], host["fd_info"]
+            for i, (name, _) in enumerate(self._fd_sets):
+                if not info[i][1]:
+                    print(f"[WARN] frechet: the eigensolver did not converge on the covariance of set '{name}' in "
+                          f"{int(info[i][0])} sweeps: its spectrum and distances are null", file=sys.stderr)
+                triple = tuple(float(v) for v in spec[i])
+                if name in ("real", "fake"):
+                    spectra[name] = triple
+                else:
+                    spectra[name[:4] + "_e"][int(name[4:])] = triple
+            for j, (tag, a, b) in enumerate(self._fd_pairs):
+                if not info[S + j][1]:
+                    print(f"[WARN] frechet: the eigensolver did not converge on pair {tag} in {int(info[S + j][0])} sweeps: "
+                          "its distance is null", file=sys.stderr)
+                row = tuple(float(v) for v in out[j])
+                if tag == "whole":
+                    rows["whole"] = row
+                else:
+                    rows["ef"][tag[0]][tag[1]] = row
+        fb = FM.frechet_block(block["dim"], EMOTIONS, counts, rows, spectra)
+        for name, v in fb.pop("fd_e").items():
+            block["per_emotion"][name]["fd"] = v
+        block.update(fb)
 
     def evaluate(self, dataset, seed: int, noise: Optional[torch.Tensor] = None, train_dataset=None) -> dict:
         """One pass over a resident GANDataset in row order; returns the report.  noise: an (n, NOISE_DIM) resident fp32
@@ -541,6 +626,9 @@ def parse_args(argv=None):
     ap.add_argument("--tsne", action="store_true",
                     help="also embed the real and the generated features jointly by exact t-SNE and write <out stem>_tsne.npy / "
                          ".svg (needs --feature-metrics)")
+    ap.add_argument("--frechet", action="store_true",
+                    help="also report the Frechet distance between the real and the generated features and the spectrum of "
+                         "every feature covariance (needs --feature-metrics)")
     ap.add_argument("--ema", action="store_true", help="evaluate the averaged weights in a full checkpoint's 'ema' block")
     return ap.parse_args(argv)
 
@@ -565,6 +653,7 @@ class Plan:
     music: bool = False
     tsne: bool = False
     ema: bool = False
+    frechet: bool = False
 
 
 def plan(args) -> Plan:
@@ -580,6 +669,8 @@ def plan(args) -> Plan:
         raise EvaluateError(f"--knn-k {knn_k}: must be in 1..{MAX_KNN_K}")
     tsne = bool(getattr(args, "tsne", False))
     check_tsne_options(tsne, features, args.synthetic or None)
+    frechet = bool(getattr(args, "frechet", False))
+    check_frechet_options(frechet, features)
     if features and args.ed_config is None:
         check_feature_options(True, knn_k, None)
     cfg, ckpt_path = G.plan_config(args, EvaluateError)
@@ -598,6 +689,7 @@ def plan(args) -> Plan:
         ed_cfg = read_config(args.ed_config, "ED config", EvaluateError)
         check_ed_config(ed_cfg, cfg, f"ED config {args.ed_config}")
         check_feature_options(features, knn_k, ed_cfg)
+        check_frechet_options(frechet, features, ed_cfg)
         if not os.path.isfile(args.ed_ckpt):
             raise EvaluateError(f"ED checkpoint {args.ed_ckpt} does not exist")
     arrays = None
@@ -615,7 +707,7 @@ def plan(args) -> Plan:
     out = args.out or os.path.join(cfg.get("LOG_DIR", "experiments/gan/logs"), "eval.json")
     seed = args.seed if args.seed is not None else int(cfg.get("SEED", 42))
     return Plan(cfg, ed_cfg, ckpt_path, ckpt, has_critic, args.ed_ckpt, arrays, int(args.synthetic), seed, args.batch, out,
-                features, knn_k, memorisation, train_arrays, music, tsne, ema)
+                features, knn_k, memorisation, train_arrays, music, tsne, ema, frechet)
 
 
 def main(argv=None) -> int:
@@ -638,7 +730,8 @@ def main(argv=None) -> int:
         train_ds = (GANDataset.synthetic(p.synthetic, int(cfg["MAX_NOTES"]), int(cfg["NOTE_DIM"]), int(cfg["LATENT_DIM"]),
                                          int(cfg.get("SEED", 42)), "cuda") if p.synthetic else
                     GANDataset(*p.train_arrays, int(cfg["LATENT_DIM"]), "cuda", resident=True))
-    ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch, features=p.features, knn_k=p.knn_k, music=p.music)
+    ev = Evaluator(cfg, p.ed_cfg, "cuda", p.batch, features=p.features, knn_k=p.knn_k, music=p.music,
+                   frechet=p.frechet)
     weights = ev.load_generator(p.ckpt, ema=p.ema)
     if p.has_critic:
         ev.load_critic(p.ckpt)

@@ -2354,6 +2354,94 @@ def pair_margin(A, B, r2B, out):
     return out
 
 
+FRECHET_MAX_D, FRECHET_MAX_SETS, FRECHET_MAX_PAIRS = 256, 4096, 65535
+
+
+def frechet_workspace(n: int, D: int, S: int, P: int, device) -> Tensor:
+    """A scratch buffer of mg_frechet_workspace_bytes(n, D, S, P), owned by the caller: it serves feat_moments on n rows of
+    width D (n = 0: not asked), sym_eig on a batch of S (P = 0) and frechet_pairs on S sets and P pairs."""
+    nbytes = L.load().mg_frechet_workspace_bytes(int(n), int(D), int(S), int(P))
+    if nbytes == 0:
+        raise ValueError(f"frechet_workspace: n = {n}, D = {D}, S = {S}, P = {P}: n = 0 or 2..2^20 rows (then D a multiple of 4), "
+                         f"D in 1..{FRECHET_MAX_D}, up to {FRECHET_MAX_SETS} sets and {FRECHET_MAX_PAIRS} pairs, something asked")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _frechet_work(who, n, D, S, P, device, work):
+    if work is None:
+        return workspace(L.load().mg_frechet_workspace_bytes(n, D, S, P), device, "frechet")
+    _chk(work, f"{who}: work", dtype=torch.uint8)
+    if work.data_ptr() % 16 or work.numel() < L.load().mg_frechet_workspace_bytes(n, D, S, P):
+        raise ValueError(f"{who}: work must be a 16-byte aligned frechet_workspace({n}, {D}, {S}, {P}, device)")
+    return work
+
+
+def feat_moments(X, mean, cov, work=None):
+    """mean (D) and the unbiased covariance cov (D, D), both fp64, of the rows of X (n, D) fp32 (mg_feat_moments): n in
+    2..2^20, D a multiple of 4 in 4..256; cov is the full matrix, exactly symmetric."""
+    _chk(X, "feat_moments: X")
+    if X.dim() != 2:
+        raise ValueError(f"feat_moments: X (n, D) expected, got {tuple(X.shape)}")
+    n, D = X.shape
+    if not (D % 4 == 0 and 4 <= D <= FRECHET_MAX_D):
+        raise ValueError(f"feat_moments: D must be a multiple of 4 in 4..{FRECHET_MAX_D}")
+    if not 2 <= n <= PAIR_MAX_ROWS:
+        raise ValueError("feat_moments: 2..2^20 rows")
+    if X.data_ptr() % 16:
+        raise ValueError("feat_moments: X must be 16-byte aligned")
+    _chk(mean, "feat_moments: mean", (D,), torch.float64)
+    _chk(cov, "feat_moments: cov", (D, D), torch.float64)
+    work = _frechet_work("feat_moments", n, D, 0, 0, X.device, work)
+    L.check(L.load().mg_feat_moments(_p(X), n, D, _p(mean), _p(cov), _p(work), work.numel(), _stream()), "mg_feat_moments")
+    return mean, cov
+
+
+def sym_eig(A, w, V=None, info=None, work=None):
+    """The eigenvalues w (batch, D), ascending, and (V given) the orthonormal eigenvectors V (batch, D, D), columns in w's
+    order, of the symmetric fp64 matrices A (batch, D, D) (mg_sym_eig: cyclic Jacobi, at most 30 sweeps); info (batch, 2) int32
+    = {sweeps, converged}.  Returns (w, V, info)."""
+    _chk(A, "sym_eig: A", dtype=torch.float64)
+    if A.dim() != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError(f"sym_eig: A (batch, D, D) expected, got {tuple(A.shape)}")
+    batch, D = A.shape[0], A.shape[1]
+    if not (1 <= D <= FRECHET_MAX_D and 1 <= batch <= FRECHET_MAX_SETS):
+        raise ValueError(f"sym_eig: D in 1..{FRECHET_MAX_D} and 1..{FRECHET_MAX_SETS} matrices")
+    _chk(w, "sym_eig: w", (batch, D), torch.float64)
+    if V is not None:
+        _chk(V, "sym_eig: V", (batch, D, D), torch.float64)
+    if info is None:
+        info = torch.zeros(batch, 2, dtype=torch.int32, device=A.device)
+    _chk(info, "sym_eig: info", (batch, 2), torch.int32)
+    work = _frechet_work("sym_eig", 0, D, batch, 0, A.device, work)
+    L.check(L.load().mg_sym_eig(_p(A), batch, D, _p(w), _p(V), _p(info), _p(work), work.numel(), _stream()), "mg_sym_eig")
+    return w, V, info
+
+
+def frechet_pairs(means, covs, pairs, out, spectrum, info, work=None):
+    """The Frechet distances of P ordered pairs of S sets given by their fp64 moments (mg_frechet_pairs): means (S, D),
+    covs (S, D, D), pairs (P, 2) int32 on the device -> out (P, 4) = {fd, mean term, trace term, sqrt term}, spectrum (S, 3) =
+    {participation ratio, effective rank, top-1 share} and info (S + P, 2) int32 = {sweeps, converged}, sets first."""
+    _chk(means, "frechet_pairs: means", dtype=torch.float64)
+    _chk(covs, "frechet_pairs: covs", dtype=torch.float64)
+    if means.dim() != 2 or covs.dim() != 3 or tuple(covs.shape) != (means.shape[0], means.shape[1], means.shape[1]):
+        raise ValueError(f"frechet_pairs: means (S, D) and covs (S, D, D) expected, got {tuple(means.shape)} and "
+                         f"{tuple(covs.shape)}")
+    S, D = means.shape
+    _chk(pairs, "frechet_pairs: pairs", dtype=torch.int32)
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"frechet_pairs: pairs (P, 2) expected, got {tuple(pairs.shape)}")
+    P = pairs.shape[0]
+    if not (1 <= D <= FRECHET_MAX_D and 1 <= S <= FRECHET_MAX_SETS and 1 <= P <= FRECHET_MAX_PAIRS):
+        raise ValueError(f"frechet_pairs: D in 1..{FRECHET_MAX_D}, 1..{FRECHET_MAX_SETS} sets and 1..{FRECHET_MAX_PAIRS} pairs")
+    _chk(out, "frechet_pairs: out", (P, 4), torch.float64)
+    _chk(spectrum, "frechet_pairs: spectrum", (S, 3), torch.float64)
+    _chk(info, "frechet_pairs: info", (S + P, 2), torch.int32)
+    work = _frechet_work("frechet_pairs", 0, D, S, P, means.device, work)
+    L.check(L.load().mg_frechet_pairs(_p(means), _p(covs), S, D, _p(pairs), P, _p(out), _p(spectrum), _p(info), _p(work),
+                                      work.numel(), _stream()), "mg_frechet_pairs")
+    return out, spectrum, info
+
+
 def scatter_rows_cursor(src, dst, counter, base):
     """stage_rows_cursor's inverse (mg_scatter_rows_cursor): row r of src (rows, width) goes to row (counter - base) * rows + r
     of dst (dst_rows, width); rows past dst's end are dropped.  counter / base: int64 device scalars (1,)."""
