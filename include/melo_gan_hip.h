@@ -493,7 +493,8 @@ int mg_stage_rows_cursor(const mg_stage_job* jobs, int n_jobs, int n_rows, const
  *     row += noise_std * N(0,1); dropout_prob > 0: a time row is kept with probability 1 - p, else ALL its columns become 0;
  *     pitch_shift_prob > 0: per sample, with that probability, column 0 of every row += +1 or -1 (equal odds; dropped rows too).
  *   MG_AUG_AE (src/ae/dataset.py:11-38,89-104): five per-sample gates with odds 0.3 / 0.3 / 0.2 / 0.3 / 0.2, in order: columns
- *     1, 2 *= 1 + U(-tempo_jitter, tempo_jitter) (one factor per sample); column 0 += randint(-pitch_shift, pitch_shift)
+ *     1, 2 *= 1 + U(-tempo_jitter, tempo_jitter) (one factor per sample: 1 + (2u - 1) * tempo_jitter in fp32, the product and
+ *     the sum each rounded on its own); column 0 += randint(-pitch_shift, pitch_shift)
  *     (inclusive); time rows dropped with probability note_dropout; column 3 += N(0, velocity_jitter); column 1 +=
  *     N(0, timing_jitter) then max(., 0) -- the last two also on dropped rows.  (The reference's nan_to_num is a no-op on
  *     finite input and is not restated.)
@@ -531,8 +532,13 @@ int mg_ed_metrics_acc(const float* logits, const int64_t* labels, const float* l
 /* ---- per-step random inputs (replaces torch.randn / torch.rand / nn.Dropout's bernoulli draws:
  *      src/gan/train_gan.py:188,218; src/gan/utils.py:76; src/gan/feature_encoder.py:34) in ONE launch:
  *      normal[n_normal] ~ N(0,1), uniform[n_uniform] ~ U(0,1), mask{0,1} = keep-mask * 1/(1-p_drop).
+ *      A uniform is (k + 0.5) 2^-24 for the top 24 bits k of its Philox word, clamped to 1 - 2^-24: range [2^-25, 1 - 2^-24],
+ *      never 0 and never 1.  A mask element is kept when its uniform >= p_drop.
  *      Philox4x32-10 keyed by `seed`; *step_counter (device, uint64) is read and then advanced on device,
  *      so a captured hipGraph draws fresh numbers at every replay.  Any tensor pointer may be NULL.
+ *      Counter = (q, (q >> 32) ^ (jid << 28), step lo, step hi): q the block of elements 4q .. 4q + 3 (one word each for a
+ *      uniform or a mask, Box-Muller on the word pairs (0, 1) and (2, 3) for the normals), jid the tensor's place among the
+ *      non-NULL ones in the order normal, uniform, mask0, mask1.  tests/draw_ref.py restates every layout on the host.
  *      Riders (each NULL: absent):
  *        adam_state:  *step_counter is NOT advanced here; instead the Adam state of the optimiser whose update will consume the
  *                     draws is advanced (it is not read by this launch).  Pair it with mg_adam_flat(state_ticked = 1), which

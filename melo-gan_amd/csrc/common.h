@@ -227,7 +227,8 @@ __device__ __forceinline__ void mg_epilogue_column(const mg_epilogue& E, V& a, i
 }
 
 // Philox4x32-10 (Salmon et al., SC'11): ten rounds over a 4-word counter under a 2-word key; u01 maps a word to (0, 1).
-// The counter layouts are their users' (small_kernels.hip: rng_fill_kernel, gen_inputs_kernel, aug_draw; mlp_train.hip).
+// The counter layouts are their users' (small_kernels.hip: rng_fill_kernel, gen_inputs_kernel, aug_draw; mlp_train.hip;
+// eval_metrics.hip: eval_noise_kernel; latent_edit.hip: latent_rows_kernel).  tests/draw_ref.py restates all of this.
 __device__ __forceinline__ void philox_round(unsigned (&c)[4], unsigned k0, unsigned k1) {
     const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
     const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
@@ -243,7 +244,11 @@ __device__ __forceinline__ void philox4(unsigned (&c)[4], unsigned k0, unsigned 
         k1 += 0xBB67AE85u;
     }
 }
-__device__ __forceinline__ float u01(unsigned x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+// The top 24 bits k of the word -> (k + 0.5) 2^-24, range [2^-25, 1 - 2^-24].  k = 2^24 - 1 alone needs the clamp: 16777215.5
+// is a tie that rounds to 2^24, which would give 1.0f; every other word keeps the value it always had.
+__device__ __forceinline__ float u01(unsigned x) {
+    return fminf(((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+}
 // four N(0,1) draws from one Philox output block (Box-Muller on the pairs (c0, c1) and (c2, c3))
 __device__ __forceinline__ void box_muller4(const unsigned (&c)[4], float (&v)[4]) {
     const float r0 = sqrtf(-2.f * logf(u01(c[0]))), r1 = sqrtf(-2.f * logf(u01(c[2])));

@@ -275,11 +275,6 @@ __global__ void eval_reset_kernel(long long* acc, const EvalLayout L, int K, int
 
 // Evaluation noise: one workgroup per batch row, Philox counter (element block, EVAL_TAG, split row lo, split row hi).
 constexpr unsigned EVAL_TAG = 0x4556414Cu;      // apart from mg_rng_fill (< 0x40000000), mg_stage_augment (0x415547xx), mg_gen_inputs (0x47454Exx)
-__device__ __forceinline__ void eval_box_muller4(const unsigned (&c)[4], float (&v)[4]) {
-    const float r0 = sqrtf(-2.f * logf(u01(c[0]))), r1 = sqrtf(-2.f * logf(u01(c[2])));
-    const float t0 = 6.28318530717958647692f * u01(c[1]), t1 = 6.28318530717958647692f * u01(c[3]);
-    v[0] = r0 * cosf(t0); v[1] = r0 * sinf(t0); v[2] = r1 * cosf(t1); v[3] = r1 * sinf(t1);
-}
 __global__ __launch_bounds__(64) void eval_noise_kernel(float* __restrict__ noise, int rows, int noise_dim,
                                                         const unsigned long long* __restrict__ counter,
                                                         const unsigned long long* __restrict__ base, unsigned long long n,
@@ -291,7 +286,7 @@ __global__ __launch_bounds__(64) void eval_noise_kernel(float* __restrict__ nois
         unsigned c[4] = {(unsigned)qb, EVAL_TAG, (unsigned)i, (unsigned)(i >> 32)};
         philox4(c, (unsigned)seed, (unsigned)(seed >> 32));
         float v[4];
-        eval_box_muller4(c, v);
+        box_muller4(c, v);       // csrc/common.h
         for (int j = 0; j < 4; ++j) {
             const int col = 4 * qb + j;
             if (col < noise_dim) noise[(long)r * noise_dim + col] = pad ? 0.f : v[j];

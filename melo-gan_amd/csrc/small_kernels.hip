@@ -882,7 +882,7 @@ __global__ void act_bwd_kernel(const float* __restrict__ dy, const float* __rest
 // step lo, step hi); the step counter lives in device memory and is advanced by the kernel itself so a
 // captured hipGraph draws fresh numbers on every replay.
 // philox4 / u01: csrc/common.h (csrc/mlp_train.hip draws its dropout masks from the same streams)
-// box_muller4: csrc/common.h too (csrc/latent_edit.hip draws its normals through it)
+// box_muller4: csrc/common.h too (csrc/latent_edit.hip and csrc/eval_metrics.hip draw their normals through it)
 
 struct RngJob { float* dst; long n; int kind; float p0; };   // kind 0: N(0,1); 1: U(0,1); 2: keep-mask*(1/(1-p0))
 struct RngJobs { RngJob j[4]; int njobs; };
@@ -1180,6 +1180,7 @@ __device__ __forceinline__ AugSample aug_sample(const mg_augment& A, unsigned lo
         aug_draw(c, 0u, AUG_GATES, serial, A.seed);
         aug_draw(g, 0u, AUG_GATES2, serial, A.seed);
         if (A.tempo_jitter > 0.f && u01(c[0]) < 0.3f) {
+#pragma clang fp contract(off)      // the product and the sum rounded on their own (tests/draw_ref.py), not one fma
             S.scale = true;
             S.factor = 1.f + (2.f * u01(g[1]) - 1.f) * A.tempo_jitter;
         }
